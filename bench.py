@@ -2,13 +2,19 @@
 """bench.py — triplet-updates/s of the fused MI355X training step at BASELINE.json's C2
 (n=m=4096, d=64, p=0.01, random triplets, fp32, B=64, Adam lr=1e-3 wd=1e-5).
 
-  python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N>1: launched by torch.distributed.run)
 
 A "step" is one optimiser step = one pass of the hot path over one batch of 64 synthetic triplets.
 Steps are consumed the way train_model consumes them: epoch by epoch (1049 steps per epoch at C2, the
 last batch short), a fresh permutation per epoch, and the no-grad validation pass after every complete
 epoch.  Inputs are resident in HBM when the timed region starts.
 Prints ONE JSON line (rank 0).
+
+A plain run measures the headline only: set-up, the untimed clock ramp, W warm-up steps, the K timed steps
+(`value`, `ms_per_step`; `roofline` from the timed region's own event pairs when it holds >= 256 steps), the
+outputs if --dump-outputs is given, the line.  --full adds what takes runs of its own: `roofline.kernel_only`,
+`steady_state`, `uvt` and `cpu_baseline` (--no-extras / --no-cpu-baseline drop some of them again), and on the
+multi-GPU path the phase split, cost model and C4 sub-record.
 """
 import argparse
 import json
@@ -226,6 +232,7 @@ class Runner:
         engine.reserve_workspace(self.train.N, cfg["B"], cfg["n"], cfg["m"], cfg["d"], dev)
         self.event_pool = [torch.cuda.Event(enable_timing=True) for _ in range(64)]
         self.loss_bufs = {}
+        self.last_loss, self.call_lengths = None, []
 
     def _event(self):
         return self.event_pool.pop() if self.event_pool else torch.cuda.Event(enable_timing=True)
@@ -257,6 +264,9 @@ class Runner:
             if buf is None:
                 buf = self.loss_bufs[take] = torch.empty(take, dtype=torch.float32, device=self.dev)
             self.engine.train_steps(bind, self.stream[lo:hi], B, loss_out=buf, defer_step=True)
+            if bind is self.bind:
+                self.last_loss = buf            # the per-step losses the most recent call on the measured model returned
+                self.call_lengths.append(take)
             if record:
                 e1.record()
                 self.train_events.append((e0, e1, take))
@@ -567,6 +577,34 @@ def uvt_record(dev, U2, V2):
     return out
 
 
+DUMP_LIMIT_BYTES = 60 << 20      # every file of a dump together, .npy headers included, stays under 64 MB
+
+
+def dump_outputs(runner, out_dir):
+    """--dump-outputs: what the timed path handed its caller after its last step, as float32 `out_dir/<name>.npy` —
+    the factor tables U and V and the Adam moments of both (the fused step updates the caller's model and
+    torch.optim.Adam state in place), and `loss`, the per-step batch-mean losses of the timed region's last call.
+    When the tables would take the files past DUMP_LIMIT_BYTES in all (C4), each table keeps a fixed, seeded sample
+    of its rows, the same in every run and for every table of the same height.  Returns a summary."""
+    os.makedirs(out_dir, exist_ok=True)
+    U, V, mU, vU, mV, vV = runner.bind.tensors()
+    tables = {"U": U, "V": V, "U_exp_avg": mU, "U_exp_avg_sq": vU, "V_exp_avg": mV, "V_exp_avg_sq": vV}
+    loss = runner.last_loss.float().cpu().numpy()
+    table_bytes = sum(t.numel() * 4 for t in tables.values())
+    keep = min(1.0, (DUMP_LIMIT_BYTES - loss.nbytes - 8 * 4096) / table_bytes)
+    rows = {}
+    for name, t in tables.items():
+        n = t.shape[0]
+        if keep < 1.0 and n not in rows:
+            k = int(n * keep)
+            rows[n] = torch.from_numpy(np.sort(np.random.default_rng(n).choice(n, k, replace=False))).to(t.device)
+        a = (t.index_select(0, rows[n]) if keep < 1.0 else t).float().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    np.save(os.path.join(out_dir, "loss.npy"), loss)
+    return {"dir": out_dir, "files": sorted(tables) + ["loss"], "dtype": "float32",
+            "rows_kept": "all" if keep >= 1.0 else {str(n): int(r.numel()) for n, r in rows.items()}}
+
+
 def relaunch_multi_gpu(n_gpus):
     """`python bench.py --gpus N` outside torch.distributed.run: start N ranks ourselves (one process per GPU, RCCL over
     xGMI), relay rank 0's JSON line and exit with the children's status.  Runs BEFORE this process touches the GPU."""
@@ -591,6 +629,8 @@ def relaunch_multi_gpu(n_gpus):
 def main():
     ap = build_parser()
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.dp_mode):
+        ap.error("--dump-outputs covers the single-GPU path only (no --dp-mode, --gpus 1)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_multi_gpu(args.gpus)
     with _StdoutToStderr():
@@ -604,8 +644,16 @@ def build_parser():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10490)   # 10 epochs of C2
     ap.add_argument("--warmup", type=int, default=1049)   # 1 epoch
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the steady_state and uvt records (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the kernel-only sample and its offline / "
+                         "chain-model records, steady_state, uvt and cpu_baseline (multi-GPU: phase split, cost model, "
+                         "C4 sub-record)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (factor tables, Adam moments, the last call's "
+                         "losses) as float32 DIR/<name>.npy; see dump_outputs()")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline record")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the steady_state and uvt records (profiling runs)")
     ap.add_argument("--steady-epochs", type=int, default=5, help="full epochs of the steady_state record (>= 3)")
     ap.add_argument("--clock-ramp", type=float, default=0.3, metavar="SECONDS",
                     help="untimed busy phase on scratch state in front of the timed region (0 = none); see clock_ramp()")
@@ -662,7 +710,8 @@ def _run(args):
         if args.tune:
             from mfcd import engine as _eng
             _eng.set_tuning(**{k: int(v) for k, v in (kv.split("=", 1) for kv in args.tune)})
-        out = mdist.bench_data_parallel(cfg, dev, args.steps, args.warmup, args.seed, mode=args.dp_mode or "native")
+        out = mdist.bench_data_parallel(cfg, dev, args.steps, args.warmup, args.seed, mode=args.dp_mode or "native",
+                                        extras=args.full)
         dist.destroy_process_group()
         return out, rank == 0
 
@@ -680,6 +729,7 @@ def _run(args):
     ramp = clock_ramp(runner, args.clock_ramp, max(1, min(args.steps, runner.steps_per_epoch))) if args.clock_ramp > 0 else None
     runner.run(args.warmup)
     torch.cuda.synchronize()
+    runner.call_lengths = []
     t0 = time.perf_counter()
     # a HIP event pair around a call costs ~10 us of host + queue time (tools/exp_driver_call.py: 61 -> 51 us for the
     # driver's 20-step call): long runs are bracketed inside the timed region, a short one by an identical call right after
@@ -688,7 +738,9 @@ def _run(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     engine.check_status()   # a resident launch that gave up on a bounded wait would invalidate the number
-    if not in_region:
+    timed_calls = runner.call_lengths
+    dumped = dump_outputs(runner, args.dump_outputs) if args.dump_outputs else None
+    if not in_region and args.full:
         runner.run(args.steps, record=True)
         torch.cuda.synchronize()
 
@@ -696,7 +748,7 @@ def _run(args):
     train_ms = sum(a.elapsed_time(b) for a, b, _ in runner.train_events)
     period_us = train_ms * 1e3 / max(launches, 1)          # HIP events around the fused-step calls, gaps included
     # the form the timed calls took: the longest call of the timed region decides what the record describes
-    longest = max((k for _, _, k in runner.train_events), default=args.steps)
+    longest = max((k for _, _, k in runner.train_events), default=max(timed_calls))
     plan = engine.train_plan(min(longest * cfg["B"], runner.train.N), cfg["B"], cfg["n"], cfg["m"], cfg["d"], bf16=bf16)
     big = getattr(runner.bind, "_big", None)
     used_big = bool(big) and big.ws is not None and longest >= engine.BIG_MIN_STEPS     # engine.train_steps took csrc/big.hip
@@ -714,7 +766,8 @@ def _run(args):
                    "train_samples": runner.train.N, "parallelism": "single", "step_form": plan["form_name"]},
     }
     kstep = kone = None
-    if not bf16 and not used_big:       # (the timed twin exists for the library's own forms; the big form is priced on the call)
+    # (the timed twin exists for the library's own forms; the big form is priced on the call)
+    if args.full and not bf16 and not used_big:
         # the dominant kernel alone, for a call of the timed call's length: HIP event pair directly around its launch inside
         # the library (mfcd_train_steps_timed).  This is the figure a `rocprofv3 --kernel-trace --stats` of the same command
         # shows as that kernel's average duration, and what `achieved` / `frac` are priced on; `call_level` brackets the
@@ -724,9 +777,10 @@ def _run(args):
         per_launch = 1 if plan["form_name"] == "streaming" else klen      # streaming: one launch per optimiser step
         kone = {"steps_per_launch": per_launch, "kernel_launch_us": round(kstep * per_launch, 2),
                 "kernel_us_per_step": round(kstep, 4)}
-    out["roofline"] = roofline_record(cfg, plan, period_us, kernel_step_us=kstep)
-    out["roofline"]["period_from"] = ("HIP event pairs around the calls of the timed region" if in_region else
-                                      "HIP event pair around an identical call issued right after the timed region")
+    if runner.train_events:     # (a plain run of fewer than 256 steps records no event pair: no roofline without --full)
+        out["roofline"] = roofline_record(cfg, plan, period_us, kernel_step_us=kstep)
+        out["roofline"]["period_from"] = ("HIP event pairs around the calls of the timed region" if in_region else
+                                          "HIP event pair around an identical call issued right after the timed region")
     if kone:
         off = offline_kernel_stats(cfg, plan, kone["steps_per_launch"])
         if off:
@@ -737,7 +791,9 @@ def _run(args):
         out["roofline"]["kernel_only"] = kone
     if ramp:
         out["clock_ramp"] = ramp
-    if not args.no_extras:
+    if dumped:
+        out["outputs"] = dumped
+    if args.full and not args.no_extras:
         # ---- steady state: whole epochs in this same process (what a training run sees; --steps may be far shorter) ----
         E = max(3, args.steady_epochs)
         runner.run(runner.steps_per_epoch - runner.pos if runner.stream is not None else 0)   # finish the open epoch
@@ -772,7 +828,7 @@ def _run(args):
             "roofline": roofline_record(cfg, splan, ev_us, (kavg, kmin, kmax), kernel_step_us=None if bf16 else kavg)}
         out["uvt"] = uvt_record(dev, runner.model.U.data, runner.model.V.data)
     runner.bind.flush()     # (the Adam step counters were deferred; ADVICE r2: never leave them stale)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, args.seed)
     return out, True
 

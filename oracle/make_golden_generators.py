@@ -4,8 +4,10 @@
 Imports the *unmodified* reference (structure.generate_X, structure.py:590-663, over generation_data.py:346-715) and
 stores, per `generation` keyword, the matrix X it returns under fixed seeds of the three generators the laws draw from
 (torch, numpy, and Python's `random` — networkx's small-world graph uses the latter), plus one draw from each taken right
-after the call.  "graph" is absent: the reference raises TypeError for it (a stray comma at generation_data.py:565 turns
-`noise` into a tuple).  Only data is committed (tests/golden/generators.npz).
+after the call, and for the generators that decompose a matrix ("svd") the argument and result of that one
+`torch.svd` call, which the test replays: the signs and last bits of a LAPACK SVD depend on the host's CPU and math
+library, and the generator's matrix with them.  "graph" is absent: the reference raises TypeError for it (a stray
+comma at generation_data.py:565 turns `noise` into a tuple).  Only data is committed (tests/golden/generators.npz).
 
 Usage:  OMP_NUM_THREADS=4 PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden_generators.py
 """
@@ -26,6 +28,18 @@ import torch  # noqa: E402
 
 import structure as R  # noqa: E402  (the reference)
 
+_svd, _svd_calls = torch.svd, []
+
+
+def _recording_svd(a, *args, **kw):
+    """torch.svd itself; records its argument and (U, S, V) for the fixture."""
+    res = _svd(a, *args, **kw)
+    _svd_calls.append([t.detach().cpu().numpy().copy() for t in (a,) + tuple(res)])
+    return res
+
+
+torch.svd = _recording_svd
+
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "generators.npz")
 CASES = [("base", 24, 18, 4, {}), ("low_rank", 24, 18, 5, {"rank": 3}), ("low_rank", 10, 30, 4, {}), ("clustered", 24, 18, 4, {}),
          ("structured", 24, 18, 4, {}), ("svd", 24, 18, 4, {}), ("correlated", 24, 18, 4, {}), ("social", 24, 18, 4, {}),
@@ -38,7 +52,12 @@ def main():
         torch.manual_seed(300 + k)
         np.random.seed(300 + k)
         random.seed(300 + k)
+        _svd_calls.clear()
         X = R.generate_X(n, m, d, "cpu", generation=g, **kw)
+        if _svd_calls:
+            assert len(_svd_calls) == 1, (g, len(_svd_calls))
+            for key, a in zip(("svd_in", "svd_U", "svd_S", "svd_V"), _svd_calls[0]):
+                out[f"{k}.{key}"] = a
         out[f"{k}.X"] = X.detach().cpu().numpy().copy()
         out[f"{k}.after"] = np.asarray([float(torch.rand(1, dtype=torch.float64)), float(np.random.random_sample()),
                                         random.random()])

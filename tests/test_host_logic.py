@@ -336,16 +336,30 @@ def _golden_generator_cases():
 
 
 @pytest.mark.parametrize("k,case", list(enumerate(_golden_generator_cases()[1])))
-def test_ground_truth_generators_reproduce_the_reference_matrices(k, case):
+def test_ground_truth_generators_reproduce_the_reference_matrices(k, case, monkeypatch):
     """tests/golden/generators.npz holds what the UNMODIFIED reference's generate_X returned per `generation` keyword
     under fixed torch / numpy / `random` seeds (oracle/make_golden_generators.py; structure.py:590-663 over
     generation_data.py:346-715): the restated generators draw in the same order and return the same matrix, and leave
-    the three generators in the same state.  (The host side of generate_X is device-agnostic: built on the CPU here.)"""
+    the three generators in the same state.  (The host side of generate_X is device-agnostic: built on the CPU here.)
+    The one `torch.svd` call ("svd") is replayed from the fixture after its argument is checked bit for bit: the signs
+    and last bits of a LAPACK SVD differ between hosts (CPU model, math-library code path), and the matrix with them."""
     import random
     import generation_data as G
     z, _ = _golden_generator_cases()
     g, n, m, d, rank = case.split(":")
     n, m, d, rank = int(n), int(m), int(d), int(rank)
+    svd_calls = []
+    if f"{k}.svd_in" in z.files:
+        live_svd = torch.svd
+
+        def replay_svd(a, *args, **kw):
+            np.testing.assert_array_equal(a.numpy(), z[f"{k}.svd_in"])
+            svd_calls.append(a)
+            # the live call's memory layout (LAPACK's column-major factors: torch's randn_like draws in layout order)
+            live = live_svd(a, *args, **kw)
+            return tuple(torch.empty_strided(t.shape, t.stride(), dtype=t.dtype).copy_(
+                torch.from_numpy(z[f"{k}.svd_{w}"])) for t, w in zip(live, "USV"))
+        monkeypatch.setattr(torch, "svd", replay_svd)
     torch.manual_seed(300 + k)
     np.random.seed(300 + k)
     random.seed(300 + k)
@@ -360,6 +374,7 @@ def test_ground_truth_generators_reproduce_the_reference_matrices(k, case):
         A, B = getattr(G, f"generate_{g}_embeddings")(n, m, d, device="cpu")
         X = A @ B.t()
     want = z[f"{k}.X"]
+    assert len(svd_calls) == (1 if f"{k}.svd_in" in z.files else 0)
     assert tuple(X.shape) == want.shape
     np.testing.assert_allclose(X.numpy(), want, rtol=0, atol=1e-6 * max(1.0, float(np.abs(want).max())))
     after = [float(torch.rand(1, dtype=torch.float64)), float(np.random.random_sample()), random.random()]

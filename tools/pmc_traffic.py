@@ -1,5 +1,5 @@
 """Builds profiles/pmc_traffic.json from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE; --kernel-trace only) of
-`bench.py --no-cpu-baseline --steps 2098 --warmup 1049`: memory-side bytes of the resident step kernel per optimiser
+`bench.py --full --no-cpu-baseline --steps 2098 --warmup 1049`: memory-side bytes of the resident step kernel per optimiser
 step.  usage: pmc_traffic.py <dir with the FETCH_SIZE pass> <dir with the WRITE_SIZE pass> <out.json>"""
 import csv, glob, json, sys
 

@@ -6,15 +6,15 @@ mkdir -p $E
 cd $R
 if [ "$1" = "bench" ]; then
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $E/gpu_tests.log 2>&1; tail -1 $E/gpu_tests.log
-timeout -k 10 400 python bench.py > $E/bench_c2_default.json 2> $E/bench_c2_default.err; cut -c1-220 $E/bench_c2_default.json
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $E/bench_c2_driver_cmd.json 2>/dev/null; cut -c1-220 $E/bench_c2_driver_cmd.json
-timeout -k 10 300 python bench.py --workload C3 --steps 3356 --warmup 1678 --no-cpu-baseline > $E/bench_c3_f32.json 2>/dev/null; cut -c1-200 $E/bench_c3_f32.json
-timeout -k 10 300 python bench.py --workload C3 --factor-dtype bf16 --steps 3356 --warmup 1678 --no-cpu-baseline > $E/bench_c3_bf16.json 2>/dev/null; cut -c1-200 $E/bench_c3_bf16.json
-timeout -k 10 300 python bench.py --workload C4 --steps 2000 --warmup 200 --no-cpu-baseline --no-extras > $E/bench_c4_single.json 2>/dev/null; cut -c1-200 $E/bench_c4_single.json
-timeout -k 10 300 python bench.py --dp-mode native --no-cpu-baseline --steps 2098 --warmup 1049 > $E/bench_c2_dp_native_one_rank.json 2>/dev/null; cut -c1-200 $E/bench_c2_dp_native_one_rank.json
-timeout -k 10 300 python bench.py --dp-mode shard --no-cpu-baseline --steps 2098 --warmup 1049 > $E/bench_c2_shard_one_rank.json 2>/dev/null; cut -c1-200 $E/bench_c2_shard_one_rank.json
-timeout -k 10 300 python bench.py --workload C4 --dp-mode shard --no-cpu-baseline --no-extras --steps 2000 --warmup 200 > $E/bench_c4_shard_one_rank.json 2>/dev/null; cut -c1-200 $E/bench_c4_shard_one_rank.json
-timeout -k 10 300 python bench.py --workload C4 --dp-mode shard --tune shard_pipeline=0 --no-cpu-baseline --no-extras --steps 2000 --warmup 200 > $E/bench_c4_shard_one_rank_strict.json 2>/dev/null; cut -c1-200 $E/bench_c4_shard_one_rank_strict.json
+timeout -k 10 400 python bench.py --full > $E/bench_c2_default.json 2> $E/bench_c2_default.err; cut -c1-220 $E/bench_c2_default.json
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $E/bench_c2_driver_cmd.json 2>/dev/null; cut -c1-220 $E/bench_c2_driver_cmd.json
+timeout -k 10 300 python bench.py --full --workload C3 --steps 3356 --warmup 1678 --no-cpu-baseline > $E/bench_c3_f32.json 2>/dev/null; cut -c1-200 $E/bench_c3_f32.json
+timeout -k 10 300 python bench.py --full --workload C3 --factor-dtype bf16 --steps 3356 --warmup 1678 --no-cpu-baseline > $E/bench_c3_bf16.json 2>/dev/null; cut -c1-200 $E/bench_c3_bf16.json
+timeout -k 10 300 python bench.py --full --workload C4 --steps 2000 --warmup 200 --no-cpu-baseline --no-extras > $E/bench_c4_single.json 2>/dev/null; cut -c1-200 $E/bench_c4_single.json
+timeout -k 10 300 python bench.py --full --dp-mode native --no-cpu-baseline --steps 2098 --warmup 1049 > $E/bench_c2_dp_native_one_rank.json 2>/dev/null; cut -c1-200 $E/bench_c2_dp_native_one_rank.json
+timeout -k 10 300 python bench.py --full --dp-mode shard --no-cpu-baseline --steps 2098 --warmup 1049 > $E/bench_c2_shard_one_rank.json 2>/dev/null; cut -c1-200 $E/bench_c2_shard_one_rank.json
+timeout -k 10 300 python bench.py --full --workload C4 --dp-mode shard --no-cpu-baseline --no-extras --steps 2000 --warmup 200 > $E/bench_c4_shard_one_rank.json 2>/dev/null; cut -c1-200 $E/bench_c4_shard_one_rank.json
+timeout -k 10 300 python bench.py --full --workload C4 --dp-mode shard --tune shard_pipeline=0 --no-cpu-baseline --no-extras --steps 2000 --warmup 200 > $E/bench_c4_shard_one_rank_strict.json 2>/dev/null; cut -c1-200 $E/bench_c4_shard_one_rank_strict.json
 timeout -k 10 300 python tools/bench_samplers.py > $E/samplers.txt 2>&1; tail -6 $E/samplers.txt
 timeout -k 10 300 python tools/bench_big.py 2000 > $E/big_resident.txt 2>&1; tail -4 $E/big_resident.txt
 timeout -k 10 300 python tools/exp_chain_depth.py > $E/chain_depth_experiment.txt 2>&1; tail -3 $E/chain_depth_experiment.txt
@@ -37,19 +37,19 @@ fi
 cd /tmp && export TMPDIR=/tmp
 P="rocprofv3 --kernel-trace --output-format csv"
 if [ "$1" = "prof" ]; then
-$P --stats -d $E/prof_driver -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $E/bench_c2_driver_cmd_under_rocprof.json 2>/dev/null
-$P --stats -d $E/prof_bench -- python3 $R/bench.py --no-cpu-baseline --no-extras > $E/bench_c2_under_rocprof.json 2>/dev/null
-$P --stats -d $E/prof_c3 -- python3 $R/bench.py --workload C3 --steps 3356 --warmup 1678 --no-cpu-baseline --no-extras > /dev/null 2>&1
-$P --stats -d $E/prof_c4 -- python3 $R/bench.py --workload C4 --steps 4000 --warmup 300 --no-cpu-baseline --no-extras > /dev/null 2>&1
+$P --stats -d $E/prof_driver -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $E/bench_c2_driver_cmd_under_rocprof.json 2>/dev/null
+$P --stats -d $E/prof_bench -- python3 $R/bench.py --full --no-cpu-baseline --no-extras > $E/bench_c2_under_rocprof.json 2>/dev/null
+$P --stats -d $E/prof_c3 -- python3 $R/bench.py --full --workload C3 --steps 3356 --warmup 1678 --no-cpu-baseline --no-extras > /dev/null 2>&1
+$P --stats -d $E/prof_c4 -- python3 $R/bench.py --full --workload C4 --steps 4000 --warmup 300 --no-cpu-baseline --no-extras > /dev/null 2>&1
 MFCD_SKIP_TORCH=1 UVT_BENCH_SECONDS=0.01 $P --stats -d $E/prof_uvt -- python3 $R/tools/bench_uvt.py C2 C3 C5 > /dev/null 2>&1
 fi
 if [ "$1" = "pmc" ]; then
-B="python3 $R/bench.py --no-cpu-baseline --no-extras --clock-ramp 0 --steps 2098 --warmup 1049"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-extras --clock-ramp 0 --steps 2098 --warmup 1049"
 $P --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAVES SQ_INSTS_LDS SQ_INSTS_BRANCH -d $E/pmc_c2_a -- $B > /dev/null 2>&1
 $P --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA GRBM_GUI_ACTIVE -d $E/pmc_c2_b -- $B > /dev/null 2>&1
 $P --pmc FETCH_SIZE -d $E/pmc_c2_fetch -- $B > /dev/null 2>&1
 $P --pmc WRITE_SIZE -d $E/pmc_c2_write -- $B > /dev/null 2>&1
-B3="python3 $R/bench.py --workload C3 --no-cpu-baseline --no-extras --clock-ramp 0 --steps 3356 --warmup 1678"
+B3="python3 $R/bench.py --full --workload C3 --no-cpu-baseline --no-extras --clock-ramp 0 --steps 3356 --warmup 1678"
 $P --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAVES SQ_INSTS_LDS SQ_INSTS_BRANCH -d $E/pmc_c3_a -- $B3 > /dev/null 2>&1
 $P --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA GRBM_GUI_ACTIVE -d $E/pmc_c3_b -- $B3 > /dev/null 2>&1
 U="python3 $R/tools/bench_uvt.py C3 C5"
