@@ -85,7 +85,8 @@ int mfcd_eval_batches(const float *U, const float *V, const mfcd_sample *samples
  *        serves one model on one stream and is driven by one host thread at a time; use one per model / stream.
  *   mfcd_train_steps(..., ws, bytes, stream)                    any N <= N_cap with ceil(N/B) <= ceil(N_cap/B_plan),
  *        the same n, m, d; MFCD_ESTATE for an unregistered workspace or other n, m, d, MFCD_EWORKSPACE past the capacity
- *   mfcd_train_workspace_release(ws)                            before freeing it
+ *   mfcd_train_workspace_release(ws)                            before freeing it (also releases a workspace
+ *        registered by mfcd_multi_workspace_init)
  *
  * The first 4 bytes are an int32 status word: 0 = ok, 1 = a bounded in-kernel wait of the resident form expired
  * (U, V, m, v are then undefined).  It is STICKY: no call clears it, so an abort in any earlier call is still
@@ -233,6 +234,76 @@ int mfcd_train_call_run(void *handle, const mfcd_sample *samples, int64_t N, int
 int mfcd_train_call_stage(void *handle, const mfcd_sample *samples, int64_t N, int64_t step0, float *loss_per_step,
                           void *side_stream);
 int mfcd_train_call_release(void *handle);
+
+/*
+ * Batched local form: R independent fp32 models trained in ONE launch, one workgroup (one CU) per model, each
+ * running the local form's per-workgroup code unchanged (mfcd_set_train_path mode 3) on its own tables, records,
+ * batch size, hyper-parameters and Adam step count.  Every model's results (loss_per_step, U, V, the moments) are
+ * bit-identical to what mfcd_train_steps gives for that model on its own.  Workgroups never wait on each other, so R
+ * may exceed the number of CUs (the hardware queues the rest).  Replaces, for a repetition / parameter scan of the
+ * reference (structure.py:352-387, 413-450), R consecutive calls of the per-epoch body of train_model (845-852).
+ *
+ * mfcd_local_model: one model's call, HOST memory; 136 bytes (mfcd_local_model_bytes() reports the size the library
+ * was built with).  The fields mean what the arguments of mfcd_train_steps of the same names mean; loss_per_step
+ * ([ceil(N/B)] fp32, device) is required.  The tables of different models must not overlap.
+ */
+typedef struct mfcd_local_model {
+    float *U, *V, *mU, *vU, *mV, *vV;    /* device; parameters and Adam moments, updated in place              */
+    const mfcd_sample *samples;          /* device; N records consumed in order, batches of B (last one short) */
+    int64_t N;                           /* >= 1                                                               */
+    int64_t step0;                       /* Adam steps already taken                                           */
+    int32_t B, n, m, d;
+    double lr, beta1, beta2, eps, weight_decay;
+    float *loss_per_step;                /* device; [ceil(N/B)] batch-mean BCE per step                       */
+} mfcd_local_model;
+size_t mfcd_local_model_bytes(void);
+
+/*
+ * Workspace of the multi-model entries: caller-owned device memory (256-byte aligned) of
+ *   mfcd_train_local_multi_workspace_bytes(models, R, &stage)   training: descriptors, per-step scalars, loss terms
+ *   mfcd_eval_multi_workspace_bytes(R, &stage)                 validation: descriptors
+ * bytes (0 = bad sizes), registered once with mfcd_multi_workspace_init(ws, bytes, stage), which reserves the pinned
+ * staging ring (four slots of `stage` bytes) the descriptors travel through; release it with
+ * mfcd_train_workspace_release(ws).  A workspace planned for one set of models serves every later call whose own
+ * query is no larger (the epochs of a run: only step0 and the records move).  One workspace per stream, driven by one
+ * host thread at a time; calls on it are stream-ordered, so a training call and a validation call need one each.
+ */
+size_t mfcd_train_local_multi_workspace_bytes(const mfcd_local_model *models, int R, size_t *stage_bytes_out);
+size_t mfcd_eval_multi_workspace_bytes(int R, size_t *stage_bytes_out);
+int mfcd_multi_workspace_init(void *workspace, size_t workspace_bytes, size_t stage_bytes);
+
+/*
+ * Runs ceil(N_r/B_r) optimiser steps for each of the R models of `models` (host array): one prologue kernel copies the
+ * descriptors and the per-step bias-correction scalars (built by the same host code as mfcd_train_steps') from the
+ * pinned ring to the workspace, one launch of R workgroups trains the models, one launch over the flat (model, step)
+ * grid forms every model's batch means.  MFCD_EINVAL, with nothing launched and no table touched, if ANY model is one
+ * mfcd_train_steps would not put on the local form under the current mfcd_set_train_path (auto or local; fp32
+ * tables, (n+m)*d <= 8192, the batch fits the lane groups and the LDS); MFCD_ESTATE for a workspace not registered
+ * by mfcd_multi_workspace_init, MFCD_EWORKSPACE for one smaller than the query says.  The Adam flavour is
+ * mfcd_set_resident_math's.  No host synchronisation and no allocation per call, with the bound of mfcd_train_steps:
+ * a workspace's fifth queued call waits until its first has started.
+ */
+int mfcd_train_steps_local_multi(const mfcd_local_model *models, int R, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+
+/*
+ * mfcd_eval_batches over R models at once (fp32 tables): one launch, one workgroup per (model, batch), the same
+ * per-workgroup code, so loss_per_batch / correct_per_batch equal mfcd_eval_batches' for each model bit for bit.
+ * mfcd_eval_model: one model's pass, HOST memory; 64 bytes (mfcd_eval_model_bytes()); correct_per_batch is
+ * nullable, a model with N = 0 has no batch.  Replaces the validation loop of train_model (structure.py:858-868) of
+ * R experiments.  Same workspace rules and error codes as the training entry above.
+ */
+typedef struct mfcd_eval_model {
+    const float *U, *V;                  /* device; U [n][d], V [m][d]                                          */
+    const mfcd_sample *samples;          /* device; N records in batches of B (last one short)                 */
+    int64_t N;
+    int32_t B, n, m, d;                  /* 1 <= B <= 16384, 1 <= d <= MFCD_MAX_D                               */
+    float *loss_per_batch;               /* device; [ceil(N/B)] mean BCE per batch                             */
+    int32_t *correct_per_batch;          /* device; [ceil(N/B)] matches per batch, nullable                    */
+} mfcd_eval_model;
+size_t mfcd_eval_model_bytes(void);
+int mfcd_eval_batches_multi(const mfcd_eval_model *models, int R, void *workspace, size_t workspace_bytes,
+                            void *stream);
 
 /*
  * Split form for data-parallel training (one exchange step between the two calls):

@@ -4,22 +4,33 @@
 // sample of the batch: the pass is a chain of dependent gathers, so it wants waves, not bytes); the batch
 // mean and the match count are reduced in a fixed order, so results are run-to-run identical.
 #include "common.h"
+#include "train_common.h"
 
 namespace {
 
 constexpr int kEvalWaves = 16;
 
+// segs != nullptr (mfcd_eval_batches_multi): a flat grid over the batches of several models; block b is batch
+// b - blk_begin of the model of the segment it falls in, and the arguments before `segs` are that model's
 template <typename TP>
 __global__ __launch_bounds__(kEvalWaves * 64) void eval_batches_kernel(const TP *__restrict__ U, const TP *__restrict__ V,
                                                            const mfcd_sample *__restrict__ samples, int64_t N, int B,
                                                            int d, float *__restrict__ loss_per_batch,
                                                            int32_t *__restrict__ correct_per_batch,
-                                                           float *__restrict__ p_out)
+                                                           float *__restrict__ p_out,
+                                                           const mfcd_detail::EvalSeg *__restrict__ segs, int nseg)
 {
     extern __shared__ __attribute__((aligned(16))) float terms[];  // [B] BCE terms, then [B] matches
+    int64_t blk = blockIdx.x;
+    if (segs) {
+        const mfcd_detail::EvalSeg &sg = segs[mfcd_detail::find_seg(segs, nseg, blk)];
+        U = (const TP *)sg.U; V = (const TP *)sg.V; samples = sg.samples; N = sg.N; B = sg.B; d = sg.d;
+        loss_per_batch = sg.loss; correct_per_batch = sg.correct;
+        blk -= sg.blk_begin;
+    }
     int *match = reinterpret_cast<int *>(terms + B);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t off = (int64_t)blockIdx.x * B;
+    const int64_t off = blk * B;
     const int b = (int)((N - off) < B ? (N - off) : B);
     for (int t = wave; t < b; t += kEvalWaves) {
         const mfcd_sample s = samples[off + t];
@@ -41,8 +52,8 @@ __global__ __launch_bounds__(kEvalWaves * 64) void eval_batches_kernel(const TP 
         acc = wave_sum64(acc);
         c = wave_sum64_i(c);
         if (lane == 0) {
-            loss_per_batch[blockIdx.x] = acc / (float)b;
-            if (correct_per_batch) correct_per_batch[blockIdx.x] = c;
+            loss_per_batch[blk] = acc / (float)b;
+            if (correct_per_batch) correct_per_batch[blk] = c;
         }
     }
 }
@@ -71,11 +82,24 @@ int eval_batches_impl(const TP *U, const TP *V, const mfcd_sample *samples, int6
     if (!samples || !loss_per_batch) return MFCD_EINVAL;
     const int64_t nb = (N + B - 1) / B;
     hipLaunchKernelGGL((eval_batches_kernel<TP>), dim3((unsigned)nb), dim3(kEvalWaves * 64), sizeof(float) * 2 * (size_t)B,
-                       (hipStream_t)stream, U, V, samples, N, B, d, loss_per_batch, correct_per_batch, p_out);
+                       (hipStream_t)stream, U, V, samples, N, B, d, loss_per_batch, correct_per_batch, p_out,
+                       (const mfcd_detail::EvalSeg *)nullptr, 0);
     MFCD_HIP_TRY(hipGetLastError());
     return 0;
 }
 }  // namespace
+
+namespace mfcd_detail {
+int launch_eval_multi(const EvalSeg *segs_dev, int nseg, int64_t blocks, int max_B, hipStream_t st)
+{
+    hipLaunchKernelGGL((eval_batches_kernel<float>), dim3((unsigned)blocks), dim3(kEvalWaves * 64),
+                       sizeof(float) * 2 * (size_t)max_B, st, (const float *)nullptr, (const float *)nullptr,
+                       (const mfcd_sample *)nullptr, (int64_t)0, 0, 0, (float *)nullptr, (int32_t *)nullptr,
+                       (float *)nullptr, segs_dev, nseg);
+    MFCD_HIP_TRY(hipGetLastError());
+    return 0;
+}
+}  // namespace mfcd_detail
 
 extern "C" int mfcd_eval_batches(const float *U, const float *V, const mfcd_sample *samples, int64_t N, int B, int n,
                                  int m, int d, float *loss_per_batch, int32_t *correct_per_batch, float *p_out,

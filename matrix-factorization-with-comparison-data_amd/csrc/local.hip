@@ -23,6 +23,8 @@
 
 namespace {
 
+using mfcd_detail::LocalArgs;
+
 #ifndef MFCD_LOCAL_PACKED
 #define MFCD_LOCAL_PACKED 1   // Adam on packed fp32 pairs (v_pk_*): bit-identical to the scalar form
 #endif
@@ -31,18 +33,7 @@ constexpr int kSlots = 2;       // hits a lane group owns per step
 constexpr int kMaxLpsShift = 3; // at most 8 lanes per sample / per hit, i.e. at least 128 lane groups
 constexpr int kLocalThreads = 1024;
 constexpr int kRecSlots = 4;   // largest batch = 4 * 1024
-
-struct LocalArgs {
-    float *U, *V, *mU, *vU, *mV, *vV;
-    const mfcd_sample *samples;
-    const StepScalars *sc;   // [K]
-    float *loss_terms;       // [N] sigmoid outputs (the finalize kernel forms the BCE terms)
-    int64_t N;
-    int B, n, m, d, K;
-    int Tpad, Rpad, Bpad;    // LDS carve-up (elements / rows / batch, each padded to a multiple of 4)
-    int lps_shift;           // lanes per sample in phase A = 1 << lps_shift
-    AdamStatic ac;
-};
+static_assert(mfcd_detail::kLocalSmallBatch == kLocalThreads, "RS = 1 stages one record per thread");
 
 // sum over aligned groups of (1 << shift) lanes; every lane of a group gets the group's sum
 __device__ __forceinline__ float group_sum(float x, int shift)
@@ -56,9 +47,12 @@ __device__ __forceinline__ float group_sum(float x, int shift)
     return x;
 }
 
-template <int QL, bool FAST, int RS>   // RS = records a thread stages per step (batch <= RS * 1024)
-__global__ __launch_bounds__(kLocalThreads) void local_train_kernel(LocalArgs a)
+// MULTI: one model per workgroup, workgroup b trains the model of descriptor tab[b] (mfcd_train_steps_local_multi);
+// otherwise the one model of the by-value argument.  The per-workgroup code is the same either way.
+template <int QL, bool FAST, int RS, bool MULTI>   // RS = records a thread stages per step (batch <= RS * 1024)
+__global__ __launch_bounds__(kLocalThreads) void local_train_kernel(LocalArgs a_arg, const LocalArgs *__restrict__ tab)
 {
+    const LocalArgs a = MULTI ? tab[blockIdx.x] : a_arg;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *pL = lds;                                              // [QL*1024] parameters, U rows then V rows, zero pad
     float *gacc = lds + QL * kLocalThreads;                       // [QL*1024] row gradients of the current step
@@ -251,57 +245,72 @@ __global__ __launch_bounds__(kLocalThreads) void local_train_kernel(LocalArgs a)
     }
 }
 
-int local_ql(int n, int m, int d)
-{
-    const int ql = ((n + m) * d + kLocalThreads - 1) / kLocalThreads;
-    return ql <= 1 ? 1 : ql <= 2 ? 2 : ql <= 4 ? 4 : 8;
-}
-
-size_t local_lds_bytes(int B, int n, int m, int d, LocalArgs *a)
+size_t local_lds_bytes(int B, int n, int m, int d, int ql, LocalArgs *a)
 {
     const int R = n + m;
-    const int Tpad = local_ql(n, m, d) * kLocalThreads, Rpad = (R + 3) & ~3, Bpad = (B + 3) & ~3;
+    const int Tpad = ql * kLocalThreads, Rpad = (R + 3) & ~3, Bpad = (B + 3) & ~3;
     if (a) { a->Tpad = Tpad; a->Rpad = Rpad; a->Bpad = Bpad; }
     return sizeof(float) * (2 * (size_t)Tpad + 3 * (size_t)Rpad + (size_t)Bpad) + sizeof(mfcd_sample) * (size_t)B + 16;
 }
 
-template <int QL, bool FAST, int RS>
-int launch_local_inst(const LocalArgs &a, size_t lds_bytes, hipStream_t st)
+int lps_shift_for(int d)
+{
+    int s = 0;
+    while ((1 << s) < d && s < kMaxLpsShift) ++s;
+    return s;
+}
+
+template <int QL, bool FAST, int RS, bool MULTI>
+int launch_local_inst(const LocalArgs &a, const LocalArgs *tab, int grid, size_t lds_bytes, hipStream_t st)
 {
     static size_t allowed = 0;   // per instantiation: raise the dynamic-LDS limit only when a launch needs more
     if (lds_bytes > allowed) {
-        MFCD_HIP_TRY(hipFuncSetAttribute((const void *)local_train_kernel<QL, FAST, RS>,
+        MFCD_HIP_TRY(hipFuncSetAttribute((const void *)local_train_kernel<QL, FAST, RS, MULTI>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
         allowed = lds_bytes;
     }
-    hipLaunchKernelGGL((local_train_kernel<QL, FAST, RS>), dim3(1), dim3(kLocalThreads), lds_bytes, st, a);
+    hipLaunchKernelGGL((local_train_kernel<QL, FAST, RS, MULTI>), dim3(grid), dim3(kLocalThreads), lds_bytes, st, a, tab);
     MFCD_HIP_TRY(hipGetLastError());
     return 0;
 }
 
-template <int QL>
-int launch_local(const LocalArgs &a, size_t lds_bytes, hipStream_t st)
+template <int QL, bool MULTI>
+int launch_local(const LocalArgs &a, const LocalArgs *tab, int grid, bool small_batch, size_t lds_bytes, hipStream_t st)
 {
     // one CU does all the Adam arithmetic here, so the flavour matters even more than in the resident form
-    const bool fast = mfcd_detail::g_resident_math != 0, small_batch = a.B <= kLocalThreads;
-    if (fast) return small_batch ? launch_local_inst<QL, true, 1>(a, lds_bytes, st)
-                                 : launch_local_inst<QL, true, kRecSlots>(a, lds_bytes, st);
-    return small_batch ? launch_local_inst<QL, false, 1>(a, lds_bytes, st)
-                       : launch_local_inst<QL, false, kRecSlots>(a, lds_bytes, st);
+    const bool fast = mfcd_detail::g_resident_math != 0;
+    if (fast) return small_batch ? launch_local_inst<QL, true, 1, MULTI>(a, tab, grid, lds_bytes, st)
+                                 : launch_local_inst<QL, true, kRecSlots, MULTI>(a, tab, grid, lds_bytes, st);
+    return small_batch ? launch_local_inst<QL, false, 1, MULTI>(a, tab, grid, lds_bytes, st)
+                       : launch_local_inst<QL, false, kRecSlots, MULTI>(a, tab, grid, lds_bytes, st);
+}
+
+template <bool MULTI>
+int launch_local_ql(int ql, const LocalArgs &a, const LocalArgs *tab, int grid, bool small_batch, size_t lds, hipStream_t st)
+{
+    if (ql <= 1) return launch_local<1, MULTI>(a, tab, grid, small_batch, lds, st);
+    if (ql <= 2) return launch_local<2, MULTI>(a, tab, grid, small_batch, lds, st);
+    if (ql <= 4) return launch_local<4, MULTI>(a, tab, grid, small_batch, lds, st);
+    return launch_local<8, MULTI>(a, tab, grid, small_batch, lds, st);
 }
 
 }  // namespace
 
 namespace mfcd_detail {
 
+int local_ql(int n, int m, int d)
+{
+    const int ql = ((n + m) * d + kLocalThreads - 1) / kLocalThreads;
+    return ql <= 1 ? 1 : ql <= 2 ? 2 : ql <= 4 ? 4 : 8;
+}
+
 bool local_applies(int64_t N, int B, int n, int m, int d)
 {
     if (!(N > 0 && B >= 1 && B <= kRecSlots * kLocalThreads && d >= 1 && (int64_t)(n + m) * d <= kLocalMaxElems))
         return false;
-    int lps_shift = 0;
-    while ((1 << lps_shift) < d && lps_shift < kMaxLpsShift) ++lps_shift;
+    const int lps_shift = lps_shift_for(d);
     if ((int64_t)3 * B > (int64_t)kSlots * (kLocalThreads >> lps_shift)) return false;   // hits per lane group
-    return local_lds_bytes(B, n, m, d, nullptr) <= (size_t)160 * 1024;
+    return local_lds_bytes(B, n, m, d, local_ql(n, m, d), nullptr) <= kLocalMaxLds;
 }
 
 int launch_local_steps(float *U, float *V, float *mU, float *vU, float *mV, float *vV, const mfcd_sample *samples,
@@ -312,14 +321,22 @@ int launch_local_steps(float *U, float *V, float *mU, float *vU, float *mV, floa
     a.U = U; a.V = V; a.mU = mU; a.vU = vU; a.mV = mV; a.vV = vV;
     a.samples = samples; a.sc = sc_dev; a.loss_terms = loss_terms;
     a.N = N; a.B = B; a.n = n; a.m = m; a.d = d; a.K = K; a.ac = ac;
-    const size_t lds = local_lds_bytes(B, n, m, d, &a);
-    a.lps_shift = 0;
-    while ((1 << a.lps_shift) < d && a.lps_shift < kMaxLpsShift) ++a.lps_shift;
     const int ql = local_ql(n, m, d);
-    if (ql <= 1) return launch_local<1>(a, lds, st);
-    if (ql <= 2) return launch_local<2>(a, lds, st);
-    if (ql <= 4) return launch_local<4>(a, lds, st);
-    return launch_local<8>(a, lds, st);
+    const size_t lds = local_lds_bytes(B, n, m, d, ql, &a);
+    a.lps_shift = lps_shift_for(d);
+    return launch_local_ql<false>(ql, a, nullptr, 1, B <= kLocalSmallBatch, lds, st);
+}
+
+size_t local_multi_fill(LocalArgs &a, int ql)
+{
+    a.lps_shift = lps_shift_for(a.d);
+    return local_lds_bytes(a.B, a.n, a.m, a.d, ql, &a);
+}
+
+int launch_local_multi(const LocalArgs *tab_dev, int R, int ql, bool small_batch, size_t lds_bytes, hipStream_t st)
+{
+    const LocalArgs none{};
+    return launch_local_ql<true>(ql, none, tab_dev, R, small_batch, lds_bytes, st);
 }
 
 }  // namespace mfcd_detail

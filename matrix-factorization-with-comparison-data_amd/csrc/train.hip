@@ -330,19 +330,29 @@ __global__ __launch_bounds__(64) void dp_loss_kernel(const float2 *__restrict__ 
 // out[k] = mean(terms[k*B .. min((k+1)*B,N))) — one wave per batch, fixed summation order.
 // With `samples` set, terms[] holds sigmoid outputs p and the BCE term is formed here from p and the label
 // (the resident kernel keeps the logs off its critical path); otherwise terms[] holds ready BCE terms.
+// segs != nullptr (mfcd_train_steps_local_multi): a flat (model, step) grid; block b is step b - blk_begin of the model
+// of the segment it falls in, and the arguments before `segs` are that model's.
 __global__ __launch_bounds__(64) void batch_mean_kernel(const float *__restrict__ terms,
                                                         const mfcd_sample *__restrict__ samples, int64_t N, int B,
-                                                        float *__restrict__ out)
+                                                        float *__restrict__ out,
+                                                        const mfcd_detail::MeanSeg *__restrict__ segs, int nseg)
 {
+    int64_t blk = blockIdx.x;
+    if (segs) {
+        const mfcd_detail::MeanSeg &sg = segs[mfcd_detail::find_seg(segs, nseg, blk)];
+        terms = sg.terms; samples = sg.samples; N = sg.N; B = sg.B; out = sg.out;
+        blk -= sg.blk_begin;
+    }
     const int lane = threadIdx.x;
-    const int64_t off = (int64_t)blockIdx.x * B;
+    const int64_t off = blk * B;
     const int b = (int)((N - off) < B ? (N - off) : B);
     float acc = 0.0f;
     for (int t = lane; t < b; t += MFCD_WAVE)
         acc += samples ? bce_term_f32(terms[off + t], samples[off + t].z) : terms[off + t];
     acc = wave_sum64(acc);
-    if (lane == 0) out[blockIdx.x] = acc / (float)b;
+    if (lane == 0) out[blk] = acc / (float)b;
 }
+constexpr const mfcd_detail::MeanSeg *kNoSegs = nullptr;
 
 struct Plan {
     int vec, chunks, E, blocksU, blocksV;
@@ -942,7 +952,7 @@ int run_train_steps(TP *U, TP *V, float *mU, float *vU, float *mV, float *vV, co
         if (timing_us) MFCD_HIP_TRY(hipEventRecord(e1, st));
         if (loss_per_step && !means_inside) {
             hipLaunchKernelGGL(batch_mean_kernel, dim3((unsigned)nsteps), dim3(64), 0, st, (const float *)terms, samples, N,
-                               B, loss_per_step);
+                               B, loss_per_step, kNoSegs, 0);
             MFCD_HIP_TRY(hipGetLastError());
         }
         // the slot is free again once the prologue has read it; recorded behind the call's last launch so that the
@@ -992,7 +1002,7 @@ int run_train_steps(TP *U, TP *V, float *mU, float *vU, float *mV, float *vV, co
     }
     if (loss_per_step) {
         hipLaunchKernelGGL(batch_mean_kernel, dim3((unsigned)nsteps), dim3(64), 0, st, terms,
-                           (const mfcd_sample *)nullptr, N, B, loss_per_step);
+                           (const mfcd_sample *)nullptr, N, B, loss_per_step, kNoSegs, 0);
         MFCD_HIP_TRY(hipGetLastError());
     }
     if (timing_us) {
@@ -1132,6 +1142,203 @@ extern "C" int mfcd_train_call_stage(void *handle, const mfcd_sample *samples, i
 extern "C" int mfcd_train_call_release(void *handle)
 {
     delete (TrainCall *)handle;
+    return 0;
+}
+
+// ---- batched local form and multi-model validation pass (include/mfcd.h: mfcd_train_steps_local_multi,
+// mfcd_eval_batches_multi).  A multi-model workspace is registered like a training workspace (same registry, same pinned
+// staging ring) but with n = m = d = 0, so that neither kind of call accepts the other kind's workspace. ----
+namespace {
+
+size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// per-model validation of the batched local form: what mfcd_train_steps would put on the local form (choose_form)
+bool local_model_ok(const mfcd_local_model &md)
+{
+    if (check_common(md.U, md.V, md.n, md.m, md.d)) return false;
+    if (!md.mU || !md.vU || !md.mV || !md.vV || !md.samples || !md.loss_per_step || md.N <= 0 || md.B <= 0 ||
+        md.step0 < 0)
+        return false;
+    const FormChoice fc = choose_form(true, false, 0, md.N, md.B, md.n, md.m, md.d);
+    return fc.form == 3;
+}
+
+struct MultiLayout {   // stage region: LocalArgs[R] | MeanSeg[R] | StepScalars[sum(K_r + 1)] ; then the loss terms
+    size_t seg_off, sc_off, stage_bytes, terms_off, total;
+    int64_t steps, samples;
+};
+
+MultiLayout local_multi_layout(const mfcd_local_model *models, int R)
+{
+    MultiLayout L{};
+    for (int r = 0; r < R; ++r) {
+        L.steps += (models[r].N + models[r].B - 1) / models[r].B;
+        L.samples += models[r].N;
+    }
+    L.seg_off = align16(sizeof(mfcd_detail::LocalArgs) * (size_t)R);
+    L.sc_off = L.seg_off + align16(sizeof(mfcd_detail::MeanSeg) * (size_t)R);
+    L.stage_bytes = L.sc_off + sizeof(StepScalars) * (size_t)(L.steps + R);
+    L.terms_off = align256(L.stage_bytes);
+    L.total = L.terms_off + align256(sizeof(float) * (size_t)L.samples);
+    return L;
+}
+
+size_t eval_multi_stage_bytes(int R) { return align16(sizeof(mfcd_detail::EvalSeg) * (size_t)R); }
+
+bool eval_model_ok(const mfcd_eval_model &md)
+{
+    if (!md.U || !md.V || md.n <= 0 || md.m <= 0 || md.d <= 0 || md.d > MFCD_MAX_D || md.N < 0 || md.B <= 0 ||
+        md.B > 16384)
+        return false;
+    return md.N == 0 || (md.samples && md.loss_per_batch);
+}
+
+WsState *find_multi_ws(void *workspace)
+{
+    WsState *S = workspace ? find_ws(workspace) : nullptr;
+    return S && S->n == 0 ? S : nullptr;
+}
+
+}  // namespace
+
+extern "C" size_t mfcd_local_model_bytes(void) { return sizeof(mfcd_local_model); }
+extern "C" size_t mfcd_eval_model_bytes(void) { return sizeof(mfcd_eval_model); }
+
+extern "C" size_t mfcd_train_local_multi_workspace_bytes(const mfcd_local_model *models, int R, size_t *stage_bytes_out)
+{
+    if (!models || R <= 0) return 0;
+    for (int r = 0; r < R; ++r)
+        if (models[r].N <= 0 || models[r].B <= 0) return 0;
+    const MultiLayout L = local_multi_layout(models, R);
+    if (stage_bytes_out) *stage_bytes_out = L.stage_bytes;
+    return L.total;
+}
+
+extern "C" size_t mfcd_eval_multi_workspace_bytes(int R, size_t *stage_bytes_out)
+{
+    if (R <= 0) return 0;
+    if (stage_bytes_out) *stage_bytes_out = eval_multi_stage_bytes(R);
+    return align256(eval_multi_stage_bytes(R));
+}
+
+extern "C" int mfcd_multi_workspace_init(void *workspace, size_t workspace_bytes, size_t stage_bytes)
+{
+    if (!workspace || workspace_bytes == 0 || stage_bytes == 0 || stage_bytes > workspace_bytes) return MFCD_EINVAL;
+    if (reinterpret_cast<uintptr_t>(workspace) & 255u) return MFCD_EALIGN;
+    auto S = std::make_unique<WsState>();
+    S->bytes = workspace_bytes;
+    (void)hipGetDevice(&S->device);
+    for (auto &sl : S->slot)
+        if (int rc = stage_reserve(sl, stage_bytes)) return rc;
+    std::lock_guard<std::mutex> lock(g_ws_mu);
+    g_ws[workspace] = std::move(S);
+    return 0;
+}
+
+extern "C" int mfcd_train_steps_local_multi(const mfcd_local_model *models, int R, void *workspace,
+                                            size_t workspace_bytes, void *stream)
+{
+    using mfcd_detail::LocalArgs;
+    using mfcd_detail::MeanSeg;
+    if (!models || R <= 0 || !workspace) return MFCD_EINVAL;
+    // every check comes before the first launch: a rejected call touches no table
+    int ql = 1, max_B = 0;
+    for (int r = 0; r < R; ++r) {
+        if (!local_model_ok(models[r])) return MFCD_EINVAL;
+        const int q = mfcd_detail::local_ql(models[r].n, models[r].m, models[r].d);
+        ql = q > ql ? q : ql;
+        max_B = models[r].B > max_B ? models[r].B : max_B;
+    }
+    const MultiLayout L = local_multi_layout(models, R);
+    if (L.steps > 0x7fffffff) return MFCD_EINVAL;
+    WsState *S = find_multi_ws(workspace);
+    if (!S) return MFCD_ESTATE;   // mfcd_multi_workspace_init has not been called on this workspace
+    if (workspace_bytes < L.total || S->bytes < L.total) return MFCD_EWORKSPACE;
+    StageSlot *slot = nullptr;
+    if (int rc = stage_acquire(*S, L.stage_bytes, &slot)) return rc;
+
+    char *base = (char *)workspace, *host = (char *)slot->host;
+    LocalArgs *tab = (LocalArgs *)host;
+    MeanSeg *segs = (MeanSeg *)(host + L.seg_off);
+    StepScalars *sc = (StepScalars *)(host + L.sc_off);
+    int64_t k0 = 0, t0 = 0, blk0 = 0;
+    size_t lds = 0;
+    for (int r = 0; r < R; ++r) {
+        const mfcd_local_model &md = models[r];
+        const int64_t K = (md.N + md.B - 1) / md.B;
+        for (int64_t k = 0; k <= K; ++k) sc[k0 + k] = step_scalars(md.lr, md.beta1, md.beta2, md.step0 + k + 1);
+        LocalArgs a{};
+        a.U = md.U; a.V = md.V; a.mU = md.mU; a.vU = md.vU; a.mV = md.mV; a.vV = md.vV;
+        a.samples = md.samples;
+        a.sc = (const StepScalars *)(base + L.sc_off) + k0;
+        a.loss_terms = (float *)(base + L.terms_off) + t0;
+        a.N = md.N; a.B = md.B; a.n = md.n; a.m = md.m; a.d = md.d; a.K = (int)K;
+        a.ac = adam_static(md.beta1, md.beta2, md.eps, md.weight_decay);
+        const size_t need = mfcd_detail::local_multi_fill(a, ql);
+        lds = need > lds ? need : lds;
+        tab[r] = a;
+        MeanSeg sg{};
+        sg.terms = a.loss_terms; sg.samples = md.samples; sg.out = md.loss_per_step;
+        sg.N = md.N; sg.B = md.B; sg.blk_begin = blk0;
+        segs[r] = sg;
+        k0 += K + 1;
+        t0 += md.N;
+        blk0 += K;
+    }
+    if (lds > mfcd_detail::kLocalMaxLds) return MFCD_EINVAL;   // (not reached: every model fits at QL = 8)
+
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = mfcd_detail::launch_train_prologue(host, slot->devview, base, L.stage_bytes, nullptr, 0, 1, 0, 0, 0, 0,
+                                                    0, 0, nullptr, nullptr, nullptr, st))
+        return rc;
+    if (int rc = mfcd_detail::launch_local_multi((const LocalArgs *)base, R, ql, max_B <= mfcd_detail::kLocalSmallBatch,
+                                                 lds, st))
+        return rc;
+    hipLaunchKernelGGL(batch_mean_kernel, dim3((unsigned)L.steps), dim3(64), 0, st, (const float *)nullptr,
+                       (const mfcd_sample *)nullptr, (int64_t)0, 1, (float *)nullptr,
+                       (const MeanSeg *)(base + L.seg_off), R);
+    MFCD_HIP_TRY(hipGetLastError());
+    MFCD_HIP_TRY(hipEventRecord(slot->ev, st));   // the slot is free again once the prologue has read it
+    slot->pending = true;
+    return 0;
+}
+
+extern "C" int mfcd_eval_batches_multi(const mfcd_eval_model *models, int R, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    using mfcd_detail::EvalSeg;
+    if (!models || R <= 0 || !workspace) return MFCD_EINVAL;
+    for (int r = 0; r < R; ++r)
+        if (!eval_model_ok(models[r])) return MFCD_EINVAL;
+    WsState *S = find_multi_ws(workspace);
+    if (!S) return MFCD_ESTATE;
+    const size_t stage_bytes = eval_multi_stage_bytes(R);
+    if (workspace_bytes < stage_bytes || S->bytes < stage_bytes) return MFCD_EWORKSPACE;
+    StageSlot *slot = nullptr;
+    if (int rc = stage_acquire(*S, stage_bytes, &slot)) return rc;
+    EvalSeg *segs = (EvalSeg *)slot->host;
+    int nseg = 0, max_B = 1;
+    int64_t blocks = 0;
+    for (int r = 0; r < R; ++r) {
+        const mfcd_eval_model &md = models[r];
+        if (md.N == 0) continue;   // no batch: no segment
+        EvalSeg sg{};
+        sg.U = md.U; sg.V = md.V; sg.samples = md.samples; sg.loss = md.loss_per_batch;
+        sg.correct = md.correct_per_batch;
+        sg.N = md.N; sg.B = md.B; sg.d = md.d; sg.blk_begin = blocks;
+        segs[nseg++] = sg;
+        blocks += (md.N + md.B - 1) / md.B;
+        max_B = md.B > max_B ? md.B : max_B;
+    }
+    if (blocks == 0) return 0;
+    if (blocks > 0x7fffffff) return MFCD_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = mfcd_detail::launch_train_prologue(segs, slot->devview, workspace, stage_bytes, nullptr, 0, 1, 0, 0, 0, 0,
+                                                    0, 0, nullptr, nullptr, nullptr, st))
+        return rc;
+    if (int rc = mfcd_detail::launch_eval_multi((const EvalSeg *)workspace, nseg, blocks, max_B, st)) return rc;
+    MFCD_HIP_TRY(hipEventRecord(slot->ev, st));
+    slot->pending = true;
     return 0;
 }
 
@@ -1728,7 +1935,7 @@ int run_shard_train_steps(TP *U, TP *V, float *mU, float *vU, float *mV, float *
     }
     if (loss_per_step) {
         hipLaunchKernelGGL(batch_mean_kernel, dim3((unsigned)nsteps), dim3(64), 0, st, terms,
-                           (const mfcd_sample *)nullptr, N, B, loss_per_step);
+                           (const mfcd_sample *)nullptr, N, B, loss_per_step, kNoSegs, 0);
         MFCD_HIP_TRY(hipGetLastError());
     }
     return 0;

@@ -133,10 +133,64 @@ namespace mfcd_detail {
 
 // ---- local form (local.hip): one workgroup, parameters in LDS ----
 constexpr int64_t kLocalMaxElems = 8192;   // (n+m)*d: above this one CU's vector ALU is slower than the multi-CU resident form
+constexpr size_t kLocalMaxLds = (size_t)160 * 1024;   // one CU's LDS
 bool local_applies(int64_t N, int B, int n, int m, int d);
 int launch_local_steps(float *U, float *V, float *mU, float *vU, float *mV, float *vV, const mfcd_sample *samples,
                        int64_t N, int B, int n, int m, int d, const StepScalars *sc_dev, const AdamStatic &ac,
                        float *loss_terms, int K, hipStream_t st);
+
+// Arguments of one model's local-form launch: the kernel's by-value argument, and one entry of the device-side
+// descriptor table of the batched form (one model per workgroup).
+struct LocalArgs {
+    float *U, *V, *mU, *vU, *mV, *vV;
+    const mfcd_sample *samples;
+    const StepScalars *sc;   // [K+1] (the last entry is a pad: the kernel reads step k+1's scalars during step k)
+    float *loss_terms;       // [N] sigmoid outputs (the batch-mean kernel forms the BCE terms)
+    int64_t N;
+    int B, n, m, d, K;
+    int Tpad, Rpad, Bpad;    // LDS carve-up (elements / rows / batch, each padded to a multiple of 4)
+    int lps_shift;           // lanes per sample in phase A = 1 << lps_shift
+    AdamStatic ac;
+};
+
+// batched local form (mfcd_train_steps_local_multi): QL = local_ql of the largest model; local_multi_fill sets a
+// model's LDS carve-up and lane-group width at that QL and returns the dynamic LDS it needs there
+int local_ql(int n, int m, int d);
+size_t local_multi_fill(LocalArgs &a, int ql);
+int launch_local_multi(const LocalArgs *tab_dev, int R, int ql, bool small_batch, size_t lds_bytes, hipStream_t st);
+constexpr int kLocalSmallBatch = 1024;   // batches of at most this many records: one staging slot per thread
+
+// one segment of a flat multi-model grid: blocks [blk_begin, next segment's blk_begin) belong to one model
+struct MeanSeg {       // batch_mean_kernel (train.hip): the per-step batch means of one model
+    const float *terms;
+    const mfcd_sample *samples;
+    float *out;
+    int64_t N, blk_begin;
+    int B, pad;
+};
+struct EvalSeg {       // eval_batches_kernel (eval.hip): the validation batches of one model
+    const float *U, *V;
+    const mfcd_sample *samples;
+    float *loss;
+    int32_t *correct;
+    int64_t N, blk_begin;
+    int B, d;
+};
+
+// index of the segment block `blk` belongs to (segments sorted by blk_begin, the first one starting at 0)
+template <typename Seg>
+__device__ __forceinline__ int find_seg(const Seg *segs, int nseg, int64_t blk)
+{
+    int lo = 0, hi = nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (segs[mid].blk_begin <= blk) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+int launch_eval_multi(const EvalSeg *segs_dev, int nseg, int64_t blocks, int max_B, hipStream_t st);
 
 struct ResidentPlan {
     bool ok;

@@ -35,6 +35,13 @@ SIGNATURES = {
     "mfcd_train_call_run": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "mfcd_train_call_stage": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "mfcd_train_call_release": (_i32, [_vp]),
+    "mfcd_local_model_bytes": (_sz, []),
+    "mfcd_eval_model_bytes": (_sz, []),
+    "mfcd_train_local_multi_workspace_bytes": (_sz, [_vp, _i32, ctypes.POINTER(_sz)]),
+    "mfcd_eval_multi_workspace_bytes": (_sz, [_i32, ctypes.POINTER(_sz)]),
+    "mfcd_multi_workspace_init": (_i32, [_vp, _sz, _sz]),
+    "mfcd_train_steps_local_multi": (_i32, [_vp, _i32, _vp, _sz, _vp]),
+    "mfcd_eval_batches_multi": (_i32, [_vp, _i32, _vp, _sz, _vp]),
     "mfcd_batch_coefficients": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mfcd_apply_step": (_i32, [_vp] * 8 + [_i32, _i64, _i32, _i32, _i32] + [_dbl] * 5 + [_vp, _sz, _vp]),
     "mfcd_dense_grad": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -90,6 +97,19 @@ class TrainPlan(ctypes.Structure):
                                                "resident_lookahead", "fast_math", "streaming_vec",
                                                "streaming_chunks", "streaming_blocks", "device_cus")] + \
                [("reserved", ctypes.c_int32 * 6)]
+
+
+class LocalModel(ctypes.Structure):
+    """mfcd_local_model of include/mfcd.h (one model of mfcd_train_steps_local_multi)."""
+    _fields_ = [(k, _vp) for k in ("U", "V", "mU", "vU", "mV", "vV", "samples")] + \
+               [("N", ctypes.c_int64), ("step0", ctypes.c_int64)] + [(k, ctypes.c_int32) for k in ("B", "n", "m", "d")] + \
+               [(k, _dbl) for k in ("lr", "beta1", "beta2", "eps", "weight_decay")] + [("loss_per_step", _vp)]
+
+
+class EvalModel(ctypes.Structure):
+    """mfcd_eval_model of include/mfcd.h (one model of mfcd_eval_batches_multi)."""
+    _fields_ = [(k, _vp) for k in ("U", "V", "samples")] + [("N", ctypes.c_int64)] + \
+               [(k, ctypes.c_int32) for k in ("B", "n", "m", "d")] + [("loss_per_batch", _vp), ("correct_per_batch", _vp)]
 
 
 class Sampler(ctypes.Structure):

@@ -87,5 +87,16 @@ def epoch_order(loader):
     return order, bs
 
 
+def draw_orders(train_loader, val_loader, num_epochs):
+    """Every epoch order train_model's loop (structure.py:845, 861) would draw, drawn now, in its sequence:
+    [train_0, val_0, train_1, val_1, ...] as (order, batch_size) pairs.  Leaves torch's generators where that loop would
+    (mfcd.engine.fit(..., orders=...) replays the list without drawing)."""
+    out = []
+    for _ in range(num_epochs):
+        out.append(epoch_order(train_loader))
+        out.append(epoch_order(val_loader))
+    return out
+
+
 def n_batches(n_items, bs):
     return (n_items + bs - 1) // bs

@@ -9,7 +9,7 @@ import torch
 
 from . import _lib
 from ._lib import _raw_stream
-from .batching import dataset_records, epoch_order, n_batches, pack_records
+from .batching import dataset_records, draw_orders, epoch_order, n_batches, pack_records
 
 
 def _require_cuda_param(t, name, dtypes=(torch.float32,)):
@@ -669,11 +669,21 @@ def records_from_indices(u, i, j, n, m, device, z=None):
     return torch.stack(cols + [zf.view(torch.int32)], dim=1).contiguous()
 
 
-def fit_generic(model, train_loader, val_loader, optimizer, num_epochs, progress=None):
+def _order_source(orders):
+    """epoch_order, or a replay of pre-drawn orders (batching.draw_orders) in the sequence the loop asks for them."""
+    if orders is None:
+        return epoch_order
+    it = iter(orders)
+    return lambda loader: next(it)
+
+
+def fit_generic(model, train_loader, val_loader, optimizer, num_epochs, progress=None, orders=None):
     """The reference's own loop (structure.py:840-868) for optimisers the fused step does not implement (anything but
     plain torch.optim.Adam): per batch zero_grad, forward kernel, F.binary_cross_entropy, backward (scatter kernel),
-    optimizer.step(), loss.item() — every step a host round trip, as there; batch order and RNG use identical."""
+    optimizer.step(), loss.item() — every step a host round trip, as there; batch order and RNG use identical.
+    `orders`: pre-drawn epoch orders (batching.draw_orders) replayed instead of drawing."""
     import torch.nn.functional as F
+    next_order = _order_source(orders)
     U, V = model.U, model.V
     _require_cuda_param(U.data, "model.U")
     _require_cuda_param(V.data, "model.V")
@@ -683,7 +693,7 @@ def fit_generic(model, train_loader, val_loader, optimizer, num_epochs, progress
     train_losses, val_losses = [], []
     it = range(num_epochs) if progress is None else progress(range(num_epochs))
     for _ in it:
-        order, bs = epoch_order(train_loader)
+        order, bs = next_order(train_loader)
         rec = train.ordered(order)
         total, nb = 0.0, 0
         for off in range(0, rec.shape[0], bs):
@@ -696,7 +706,7 @@ def fit_generic(model, train_loader, val_loader, optimizer, num_epochs, progress
             total += loss.item()
             nb += 1
         train_losses.append(total / max(nb, 1))
-        vorder, vbs = epoch_order(val_loader)
+        vorder, vbs = next_order(val_loader)
         vl, _, _ = eval_batches(U.data, V.data, val.ordered(vorder), vbs)
         val_losses.append(python_float_sum(vl.cpu().numpy()) / max(len(vl), 1))
     return train_losses, val_losses
@@ -717,9 +727,11 @@ def python_float_sum(x):
     return float(np.cumsum(a)[-1]) if a.size else 0.0
 
 
-def fit(model, train_loader, val_loader, optimizer, num_epochs, progress=None):
+def fit(model, train_loader, val_loader, optimizer, num_epochs, progress=None, orders=None):
     """The epoch loop of train_model (structure.py:840-868) on the device path.
-    Returns (train_losses, val_losses): per-epoch mean of batch means, Python floats."""
+    Returns (train_losses, val_losses): per-epoch mean of batch means, Python floats.
+    `orders`: pre-drawn epoch orders (batching.draw_orders) replayed instead of drawing."""
+    next_order = _order_source(orders)
     binding = AdamBinding(model, optimizer)
     U, V = model.U.data, model.V.data
     dev = U.device
@@ -738,7 +750,7 @@ def fit(model, train_loader, val_loader, optimizer, num_epochs, progress=None):
     launched = []            # one event per enqueued train call: a staged prologue reuses the regions of the call two back
     try:
         if num_epochs > 0:
-            order, bs = epoch_order(train_loader)           # structure.py:845 iter(train_loader)
+            order, bs = next_order(train_loader)            # structure.py:845 iter(train_loader)
             pre.start(train, order)
         nsteps = n_batches(train.N, bs) if bs else 0
         loss_bufs = torch.empty((max(num_epochs, 1), max(nsteps, 1)), dtype=torch.float32, device=dev)
@@ -748,9 +760,9 @@ def fit(model, train_loader, val_loader, optimizer, num_epochs, progress=None):
             ev = torch.cuda.Event()
             ev.record()
             launched.append(ev)
-            vorder, vbs = epoch_order(val_loader)           # structure.py:861 iter(val_loader)
+            vorder, vbs = next_order(val_loader)            # structure.py:861 iter(val_loader)
             if e + 1 < num_epochs:
-                order, bs = epoch_order(train_loader)       # next epoch's structure.py:845
+                order, bs = next_order(train_loader)        # next epoch's structure.py:845
                 nxt = loss_bufs[e + 1]
                 pre.start(train, order, after=launched[e - 1] if e >= 1 else None,
                           stage=lambda rec, side, nxt=nxt: stage_next_call(binding, rec, bs, nxt, side))
@@ -766,11 +778,187 @@ def fit(model, train_loader, val_loader, optimizer, num_epochs, progress=None):
     return tl, vl
 
 
-def evaluate(model, test_loader):
-    """evaluate_model (structure.py:881-921) on the device path → (mean batch BCE, accuracy)."""
+def _numpy_mirror(struct):
+    """numpy structured dtype with the layout of a ctypes Structure (pointers as uint64): lets the host update one
+    field of every descriptor of a table with one vectorised assignment."""
+    import ctypes
+    names, formats, offsets = [], [], []
+    for name, ct in struct._fields_:
+        names.append(name)
+        formats.append(np.uint64 if ct is ctypes.c_void_p else np.dtype(ct))
+        offsets.append(getattr(struct, name).offset)
+    return np.dtype({"names": names, "formats": formats, "offsets": offsets, "itemsize": ctypes.sizeof(struct)})
+
+
+def _multi_workspace(L, nbytes, stage, dev):
+    buf = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    if buf.data_ptr() % 256:
+        raise _lib.MfcdError("multi-model workspace is not 256-byte aligned")
+    _lib.check(L.mfcd_multi_workspace_init(buf.data_ptr(), buf.numel(), int(stage)))
+    return buf
+
+
+def batched_applies(model, optimizer, n_samples, batch_size):
+    """True when fit_many trains this model in the batched local launch: the fused step applies, the factors are fp32
+    and the library would put a call of these sizes on the local form under the current settings."""
+    if n_samples <= 0 or not batch_size or not fused_step_applies(model, optimizer) or model.U.dtype != torch.float32:
+        return False
+    return train_plan(n_samples, batch_size, model.U.shape[0], model.V.shape[0], model.U.shape[1])["form_name"] == "local"
+
+
+def fit_many(models, train_loaders, val_loaders, optimizers, num_epochs, orders=None):
+    """`fit` for R independent models at once → [(train_losses, val_losses), ...], each bit-identical to what `fit` (or,
+    for optimisers the fused step does not implement, `fit_generic`) gives for that model on its own.
+
+    Models that `batched_applies` to train together (include/mfcd.h: mfcd_train_steps_local_multi): per epoch one
+    gather of all their train records, one training launch of one workgroup per model, one batch-mean launch, one
+    gather of their validation records and one validation launch (mfcd_eval_batches_multi), whatever R is; one
+    device-to-host transfer at the end.  Every other model goes through fit / fit_generic alone, in its place.
+    `num_epochs`: one count for all, or one per model.  `orders`: per model, pre-drawn epoch orders
+    (batching.draw_orders); None draws them here, model after model, exactly as consecutive train_model calls would
+    (training draws nothing else from the global generators)."""
+    R = len(models)
+    epochs = [int(num_epochs)] * R if np.ndim(num_epochs) == 0 else [int(e) for e in num_epochs]
+    if not (len(train_loaders) == len(val_loaders) == len(optimizers) == len(epochs) == R):
+        raise ValueError("fit_many needs one train loader, val loader, optimizer and epoch count per model")
+    if orders is None:
+        orders = [draw_orders(train_loaders[r], val_loaders[r], epochs[r]) for r in range(R)]
+    elif len(orders) != R or any(len(orders[r]) != 2 * epochs[r] for r in range(R)):
+        raise ValueError("fit_many needs one list of 2 * num_epochs orders per model")
+    results = [None] * R
+    groups = {}                                # device -> indices of the models trained together there
+    for r in range(R):
+        tr = orders[r][0::2]
+        same = len({(int(o.numel()), bs) for o, bs in tr}) == 1
+        if epochs[r] > 0 and same and batched_applies(models[r], optimizers[r], int(tr[0][0].numel()), tr[0][1]):
+            groups.setdefault(models[r].U.device, []).append(r)
+        elif fused_step_applies(models[r], optimizers[r]):
+            results[r] = fit(models[r], train_loaders[r], val_loaders[r], optimizers[r], epochs[r], orders=orders[r])
+        else:
+            results[r] = fit_generic(models[r], train_loaders[r], val_loaders[r], optimizers[r], epochs[r],
+                                     orders=orders[r])
+    for dev, idx in groups.items():
+        out = _fit_local_multi([models[r] for r in idx], [train_loaders[r] for r in idx], [val_loaders[r] for r in idx],
+                               [optimizers[r] for r in idx], [epochs[r] for r in idx], [orders[r] for r in idx], dev)
+        for r, res in zip(idx, out):
+            results[r] = res
+    return results
+
+
+def _packed(tab, rec, counts):
+    """Descriptors of a subset of the models, whose records were gathered side by side into `rec`."""
+    tab["samples"] = rec.data_ptr() + 16 * np.concatenate(([0], np.cumsum(counts)[:-1])).astype(np.uint64)
+    return tab
+
+
+def _fit_local_multi(models, train_loaders, val_loaders, optimizers, epochs, orders, dev):
+    L = _lib.load()
+    R, E = len(models), max(epochs)
+    ep = np.array(epochs, dtype=np.int64)
+    bindings = [AdamBinding(mo, op) for mo, op in zip(models, optimizers)]
+    shapes = [(mo.U.shape[0], mo.V.shape[0], mo.U.shape[1]) for mo in models]
+    trains = [SampleStore.from_loader(ld, n, m, dev) for ld, (n, m, _) in zip(train_loaders, shapes)]
+    vals = [SampleStore.from_loader(ld, n, m, dev) for ld, (n, m, _) in zip(val_loaders, shapes)]
+    B = np.array([o[0][1] for o in orders], dtype=np.int64)
+    Nt = np.array([o[0][0].numel() for o in orders], dtype=np.int64)
+    K = (Nt + B - 1) // B
+    vB = np.array([o[1][1] for o in orders], dtype=np.int64)
+    Nv = np.array([o[1][0].numel() for o in orders], dtype=np.int64)
+    Kv = (Nv + vB - 1) // vB
+    excl = lambda a: np.concatenate(([0], np.cumsum(a)[:-1])).astype(np.int64)   # noqa: E731
+    t_off, v_off, k_off, kv_off = excl(Nt), excl(Nv), excl(K), excl(Kv)
+    t_base = excl(np.array([st.N for st in trains]))
+    v_base = excl(np.array([st.N for st in vals]))
+    # every model's records side by side: one gather per epoch serves them all (fixed buffers: fixed descriptors)
+    t_all = torch.cat([st.dev for st in trains]) if R > 1 else trains[0].dev
+    v_all = torch.cat([st.dev for st in vals]) if R > 1 else vals[0].dev
+    t_rec = torch.empty((max(int(Nt.sum()), 1), 4), dtype=torch.int32, device=dev)
+    v_rec = torch.empty((max(int(Nv.sum()), 1), 4), dtype=torch.int32, device=dev)
+    W = int(K.sum() + Kv.sum())
+    losses = torch.empty((E, max(W, 1)), dtype=torch.float32, device=dev)   # [epoch][train steps | val batches]
+    row_bytes = losses.stride(0) * 4
+
+    tv = np.zeros(R, dtype=_numpy_mirror(_lib.LocalModel))     # the descriptor tables (host), one entry per model
+    ev = np.zeros(R, dtype=_numpy_mirror(_lib.EvalModel))
+    for r, b in enumerate(bindings):
+        ptrs, n, m, d, _, _ = b.call_context()
+        for name, p in zip(("U", "V", "mU", "vU", "mV", "vV"), ptrs):
+            tv[name][r] = p
+        lr, b1, b2, eps, wd = b.hyper()
+        tv["lr"][r], tv["beta1"][r], tv["beta2"][r], tv["eps"][r], tv["weight_decay"][r] = lr, b1, b2, eps, wd
+        tv["n"][r] = ev["n"][r] = n
+        tv["m"][r] = ev["m"][r] = m
+        tv["d"][r] = ev["d"][r] = d
+        ev["U"][r], ev["V"][r] = ptrs[0], ptrs[1]
+    tv["samples"] = t_rec.data_ptr() + 16 * t_off.astype(np.uint64)
+    tv["N"], tv["B"] = Nt, B
+    ev["samples"] = v_rec.data_ptr() + 16 * v_off.astype(np.uint64)
+    ev["N"], ev["B"] = Nv, vB
+    ev["correct_per_batch"] = 0
+    step0 = np.array([b.step for b in bindings], dtype=np.int64)
+    loss_t = losses.data_ptr() + 4 * k_off.astype(np.uint64)
+    loss_v = losses.data_ptr() + 4 * (int(K.sum()) + kv_off).astype(np.uint64)
+    tv["step0"], tv["loss_per_step"], ev["loss_per_batch"] = step0, loss_t, loss_v
+
+    import ctypes
+    stage = ctypes.c_size_t(0)
+    tws = _multi_workspace(L, L.mfcd_train_local_multi_workspace_bytes(tv.ctypes.data, R, ctypes.byref(stage)),
+                           stage.value, dev)
+    vws = None
+    try:
+        vws = _multi_workspace(L, L.mfcd_eval_multi_workspace_bytes(R, ctypes.byref(stage)), stage.value, dev)
+        stream = _lib.stream_ptr(dev)
+        # offset of each record's model in t_all / v_all, per position of the concatenated orders
+        t_shift = torch.from_numpy(np.repeat(t_base, Nt))
+        v_shift = torch.from_numpy(np.repeat(v_base, Nv))
+        for e in range(E):
+            live = np.flatnonzero(ep > e)          # models still training in epoch e (all of them unless counts differ)
+            if live.size < R:
+                t_shift = torch.from_numpy(np.repeat(t_base[live], Nt[live]))
+                v_shift = torch.from_numpy(np.repeat(v_base[live], Nv[live]))
+            idx = torch.cat([orders[r][2 * e][0] for r in live]) + t_shift
+            torch.index_select(t_all, 0, idx.pin_memory().to(dev, non_blocking=True), out=t_rec[:idx.numel()])
+            tv["step0"] = step0
+            tv["loss_per_step"] = loss_t + np.uint64(e * row_bytes)
+            t_tab = tv if live.size == R else _packed(tv[live], t_rec, Nt[live])
+            _lib.check(L.mfcd_train_steps_local_multi(t_tab.ctypes.data, int(live.size), tws.data_ptr(), tws.numel(), stream))
+            for r in live:
+                step0[r] += K[r]
+                bindings[r].advance(int(K[r]), defer=True)
+            vidx = torch.cat([orders[r][2 * e + 1][0] for r in live]) + v_shift
+            if vidx.numel():
+                torch.index_select(v_all, 0, vidx.pin_memory().to(dev, non_blocking=True), out=v_rec[:vidx.numel()])
+            ev["loss_per_batch"] = loss_v + np.uint64(e * row_bytes)
+            v_tab = ev if live.size == R else _packed(ev[live], v_rec, Nv[live])
+            _lib.check(L.mfcd_eval_batches_multi(v_tab.ctypes.data, int(live.size), vws.data_ptr(), vws.numel(), stream))
+    finally:
+        for b in bindings:
+            b.flush()       # an interrupt must not leave the moments ahead of the optimizer's `step` tensors
+        for ws in (tws, vws):
+            if ws is not None:
+                L.mfcd_train_workspace_release(ws.data_ptr())
+    host = losses.cpu().numpy().astype(np.float64)          # the one device->host transfer of the run
+    out = []
+    for r in range(R):
+        # python_float_sum per epoch: sequential f64 accumulation along each row
+        k, kv, er = int(K[r]), int(Kv[r]), int(ep[r])
+        t = host[:er, k_off[r]:k_off[r] + k]
+        tl = (np.cumsum(t, axis=1)[:, -1] / max(k, 1)).tolist()
+        if kv:
+            v = host[:er, int(K.sum()) + kv_off[r]:int(K.sum()) + kv_off[r] + kv]
+            vl = (np.cumsum(v, axis=1)[:, -1] / kv).tolist()
+        else:
+            vl = [0.0] * er
+        out.append((tl, vl))
+    return out
+
+
+def evaluate(model, test_loader, order=None):
+    """evaluate_model (structure.py:881-921) on the device path → (mean batch BCE, accuracy).
+    `order`: a pre-drawn (order, batch_size) of test_loader (epoch_order) used instead of drawing one."""
     U, V = model.U.data, model.V.data
     store = SampleStore.from_loader(test_loader, U.shape[0], V.shape[0], U.device)
-    order, bs = epoch_order(test_loader)
+    order, bs = epoch_order(test_loader) if order is None else order
     loss, corr, _ = eval_batches(U, V, store.ordered(order), bs)
     total = int(order.numel())
     lsum = python_float_sum(loss.cpu().numpy())

@@ -87,6 +87,20 @@ def train_model(model, train_loader, val_loader, optimizer, device, num_epochs=1
     return out
 
 
+def train_models(models, train_loaders, val_loaders, optimizers, device, num_epochs=100):
+    """Extension (not in the reference): `[train_model(*args, device, num_epochs) for args in zip(...)]` in one go, with
+    the same results, optimizer states and RNG use.  The models the batched local form takes (fp32, torch.optim.Adam, the
+    tiny sizes the local form covers: n = m = 1000 at d = 2, n = m = 256 at d = 8) train side by side, one CU each, in a
+    fixed number of launches per epoch; every other model trains alone in its place (mfcd.engine.fit_many)."""
+    _need_gpu(device)
+    for model in models:
+        model.train()
+    out = _engine.fit_many(models, train_loaders, val_loaders, optimizers, num_epochs)
+    for model in models:
+        model.eval()
+    return out
+
+
 def evaluate_model(model, test_loader, device):
     """ref:881-921 → (mean batch BCE, accuracy of (p > 0.5) against the labels)."""
     _need_gpu(device)
@@ -108,8 +122,13 @@ def compute_ground_truth_metrics(test_loader, X, device):
     """ref:1085-1127: MSE between sigmoid(X[u,i]-X[u,j]) (no scale) and the labels, per batch, and
     the accuracy of (diff > 0).  Two-element gather per sample, once per experiment: torch ops on
     `device`, not a kernel."""
+    return _ground_truth_metrics(test_loader, X)
+
+
+def _ground_truth_metrics(test_loader, X, order=None):
+    """compute_ground_truth_metrics; `order`: a pre-drawn (order, batch_size) of test_loader instead of drawing one."""
     rows = torch.from_numpy(_engine.dataset_records(test_loader.dataset)).to(X.device)
-    order, bs = _engine.epoch_order(test_loader)  # same RNG draw as iterating the loader
+    order, bs = _engine.epoch_order(test_loader) if order is None else order  # same RNG draw as iterating the loader
     rows = rows[order.to(X.device)]
     u, i, j = rows[:, 0].long(), rows[:, 1].long(), rows[:, 2].long()
     z = rows[:, 3].float()
@@ -349,11 +368,125 @@ _RESULT_KEYS = ("reconstruction_errors", "log_likelihoods", "accuracy", "gt_log_
                 "alpha_per_row", "sampled_UVT_rows", "sampled_X_rows")
 
 
+_CONCURRENT = 1
+
+
+def set_concurrent_experiments(k):
+    """Extension (not in the reference): with k > 1, `run_experiment` (reps > 1) and the single-process
+    `parameter_scan` run their experiments in groups of up to k: each experiment's host phase (ground truth, split,
+    model init, every epoch order, the test orders and the randperm of ref:390) in the serial RNG order, then ONE
+    `train_models` for the group (the models train side by side on the GPU's CUs), then each experiment's metrics.
+    Results, pickles and the final torch / numpy RNG states equal the serial run's.  1 (default) is the serial path."""
+    global _CONCURRENT
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError(f"set_concurrent_experiments: k must be a positive integer (got {k!r})")
+    _CONCURRENT = int(k)
+
+
+class _Experiment:
+    """One repetition of run_experiment between its host phase and its metrics (grouped path)."""
+
+    def __init__(self, n, m, d, p, s, device, lr, weight_decay, num_epochs, K, strategy, popularity_method, alpha,
+                 soft_label, generation):
+        # ref:358-390 in the order the serial loop draws from torch's / numpy's generators
+        self.s, self.device, self.num_epochs = s, device, num_epochs
+        self.X = generate_X(n, m, d, device, generation=generation)
+        self.loaders = split_dataset_from_triplets(self.X, int(n * m * p / 2), scale=s, K=K, strategy=strategy,
+                                                   popularity_method=popularity_method, alpha=alpha,
+                                                   soft_label=soft_label)
+        self.model = MatrixFactorization(n, m, d).to(device)
+        self.optimizer = torch.optim.Adam(self.model.parameters(), lr=lr, weight_decay=weight_decay)
+        train_loader, val_loader, test_loader = self.loaders
+        self.orders = _engine.draw_orders(train_loader, val_loader, num_epochs)   # train_model
+        self.test_order = _engine.epoch_order(test_loader)                        # evaluate_model
+        self.rows = torch.randperm(self.X.shape[0])[:2]                           # ref:390
+        self.gt_order = _engine.epoch_order(test_loader)                          # compute_ground_truth_metrics
+        self.losses = None
+
+    def finish(self, res):
+        _need_gpu(self.device)
+        model, X, test_loader = self.model, self.X, self.loaders[2]
+        model.eval()
+        test_loss, test_acc = _engine.evaluate(model, test_loader, order=self.test_order)
+        rec_error = compute_reconstruction_error(model, X, self.s)
+        m14 = compute_alpha_and_norm_ratios(model, X)
+        gt_loss, gt_acc = _ground_truth_metrics(test_loader, X, self.gt_order)
+        _record(res, X, model, self.losses, test_loss, test_acc, rec_error, m14, self.rows, gt_loss, gt_acc)
+
+
+def _train_group(exps):
+    """train_models over a group of experiments, replaying their pre-drawn epoch orders."""
+    for ex in exps:
+        _need_gpu(ex.device)
+    models = [ex.model for ex in exps]
+    for model in models:
+        model.train()
+    out = _engine.fit_many(models, [ex.loaders[0] for ex in exps], [ex.loaders[1] for ex in exps],
+                           [ex.optimizer for ex in exps], [ex.num_epochs for ex in exps],
+                           orders=[ex.orders for ex in exps])
+    for ex, losses in zip(exps, out):
+        ex.model.eval()
+        ex.losses = losses
+
+
+def _record(res, X, model, losses, test_loss, test_acc, rec_error, m14, rows, gt_loss, gt_acc):
+    t_losses, v_losses = losses
+    for key, val in zip(("alpha", "norm_X", "norm_ratio", "reconstruction_error_scaled", "pearson_corr",
+                         "pearson_std", "spearman_corr", "spearman_std", "svd_error_scaled", "slopes",
+                         "pearson_corr_matrix", "spearman_corr_matrix", "reconstruction_error_scaled_per_row",
+                         "alpha_per_row"), m14):
+        res[key].append(val)
+    res["train_losses"].append(t_losses)
+    res["val_losses"].append(v_losses)
+    res["accuracy"].append(test_acc)
+    res["log_likelihoods"].append(-test_loss)
+    res["reconstruction_errors"].append(rec_error)
+    res["gt_log_likelihoods"].append(-gt_loss)
+    res["gt_accuracy"].append(gt_acc)
+    res["sampled_X_rows"].append(X[rows.to(X.device)].cpu().numpy())
+    res["sampled_UVT_rows"].append(_metrics.uvt_rows(model.U.data, model.V.data, rows).cpu().numpy())
+
+
+def _run_grouped(jobs, k, on_done):
+    """jobs: (announce, make, res, last) per experiment in serial order — announce() (or None) prints what starts,
+    make() (None: no repetition) runs the experiment's host phase, res is the result dict its metrics go to, last marks
+    the final repetition of a configuration (on_done() follows its metrics).  Runs them in groups of up to k."""
+    for a in range(0, len(jobs), k):
+        group = jobs[a:a + k]
+        exps = []
+        for announce, make, _, _ in group:
+            if announce is not None:
+                announce()
+            exps.append(make() if make is not None else None)
+        live = [ex for ex in exps if ex is not None]
+        if live:
+            _train_group(live)
+        for ex, (_, _, res, last) in zip(exps, group):
+            if ex is not None:
+                ex.finish(res)
+            if last:
+                on_done()
+
+
+def _experiment_jobs(res, reps, announce=None, **kw):
+    make = lambda: _Experiment(**kw)   # noqa: E731
+    if reps <= 0:
+        return [(announce, None, res, True)]
+    return [(announce if rep == 0 else None, make, res, rep == reps - 1) for rep in range(reps)]
+
+
 def run_experiment(n, m, d, p, s, device, lr, weight_decay, reps=5, num_epochs=100, open_browser=False, K=1,
                    d1=None, strategy="random", popularity_method="zipf", alpha=1.5, soft_label=False,
                    generation="base"):
-    """ref:306-450 → dict with the 23 keys of ref:420-444, one list entry per repetition."""
+    """ref:306-450 → dict with the 23 keys of ref:420-444, one list entry per repetition.
+    Under `set_concurrent_experiments(k)` with k > 1 the repetitions run in groups of up to k (same results)."""
     res = {k: [] for k in _RESULT_KEYS}
+    if _CONCURRENT > 1 and reps > 1:
+        jobs = _experiment_jobs(res, reps, n=n, m=m, d=d, p=p, s=s, device=device, lr=lr, weight_decay=weight_decay,
+                                num_epochs=num_epochs, K=K, strategy=strategy, popularity_method=popularity_method,
+                                alpha=alpha, soft_label=soft_label, generation=generation)
+        _run_grouped(jobs, _CONCURRENT, lambda: None)
+        return res
     for rep in range(reps):
         X = generate_X(n, m, d, device, generation=generation)
         loaders = split_dataset_from_triplets(X, int(n * m * p / 2), scale=s, K=K, strategy=strategy,
@@ -369,20 +502,7 @@ def run_experiment(n, m, d, p, s, device, lr, weight_decay, reps=5, num_epochs=1
         m14 = compute_alpha_and_norm_ratios(model, X)
         rows = torch.randperm(X.shape[0])[:2]                                     # ref:390 (global generator)
         gt_loss, gt_acc = compute_ground_truth_metrics(test_loader, X, device)
-        for key, val in zip(("alpha", "norm_X", "norm_ratio", "reconstruction_error_scaled", "pearson_corr",
-                             "pearson_std", "spearman_corr", "spearman_std", "svd_error_scaled", "slopes",
-                             "pearson_corr_matrix", "spearman_corr_matrix", "reconstruction_error_scaled_per_row",
-                             "alpha_per_row"), m14):
-            res[key].append(val)
-        res["train_losses"].append(t_losses)
-        res["val_losses"].append(v_losses)
-        res["accuracy"].append(test_acc)
-        res["log_likelihoods"].append(-test_loss)
-        res["reconstruction_errors"].append(rec_error)
-        res["gt_log_likelihoods"].append(-gt_loss)
-        res["gt_accuracy"].append(gt_acc)
-        res["sampled_X_rows"].append(X[rows.to(X.device)].cpu().numpy())
-        res["sampled_UVT_rows"].append(_metrics.uvt_rows(model.U.data, model.V.data, rows).cpu().numpy())
+        _record(res, X, model, (t_losses, v_losses), test_loss, test_acc, rec_error, m14, rows, gt_loss, gt_acc)
     return res
 
 
@@ -442,6 +562,31 @@ def parameter_scan(n=1000, m=1000, d=2, p=0.5, s=1.0, device='cpu', lr=1e-3, wei
     if world > 1:
         return scan_over_ranks(configs, run_one, rank, world, device, save_path, save_every)
     pending = []
+    if _CONCURRENT > 1:    # experiments of consecutive configurations grouped (set_concurrent_experiments)
+        jobs, done = [], []
+        for cfg in configs:
+            res = {k: [] for k in _RESULT_KEYS}
+            kw = dict(n=cfg["n"], m=cfg["m"], d=cfg["d"], p=cfg["p"], s=cfg["s"], device=device, lr=cfg["lr"],
+                      weight_decay=cfg["weight_decay"], num_epochs=cfg["num_epochs"], K=cfg["K"],
+                      strategy=cfg["strategy"], popularity_method=cfg["popularity_method"], alpha=cfg["alpha"],
+                      soft_label=cfg["soft_label"], generation=cfg["generation"])
+            announce = lambda cfg=cfg: print(f"\nRunning experiment with parameters: {cfg}")   # noqa: E731
+            jobs += _experiment_jobs(res, cfg["reps"], announce, **kw)
+            done.append((cfg, res))
+        finished = iter(done)
+
+        def on_done():
+            nonlocal pending
+            cfg, res = next(finished)
+            pending.append({"params": cfg, "results": res})
+            if save_path and save_every and len(pending) >= save_every:
+                _append_pickle(save_path, pending)
+                pending = []
+        _run_grouped(jobs, _CONCURRENT, on_done)
+        if save_path and pending:
+            _append_pickle(save_path, pending)
+            pending = []
+        return pending
     for cfg in configs:
         pending.append({"params": cfg, "results": run_one(cfg, device)})
         if save_path and save_every and len(pending) >= save_every:
