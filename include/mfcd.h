@@ -100,7 +100,7 @@ int mfcd_train_workspace_release(void *workspace);
 /*
  * Which form of the fused step mfcd_train_steps uses (process-wide):
  *   0 auto (default)  local where it applies; else resident where it applies and the call has at least
- *                     MFCD_TUNE_SHORT_CALL_STEPS (3) steps; else streaming
+ *                     3 steps; else streaming
  *   1 streaming       one launch per optimiser step, state streamed through HBM (any size, any d)
  *   2 resident        one persistent launch per call, p/m/v held in registers, rows exchanged through
  *                     tagged 8-byte granules; needs d a power of two <= 256, 12*(n+m)*d bytes of state that
@@ -127,18 +127,12 @@ int mfcd_set_resident_math(int fast);
 /*
  * Tuning knobs for experiments and tests (process-wide; the defaults are the measured best and what every
  * published number uses).  They replace the environment variables the round-1 build read on every launch.
+ * Keys 1, 2, 4, 6, 7, 8 and 12 are retired and not reused: like any unknown key they return MFCD_EINVAL.
  */
-#define MFCD_TUNE_RESIDENT_Q 1          /* 0 = smallest slice that fits (default); 1, 2, 4, 16 force it          */
-#define MFCD_TUNE_RESIDENT_WPC 2        /* waves per CU for slices of <= 2 registers: 16 (default) or 8        */
 #define MFCD_TUNE_RESIDENT_LOOKAHEAD 3  /* -1 auto (default: 4), 0 off, 2 .. 16 = depth of the window in steps */
-#define MFCD_TUNE_RESIDENT_LDS_PAD 4    /* unused dynamic LDS per workgroup, bytes (default 0)                 */
 #define MFCD_TUNE_RESIDENT_SPIN_LIMIT 5 /* polls before a wave gives up; 0 = default (2^22)                    */
-#define MFCD_TUNE_SHORT_CALL_STEPS 6    /* "auto": calls of fewer steps stream instead (default 3)             */
-#define MFCD_TUNE_UVT_WPE128 7          /* waves per SIMD of the d = 128 UV^T kernel: 2 (default) or 3        */
-#define MFCD_TUNE_STREAM_CHUNKS 8       /* streaming form: 16-byte chunks per thread and array; 0 = auto      */
 #define MFCD_TUNE_UVT_TARGET_WGS 9      /* UV^T pass: workgroups the column split aims for (default 512)       */
-#define MFCD_TUNE_UVT_SPLIT 11          /* UV^T pass, d in {32, 64, 128}: 1 (default) = bf16x3 split product on the bf16 matrix pipe, 0 = fp32 MFMA */
-#define MFCD_TUNE_RANK_SORT 12          /* Spearman kernel's sort: 1 (default) = block radix sort, 0 = bitonic network in LDS */
+#define MFCD_TUNE_UVT_SPLIT 11          /* UV^T pass, d in {32, 64, 128, 256}: 1 (default) = bf16x3 split product on the bf16 matrix pipe, 0 = fp32 MFMA */
 #define MFCD_TUNE_SHARD_PIPELINE 13     /* row-sharded native loop: 1 (default) = exchange of batch k+1 under step k when world > 1, 2 = always, 0 = strict chain */
 #define MFCD_TUNE_UVT_MIN_STAGES 10     /* UV^T pass: column stages a workgroup sweeps at least (default 8)    */
 int mfcd_set_tuning(int key, int64_t value);

@@ -25,9 +25,6 @@ namespace {
 
 using mfcd_detail::LocalArgs;
 
-#ifndef MFCD_LOCAL_PACKED
-#define MFCD_LOCAL_PACKED 1   // Adam on packed fp32 pairs (v_pk_*): bit-identical to the scalar form
-#endif
 constexpr unsigned kNoClaim = 0xFFFFFFFFu;
 constexpr int kSlots = 2;       // hits a lane group owns per step
 constexpr int kMaxLpsShift = 3; // at most 8 lanes per sample / per hit, i.e. at least 128 lane groups
@@ -226,7 +223,8 @@ __global__ __launch_bounds__(kLocalThreads) void local_train_kernel(LocalArgs a_
                 gr[q] = gacc[tid + kLocalThreads * q];
                 gacc[tid + kLocalThreads * q] = 0.0f;
             }
-            adam_update_q<FAST, QL, MFCD_LOCAL_PACKED != 0>(pe, m1, m2, gr, a.ac, sc);
+            // packed fp32 pairs (v_pk_*): bit-identical to the scalar form
+            adam_update_q<FAST, QL, true>(pe, m1, m2, gr, a.ac, sc);
 #pragma unroll
             for (int q = 0; q < QL; ++q) pL[tid + kLocalThreads * q] = pe[q];
         }

@@ -7,9 +7,9 @@
 // One workgroup of 1024 threads per row pair, everything in LDS:
 //   * the row becomes (sortable 32-bit key, 16-bit column) pairs; -0.0 ranks as +0.0 (numeric equality, as numpy
 //     compares);
-//   * bitonic sort of the pairs in the normalised (all-ascending) form over the next power of two P, the positions past
-//     m being virtual keys that sort last and never move (P/2 comparators per stage, log2(P)(log2(P)+1)/2 stages, one
-//     barrier each);
+//   * block-wide LSD radix sort of the pairs (rocPRIM's block_radix_sort: keys and column indices in registers, IPT
+//     per thread, digits ranked with wave-level match operations, exchanged through LDS; padding keys sort last) —
+//     ~5x fewer instructions per element at m = 20000 than a bitonic network through LDS;
 //   * a NaN anywhere in either row makes rho NaN (scipy's nan_policy='propagate');
 //   * every run of equal keys gets the doubled average rank 2*rank = first + last + 2 (0-based positions), written by
 //     the thread that holds the run's first element;
@@ -17,7 +17,7 @@
 //     column's A rank, and the three sums of the correlation are accumulated as EXACT 64-bit integers of the doubled,
 //     centred ranks (|2 rank - (m+1)| <= m, sums <= 4 m^3 < 2^46), reduced in fixed order; rho is formed in f64.
 // The result is therefore independent of thread scheduling and equals scipy's float64 computation to rounding.
-// LDS: 8 m bytes (156 KiB at m = 20000).
+// LDS: [sort storage, then sorted keys (4 m) + columns (2 m)] + A's doubled ranks by column (2 m): 156 KiB at m = 20000.
 // Rows longer than 20448 columns (BASELINE configs[3]: 65536 items) do not fit a workgroup's LDS: mfcd_spearman_rows_long
 // sorts a block of rows at a time in global memory — one device-wide SEGMENTED radix sort of (key, column) pairs per
 // matrix (a segment = a row) — and a workgroup per row then walks its sorted row exactly as above, with the sorted
@@ -56,84 +56,7 @@ __device__ __forceinline__ long long block_sum_i64(long long v, long long *red)
     return t;
 }
 
-__global__ __launch_bounds__(kRankThreads) void spearman_rows_kernel(const float *__restrict__ A, int64_t lda,
-                                                                     const float *__restrict__ X, int64_t ldx, int m,
-                                                                     int P, double *__restrict__ rho)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned *key = reinterpret_cast<unsigned *>(smem);                       // [m]
-    unsigned short *idx = reinterpret_cast<unsigned short *>(key + m);         // [m]
-    unsigned short *ra2 = idx + m;                                             // [m] doubled rank of A by column
-    __shared__ long long red[kRankThreads / 64];
-    const int tid = threadIdx.x;
-    const int64_t r = blockIdx.x;
-    const long long centre = (long long)m + 1;     // 2 * mean rank
-    long long saa = 0, sxx = 0, sxy = 0;
-    int has_nan = 0;   // scipy.stats.spearmanr propagates NaN: a NaN anywhere in either row makes rho NaN
-
-    for (int pass = 0; pass < 2; ++pass) {
-        const float *row = pass == 0 ? A + r * lda : X + r * ldx;
-        for (int p = tid; p < m; p += kRankThreads) {
-            const float f = row[p];
-            has_nan |= (f != f);
-            key[p] = sortable_key(f);
-            idx[p] = (unsigned short)p;
-        }
-        __syncthreads();
-        // Bitonic network over P = next power of two, in its NORMALISED form: every comparator is ascending (the first
-        // step of a merge pairs an element with its mirror image in the block, the following steps are half-cleaners).
-        // Positions m .. P-1 are VIRTUAL keys that sort last: with ascending comparators only they never move, so a
-        // comparator that touches one is a no-op and is skipped, and LDS holds m elements, not P (m = 20000, BASELINE
-        // configs[4], fits: 8 m bytes).
-        for (int k = 2; k <= P; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int t = tid; t < (P >> 1); t += kRankThreads) {
-                    const int i = 2 * j * (t / j) + (t % j);
-                    const int l = (j == (k >> 1)) ? (i ^ (k - 1)) : i + j;   // mirror in the k-block / half-cleaner
-                    if (l >= m) continue;
-                    const unsigned a = key[i], b = key[l];
-                    if (a > b) {
-                        key[i] = b;
-                        key[l] = a;
-                        const unsigned short ia = idx[i];
-                        idx[i] = idx[l];
-                        idx[l] = ia;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        // NaN keys (sortable value above +inf's) sort last among the real ones
-        long long s_own = 0, s_xy = 0;
-        for (int p = tid; p < m; p += kRankThreads) {
-            const unsigned kp = key[p];
-            if (p > 0 && key[p - 1] == kp) continue;            // not the first element of its run
-            int e = p;
-            while (e + 1 < m && key[e + 1] == kp) ++e;
-            const long long c2 = (long long)(p + e + 2) - centre;   // doubled, centred average rank of the run
-            s_own += c2 * c2 * (long long)(e - p + 1);
-            if (pass == 0) {
-                for (int q = p; q <= e; ++q) ra2[idx[q]] = (unsigned short)(p + e + 2);
-            } else {
-                for (int q = p; q <= e; ++q) s_xy += c2 * ((long long)ra2[idx[q]] - centre);
-            }
-        }
-        if (pass == 0) saa = s_own;
-        else { sxx = s_own; sxy = s_xy; }
-        __syncthreads();                                         // ra2 complete / key, idx free for the next pass
-    }
-    const long long Saa = block_sum_i64(saa, red), Sxx = block_sum_i64(sxx, red), Sxy = block_sum_i64(sxy, red);
-    const long long Snan = block_sum_i64((long long)has_nan, red);   // (not __syncthreads_or: it takes LDS of its own)
-    if (tid == 0)   // 0/0 -> NaN, as scipy for constants
-        rho[r] = Snan != 0 ? __longlong_as_double(0x7ff8000000000000ll) : (double)Sxy / (sqrt((double)Saa) * sqrt((double)Sxx));
-}
-
-
-// Round 3: the same kernel with the sort done by a block-wide LSD RADIX sort (rocPRIM's block_radix_sort: keys and
-// column indices in registers, IPT per thread, digits ranked with wave-level match operations, exchanged through LDS)
-// instead of the 120-stage bitonic network through LDS: ~5x fewer instructions per element at m = 20000.  Everything
-// after the sort — average ranks per run of equal keys, exact 64-bit sums, NaN propagation — is the code above.
-// LDS: [sort storage, then sorted keys (4 m) + columns (2 m)] + A's doubled ranks by column (2 m).
+// One workgroup per row pair (the scheme above).
 template <int IPT>
 __global__ __launch_bounds__(kRankThreads) void spearman_rows_radix_kernel(const float *__restrict__ A, int64_t lda,
                                                                            const float *__restrict__ X, int64_t ldx,
@@ -150,7 +73,7 @@ __global__ __launch_bounds__(kRankThreads) void spearman_rows_radix_kernel(const
     const int64_t r = blockIdx.x;
     const long long centre = (long long)m + 1;     // 2 * mean rank
     long long saa = 0, sxx = 0, sxy = 0;
-    int has_nan = 0;
+    int has_nan = 0;   // scipy.stats.spearmanr propagates NaN: a NaN anywhere in either row makes rho NaN
 
     for (int pass = 0; pass < 2; ++pass) {
         const float *row = pass == 0 ? A + r * lda : X + r * ldx;
@@ -198,8 +121,8 @@ __global__ __launch_bounds__(kRankThreads) void spearman_rows_radix_kernel(const
         else { sxx = s_own; sxy = s_xy; }
     }
     const long long Saa = block_sum_i64(saa, red), Sxx = block_sum_i64(sxx, red), Sxy = block_sum_i64(sxy, red);
-    const long long Snan = block_sum_i64((long long)has_nan, red);
-    if (tid == 0)
+    const long long Snan = block_sum_i64((long long)has_nan, red);   // (not __syncthreads_or: it takes LDS of its own)
+    if (tid == 0)   // 0/0 -> NaN, as scipy for constants
         rho[r] = Snan != 0 ? __longlong_as_double(0x7ff8000000000000ll) : (double)Sxy / (sqrt((double)Saa) * sqrt((double)Sxx));
 }
 
@@ -322,18 +245,7 @@ int long_block_rows(int rows, int m)
     return (int)(b < rows ? b : rows);
 }
 
-int g_rank_sort = 1;   // 1 = radix (default), 0 = bitonic network (mfcd_set_tuning(MFCD_TUNE_RANK_SORT))
-
 }  // namespace
-
-namespace mfcd_detail {
-int set_rank_sort(int v)
-{
-    if (v != 0 && v != 1) return MFCD_EINVAL;
-    g_rank_sort = v;
-    return 0;
-}
-}  // namespace mfcd_detail
 
 extern "C" int mfcd_spearman_max_columns(void) { return kRankMaxCols; }
 
@@ -343,24 +255,9 @@ extern "C" int mfcd_spearman_rows(const float *A, int64_t lda, const float *X, i
     if (!A || !X || !rho || rows < 0 || m <= 0 || lda < m || ldx < m) return MFCD_EINVAL;
     if (m > kRankMaxCols) return MFCD_EINVAL;
     if (rows == 0) return 0;
-    if (g_rank_sort == 1) {
-        if (m <= 4 * kRankThreads) return launch_radix<4>(A, lda, X, ldx, rows, m, rho, (hipStream_t)stream);
-        if (m <= 8 * kRankThreads) return launch_radix<8>(A, lda, X, ldx, rows, m, rho, (hipStream_t)stream);
-        return launch_radix<20>(A, lda, X, ldx, rows, m, rho, (hipStream_t)stream);
-    }
-    int P = 2;
-    while (P < m) P <<= 1;
-    const size_t lds = (size_t)m * 8;
-    static size_t allowed = 0;
-    if (lds > allowed) {
-        MFCD_HIP_TRY(hipFuncSetAttribute((const void *)spearman_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds));
-        allowed = lds;
-    }
-    hipLaunchKernelGGL(spearman_rows_kernel, dim3((unsigned)rows), dim3(kRankThreads), lds, (hipStream_t)stream, A, lda, X,
-                       ldx, m, P, rho);
-    MFCD_HIP_TRY(hipGetLastError());
-    return 0;
+    if (m <= 4 * kRankThreads) return launch_radix<4>(A, lda, X, ldx, rows, m, rho, (hipStream_t)stream);
+    if (m <= 8 * kRankThreads) return launch_radix<8>(A, lda, X, ldx, rows, m, rho, (hipStream_t)stream);
+    return launch_radix<20>(A, lda, X, ldx, rows, m, rho, (hipStream_t)stream);
 }
 
 extern "C" size_t mfcd_spearman_long_workspace_bytes(int rows, int m)

@@ -34,7 +34,7 @@
 // a width that was not built is simply absent (weak symbol) and the streaming form is used for it.
 #define MFCD_DECL(d)                                                                                                  \
     extern "C" int mfcd_resident_launch_d##d(const mfcd_detail::ResidentArgs *, int, int, void *) __attribute__((weak)); \
-    extern "C" int mfcd_resident_occupancy_d##d(int, int, int, int, int) __attribute__((weak));
+    extern "C" int mfcd_resident_occupancy_d##d(int, int, int, int) __attribute__((weak));
 MFCD_DECL(2) MFCD_DECL(4) MFCD_DECL(8) MFCD_DECL(16) MFCD_DECL(32) MFCD_DECL(64) MFCD_DECL(128) MFCD_DECL(256)
 #undef MFCD_DECL
 
@@ -44,7 +44,7 @@ int g_resident_math = 1;   // mfcd_set_resident_math: 1 = fast flavour (default)
 Tuning g_tune;             // mfcd_set_tuning
 
 typedef int (*ResidentLauncher)(const ResidentArgs *, int, int, void *);
-typedef int (*ResidentOccupancy)(int, int, int, int, int);
+typedef int (*ResidentOccupancy)(int, int, int, int);
 
 static ResidentLauncher launcher_for(int d)
 {
@@ -91,16 +91,16 @@ int resident_lookahead(int64_t N, int B, int n, int m)
 // Workgroups of the instantiation (d, Q, look, fast) one CU holds at once, as the runtime reports it for the actual
 // code object (register and LDS use), capped by the hardware's own admission rule for 256-thread workgroups
 // (MI355X_MICROARCH.md, Residency: min(API, 8, ...)); cached per instantiation.  0 = unknown (no device / query failed).
-static int resident_blocks_per_cu(int d, int Q, int look, int fast, int bf16, int lds_pad)
+static int resident_blocks_per_cu(int d, int Q, int look, int fast, int bf16)
 {
     static std::mutex mu;
     static std::vector<std::pair<long long, int>> cache;
-    const long long key = (((((long long)d * 64 + Q) * 16 + look) * 2 + fast) * 2 + bf16) * 262144 + lds_pad;
+    const long long key = ((((long long)d * 64 + Q) * 16 + look) * 2 + fast) * 2 + bf16;
     std::lock_guard<std::mutex> lock(mu);
     for (auto &e : cache)
         if (e.first == key) return e.second;
     int occ = 0;
-    if (ResidentOccupancy fn = occupancy_for(d)) occ = fn(Q, look, fast, bf16, lds_pad);
+    if (ResidentOccupancy fn = occupancy_for(d)) occ = fn(Q, look, fast, bf16);
     if (occ > 8) occ = 8;
     if (occ < 0) occ = 0;
     cache.emplace_back(key, occ);
@@ -137,8 +137,8 @@ ResidentEvents resident_events(int B, int n, int m, int d, int num_cus)
     // expected list entries per wave and step for uniformly drawn rows; a chunk of T steps (plus the boundary copies of
     // the deepest window) should average <= 20 of the 64 slots, so that an overflow is a property of the data (a row
     // most batches name), not of chance: P[Poisson(20) > 64] ~ 1e-14
-    // (priced for slices of TWICE the smallest size: the plan may take the next slice size up — waves-per-CU knob,
-    // occupancy of the actual code object — on the same workspace)
+    // (priced for slices of TWICE the smallest size: the plan may take the next slice size up — occupancy of the actual
+    // code object — on the same workspace)
     const double h = 2.0 * 3.0 * B * ev.rows_per_wave / (double)(n + m);
     for (int ts = 8; ts >= 4; --ts)
         if (h * ((1 << ts) + kResidentEventLook) <= 20.0) {
@@ -154,8 +154,6 @@ ResidentPlan plan_resident(int64_t N, int B, int n, int m, int d, int num_cus, b
     pl.ok = false;
     if (d < 2 || d > 256 || (d & (d - 1)) != 0 || num_cus <= 0 || !launcher_for(d)) return pl;
     const int64_t T = (int64_t)(n + m) * d;
-    const int forced_q = g_tune.resident_q;
-    const int wpc = g_tune.resident_wpc > 0 ? g_tune.resident_wpc : 16;
     int look = resident_lookahead(N, B, n, m);
     const bool fast = g_resident_math != 0;
     if (ev_tshift < 0) ev_tshift = resident_events(B, n, m, d, num_cus).tshift;
@@ -163,11 +161,10 @@ ResidentPlan plan_resident(int64_t N, int B, int n, int m, int d, int num_cus, b
     static const int kQ[5] = {1, 2, 4, 16, 32};
     for (int qi = 0; qi < 5; ++qi) {
         const int Q = kQ[qi];
-        if ((64 * Q) % d != 0 || (forced_q && Q != forced_q)) continue;
+        if ((64 * Q) % d != 0) continue;
         const int64_t nw = (T + 64 * (int64_t)Q - 1) / (64 * Q);
-        const int want_wpc = Q <= 2 ? wpc : 8;
-        if (nw <= (int64_t)num_cus * want_wpc && nw <= kResidentMaxWaves) {
-            const int occ = resident_blocks_per_cu(d, Q, look, fast, bf16, g_tune.lds_pad);
+        if (nw <= (int64_t)num_cus * (Q <= 2 ? 16 : 8) && nw <= kResidentMaxWaves) {
+            const int occ = resident_blocks_per_cu(d, Q, look, fast, bf16);
             const int blocks = (int)((nw + 3) / 4);
             if (occ > 0 && (int64_t)blocks > (int64_t)occ * num_cus) continue;   // would not be resident: next Q or none
             pl.ok = true;
@@ -195,9 +192,6 @@ ResidentPlan plan_resident(int64_t N, int B, int n, int m, int d, int num_cus, b
 //      an entry that finds its list full is dropped and the count says so (the wave then takes the generic loop).
 // INLINE: the table travels in the kernel-argument segment itself (first parameter, so it sits at offset 0 of the
 // segment, which every lane can address); short calls then need no read over the host link at all.
-#ifndef MFCD_PROLOGUE_THREADS
-#define MFCD_PROLOGUE_THREADS 64
-#endif
 constexpr int kInlineStageUnits = 232;   // 16-byte units: ResidentCold (8) + 224 step scalars; 3712 bytes of kernarg
 struct InlineStage {
     uint4 v[kInlineStageUnits];
@@ -281,7 +275,7 @@ int launch_train_prologue(const void *stage_host, const void *stage_host_devview
     const int64_t items = xs ? (N > units ? N : units) : units;
     // 64-thread workgroups: the kernel is a chain of dependent round trips per thread (record load, returning atomics,
     // entry stores), so it wants many workgroups per CU in flight, not few wide ones
-    constexpr int kPT = MFCD_PROLOGUE_THREADS;
+    constexpr int kPT = 64;
     const dim3 grid((unsigned)((items + kPT - 1) / kPT));
     if (units <= kInlineStageUnits) {
         InlineStage inl;
@@ -312,7 +306,6 @@ int launch_resident_steps(const ResidentPlan &pl, const void *cold_dev, const mf
     a.tag_base = tag_base;
     a.fast_math = pl.fast_math;
     a.bf16 = pl.bf16;
-    a.lds_pad = g_tune.lds_pad;
     ResidentLauncher fn = launcher_for(d);
     if (!fn) return MFCD_EINVAL;
     return fn(&a, pl.Q, pl.blocks, (void *)st);

@@ -11,7 +11,7 @@
 
 namespace {
 
-// dynamic LDS of one workgroup: the four waves' row-gradient accumulators for Q >= 16, plus the tuning pad
+// dynamic LDS of one workgroup: the four waves' row-gradient accumulators for Q >= 16
 template <int Q>
 constexpr size_t slice_lds() { return Q >= 16 ? (size_t)4 * 64 * Q * sizeof(float) : 0; }
 
@@ -43,7 +43,7 @@ template <int D, int Q>
 int launch_q(const mfcd_detail::ResidentArgs &a, int blocks, hipStream_t st)
 {
     const int look = (a.B <= 64 && a.lookahead > 0) ? a.lookahead : 0;
-    const size_t lds = slice_lds<Q>() + (size_t)a.lds_pad;
+    const size_t lds = slice_lds<Q>();
     hipError_t err = hipSuccess;
     const bool ok = with_kernel<D, Q>(look, a.fast_math, a.bf16, [&](auto kernel) {
         static size_t allowed = 48 * 1024;   // per instantiation: raise the dynamic-LDS limit only when needed
@@ -61,12 +61,12 @@ int launch_q(const mfcd_detail::ResidentArgs &a, int blocks, hipStream_t st)
 
 // workgroups per CU the runtime admits for the instantiation the launch above would pick (0: query failed / none)
 template <int D, int Q>
-int occupancy_q(int look, int fast, int bf16, int lds_pad)
+int occupancy_q(int look, int fast, int bf16)
 {
     int nb = 0;
     hipError_t e = hipSuccess;
     const bool ok = with_kernel<D, Q>(look, fast, bf16, [&](auto kernel) {
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, slice_lds<Q>() + (size_t)lds_pad);
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, slice_lds<Q>());
     });
     if (!ok) return 0;
     if (e != hipSuccess) {
@@ -78,14 +78,14 @@ int occupancy_q(int look, int fast, int bf16, int lds_pad)
 
 }  // namespace
 
-extern "C" int MFCD_CAT(mfcd_resident_occupancy_d, MFCD_RES_D)(int Q, int look, int fast, int bf16, int lds_pad)
+extern "C" int MFCD_CAT(mfcd_resident_occupancy_d, MFCD_RES_D)(int Q, int look, int fast, int bf16)
 {
     switch (Q) {
-        case 1: return occupancy_q<MFCD_RES_D, 1>(look, fast, bf16, lds_pad);
-        case 2: return occupancy_q<MFCD_RES_D, 2>(look, fast, bf16, lds_pad);
-        case 4: return occupancy_q<MFCD_RES_D, 4>(look, fast, bf16, lds_pad);
-        case 16: return occupancy_q<MFCD_RES_D, 16>(look, fast, bf16, lds_pad);
-        case 32: return occupancy_q<MFCD_RES_D, 32>(look, fast, bf16, lds_pad);
+        case 1: return occupancy_q<MFCD_RES_D, 1>(look, fast, bf16);
+        case 2: return occupancy_q<MFCD_RES_D, 2>(look, fast, bf16);
+        case 4: return occupancy_q<MFCD_RES_D, 4>(look, fast, bf16);
+        case 16: return occupancy_q<MFCD_RES_D, 16>(look, fast, bf16);
+        case 32: return occupancy_q<MFCD_RES_D, 32>(look, fast, bf16);
         default: return 0;
     }
 }

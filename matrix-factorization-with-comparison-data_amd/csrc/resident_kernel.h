@@ -140,7 +140,6 @@ struct ResidentArgs {
     int lookahead;           // 0: publish right before use (any B); >0: look-ahead form (B <= 64)
     int fast_math;           // Adam arithmetic flavour: 0 IEEE-rounded, 1 v_sqrt / Newton-corrected rcp
     int bf16;                // factor tables are bf16 in HBM (cold->U / V then point to 2-byte elements)
-    int lds_pad;             // unused dynamic LDS per workgroup: caps workgroups per CU so placement is even
     AdamStatic ac;
 };
 
@@ -183,7 +182,7 @@ void resident_train_kernel(ResidentArgs a)
     static_assert(EW % D == 0, "a wave's slice must hold whole rows");
     static_assert(EW / D <= kEventMaxLocalRows, "local row indices are 10-bit fields of an event entry");
     constexpr bool GRL = Q >= 16;             // row-gradient accumulators in LDS
-    extern __shared__ __attribute__((aligned(16))) float lds_dyn[];   // [4 waves][64*Q] when GRL (+ the lds_pad knob)
+    extern __shared__ __attribute__((aligned(16))) float lds_dyn[];   // [4 waves][64*Q] when GRL
     const int lane = threadIdx.x & 63;
     const int gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (gw >= a.NW) return;  // whole wave

@@ -370,7 +370,6 @@ Plan make_plan(const void *const *ptrs, int nptrs, int n, int m, int d)
     // at most 4 chunks (16 KiB of each array per workgroup): measured at C3 / C4 / C5 size (profiles/r02_stream_chunks.txt),
     // 8 chunks cost 4-10 % (fewer workgroups in flight per CU: the per-workgroup LDS tile doubles)
     while (pl.chunks < 4 && total / (256 * pl.vec * pl.chunks) > 2048) pl.chunks *= 2;
-    if (mfcd_detail::g_tune.stream_chunks) pl.chunks = mfcd_detail::g_tune.stream_chunks;   // experiment knob
     pl.E = 256 * pl.vec * pl.chunks;
     pl.blocksU = (int)(((int64_t)n * d + pl.E - 1) / pl.E);
     pl.blocksV = (int)(((int64_t)m * d + pl.E - 1) / pl.E);
@@ -437,8 +436,8 @@ void dispatch_step(const Plan &pl, hipStream_t st, const TP *Uin, const TP *Vin,
     if (pl.vec == V && pl.chunks == C)                                                                               \
         return launch_step<V, C, MODE, TP>(pl, st, Uin, Vin, Uout, Vout, mU, vU, mV, vV, batch, g_in, Bk, inv_batch, \
                                            n, m, d, ac, loss_terms, Gu, Gv, g_stride, u_off, v_off);
-    MFCD_CASE(4, 1) MFCD_CASE(4, 2) MFCD_CASE(4, 4) MFCD_CASE(4, 8)
-    MFCD_CASE(1, 1) MFCD_CASE(1, 2) MFCD_CASE(1, 4) MFCD_CASE(1, 8)
+    MFCD_CASE(4, 1) MFCD_CASE(4, 2) MFCD_CASE(4, 4)
+    MFCD_CASE(1, 1) MFCD_CASE(1, 2) MFCD_CASE(1, 4)
 #undef MFCD_CASE
 }
 
@@ -687,39 +686,17 @@ extern "C" int mfcd_set_tuning(int key, int64_t value)
 {
     mfcd_detail::Tuning &t = mfcd_detail::g_tune;
     switch (key) {
-        case MFCD_TUNE_RESIDENT_Q:
-            if (value != 0 && value != 1 && value != 2 && value != 4 && value != 16) return MFCD_EINVAL;
-            t.resident_q = (int)value;
-            return 0;
-        case MFCD_TUNE_RESIDENT_WPC:
-            if (value != 8 && value != 16) return MFCD_EINVAL;
-            t.resident_wpc = (int)value;
-            return 0;
         case MFCD_TUNE_RESIDENT_LOOKAHEAD:
             if (value < -1 || value == 1 || value > 16) return MFCD_EINVAL;
             t.lookahead = (int)value;
-            return 0;
-        case MFCD_TUNE_RESIDENT_LDS_PAD:
-            if (value < 0 || value > 160 * 1024) return MFCD_EINVAL;
-            t.lds_pad = (int)value;
             return 0;
         case MFCD_TUNE_RESIDENT_SPIN_LIMIT:
             if (value < 0 || value > 0x7fffffff) return MFCD_EINVAL;
             t.spin_limit = value == 0 ? mfcd_detail::kSpinLimitDefault : (unsigned)value;
             return 0;
-        case MFCD_TUNE_UVT_WPE128: return mfcd_detail::set_uvt_wpe128((int)value);
         case MFCD_TUNE_UVT_SPLIT: return mfcd_detail::set_uvt_split((int)value);
-        case MFCD_TUNE_RANK_SORT: return mfcd_detail::set_rank_sort((int)value);
         case MFCD_TUNE_UVT_TARGET_WGS: return mfcd_detail::set_uvt_target_wgs((int)value);
         case MFCD_TUNE_UVT_MIN_STAGES: return mfcd_detail::set_uvt_min_stages((int)value);
-        case MFCD_TUNE_STREAM_CHUNKS:
-            if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return MFCD_EINVAL;
-            t.stream_chunks = (int)value;
-            return 0;
-        case MFCD_TUNE_SHORT_CALL_STEPS:
-            if (value < 0 || value > 0x7fffffff) return MFCD_EINVAL;
-            t.short_call_steps = (int)value;
-            return 0;
         case MFCD_TUNE_SHARD_PIPELINE:
             if (value < 0 || value > 2) return MFCD_EINVAL;
             t.shard_pipeline = (int)value;
@@ -774,6 +751,10 @@ extern "C" int mfcd_train_workspace_release(void *workspace)
 
 namespace {
 
+// "auto": the persistent launch has a fixed cost (prologue kernel, slice load / store: ~10 us at C2) that a call of
+// fewer steps than this does not earn back against one streaming launch per step
+constexpr int64_t kShortCallSteps = 3;
+
 // form of the fused step a call with these sizes takes under the current settings
 struct FormChoice {
     int form;   // 1 streaming, 2 resident, 3 local, <0 error
@@ -803,9 +784,7 @@ FormChoice choose_form(bool f32, bool resident_planned, int ev_tshift, int64_t N
         c.form = resident_ok ? 2 : MFCD_EINVAL;
         return c;
     }
-    // auto: the persistent launch has a fixed cost (prologue kernel, slice load / store: ~10 us at C2) that a call of
-    // one or two steps does not earn back against one streaming launch per step
-    c.form = (resident_ok && nsteps >= mfcd_detail::g_tune.short_call_steps) ? 2 : 1;
+    c.form = (resident_ok && nsteps >= kShortCallSteps) ? 2 : 1;
     return c;
 }
 

@@ -205,23 +205,15 @@ constexpr unsigned kSpinLimitDefault = 1u << 22;  // polls before a wave gives u
 
 // process-wide tuning knobs (mfcd_set_tuning; experiments and tests only, defaults are the measured best)
 struct Tuning {
-    int resident_q = 0;          // 0 = smallest slice that fits; else force Q
-    int resident_wpc = 16;       // waves per CU bound for Q <= 2
     int lookahead = -1;          // -1 auto (4, or 0 for tiny tables), 0 off, else the window depth 2 .. 16
-    int lds_pad = 0;             // unused dynamic LDS per workgroup (bytes)
     unsigned spin_limit = kSpinLimitDefault;   // polls before a wave gives up and sets the status word
-    int stream_chunks = 0;       // streaming form: 16-byte chunks per thread and array (0 = by table size)
-    int short_call_steps = 3;    // "auto": calls of fewer steps than this stream (one launch per step) instead of
-                                 // paying the persistent launch's fixed cost
     int shard_pipeline = 1;      // row-sharded loop: 1 = exchange of batch k+1 under step k where no row is shared
 };
 extern Tuning g_tune;
 
 extern int g_resident_math;
 
-int set_uvt_wpe128(int v);   // uvt.hip
 int set_uvt_split(int v);    // uvt.hip
-int set_rank_sort(int v);    // rank.hip
 int set_uvt_target_wgs(int v);   // uvt.hip
 int set_uvt_min_stages(int v);   // uvt.hip
 

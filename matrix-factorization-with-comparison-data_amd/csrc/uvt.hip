@@ -20,10 +20,6 @@
 // Roofline: MFMA-bound for d >= 64 (2*n*m*d flop vs 4*n*m bytes of X), HBM-bound (X read) below.
 #include "common.h"
 
-#ifndef MFCD_UVT_EXP
-#define MFCD_UVT_EXP 0   // diagnostic builds only (tools/): 1 no X loads, 2 no f64 epilogue, 3 no MFMA
-#endif
-
 #ifndef MFCD_UVT_STAMPS
 #define MFCD_UVT_STAMPS 0   // diagnostic builds only (tools/diag_uvt_stamps.py): in-kernel cycle accounting per phase
 #endif
@@ -617,11 +613,7 @@ void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, 
         if constexpr (XV) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-#if MFCD_UVT_EXP == 1
-                xq[g] = f32x4{(float)cb, 1.f, 2.f, 3.f};
-#else
                 xq[g] = *reinterpret_cast<const f32x4 *>(xrow0 + min(cb + 8 * g + 4 * half, m - 4));
-#endif
             }
         } else {
 #pragma unroll
@@ -710,10 +702,6 @@ void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, 
                     for (int q = 0; q < QB; ++q) {
                         const f32x4 tq = t[bi & 1][q];
                         const int k0 = 4 * (bi * QB + q);
-#if MFCD_UVT_EXP == 3
-                        acc[0] += u[k0] * tq.x + u[k0 + 1] * tq.y + u[k0 + 2] * tq.z + u[k0 + 3] * tq.w;
-                        continue;
-#endif
                         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(tq.x, u[k0 + 0], acc, 0, 0, 0);
                         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(tq.y, u[k0 + 1], acc, 0, 0, 0);
                         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(tq.z, u[k0 + 2], acc, 0, 0, 0);
@@ -749,10 +737,6 @@ void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, 
                             const f32x2 av = g2 - rm2;                         // structure.py:985
                             const f32x2 cv = x2 - x02;                         // structure.py:987, up to the shift x0 - xm
                             const f32x2 ev = (g2 - c2) - s2 * x2;              // structure.py:943, 949
-#if MFCD_UVT_EXP == 2
-                            pe2 += av + cv + ev;
-                            continue;
-#endif
                             if constexpr ((WHAT & 1) != 0) {
                                 pac2 = __builtin_elementwise_fma(av, cv, pac2);
                                 paa2 = __builtin_elementwise_fma(av, av, paa2);
@@ -1290,9 +1274,7 @@ UvtWs plan_ws(char *base, int n, int m, int d)
     return w;
 }
 
-int g_uvt_wpe128 = 2;   // mfcd_set_tuning(MFCD_TUNE_UVT_WPE128): 2 = X prefetch at 2 waves/SIMD (default), 3 = round-1 form
-
-template <int DD, int NW, int TC, int WPE, bool PFX, int WHAT>
+template <int DD, int NW, int TC, bool PFX, int WHAT>
 void launch_tiled_what(const UvtWs &w, const float *U, const float *V, const float *X, int n, int m, float s, bool xv,
                        const UvtTail &tail, hipStream_t st)
 {
@@ -1307,22 +1289,22 @@ void launch_tiled_what(const UvtWs &w, const float *U, const float *V, const flo
         }
     }
     if (xv)
-        hipLaunchKernelGGL((uvt_tiled_kernel<DD, NW, TC, true, WPE, PFX, WHAT>), dim3(blocks), dim3(NW * 64), 0, st, U, V,
+        hipLaunchKernelGGL((uvt_tiled_kernel<DD, NW, TC, true, 2, PFX, WHAT>), dim3(blocks), dim3(NW * 64), 0, st, U, V,
                            X, w.rm, w.cm, n, m, s, w.cols_per_split, w.splits, row_blocks, w.part_rows, w.part_err,
                            w.part_xx, tail);
     else
-        hipLaunchKernelGGL((uvt_tiled_kernel<DD, NW, TC, false, WPE, false, WHAT>), dim3(blocks), dim3(NW * 64), 0, st, U,
+        hipLaunchKernelGGL((uvt_tiled_kernel<DD, NW, TC, false, 2, false, WHAT>), dim3(blocks), dim3(NW * 64), 0, st, U,
                            V, X, w.rm, w.cm, n, m, s, w.cols_per_split, w.splits, row_blocks, w.part_rows, w.part_err,
                            w.part_xx, tail);
 }
 
-template <int DD, int NW, int TC, int WPE = 2, bool PFX = (DD <= 128)>
+template <int DD, int NW, int TC, bool PFX = (DD <= 128)>
 int launch_tiled(const UvtWs &w, const float *U, const float *V, const float *X, int n, int m, float s, bool xv,
                  int what, const UvtTail &tail, hipStream_t st)
 {
-    if (what == 1) launch_tiled_what<DD, NW, TC, WPE, PFX, 1>(w, U, V, X, n, m, s, xv, tail, st);
-    else if (what == 2) launch_tiled_what<DD, NW, TC, WPE, PFX, 2>(w, U, V, X, n, m, s, xv, tail, st);
-    else launch_tiled_what<DD, NW, TC, WPE, PFX, 3>(w, U, V, X, n, m, s, xv, tail, st);
+    if (what == 1) launch_tiled_what<DD, NW, TC, PFX, 1>(w, U, V, X, n, m, s, xv, tail, st);
+    else if (what == 2) launch_tiled_what<DD, NW, TC, PFX, 2>(w, U, V, X, n, m, s, xv, tail, st);
+    else launch_tiled_what<DD, NW, TC, PFX, 3>(w, U, V, X, n, m, s, xv, tail, st);
     return 0;
 }
 
@@ -1347,13 +1329,6 @@ int set_uvt_split(int v)
 {
     if (v != 0 && v != 1) return MFCD_EINVAL;
     g_uvt_split = v;
-    return 0;
-}
-
-int set_uvt_wpe128(int v)
-{
-    if (v != 2 && v != 3) return MFCD_EINVAL;
-    g_uvt_wpe128 = v;
     return 0;
 }
 }  // namespace mfcd_detail
@@ -1394,13 +1369,13 @@ int run_uvt(const float *U, const float *V, const float *Xs, int n, int m, int d
         const int rpb = 16;
         hipLaunchKernelGGL(centre_vectors_kernel, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256),
                            sizeof(float) * 2 * (size_t)(d + 1) + (merged ? sizeof(double) * 8 * (size_t)d : 0), st, U, V, wf.colpart, merged ? (const float *)nullptr : wf.bar, n,
-                           m, d, rpb, wf.rm, wf.cm, (ws.tiled && al16 && xv && !(d == 128 && g_uvt_wpe128 == 3)) ? wf.vsplit : nullptr);
+                           m, d, rpb, wf.rm, wf.cm, (ws.tiled && al16 && xv) ? wf.vsplit : nullptr);
     }
     const float *Us = U + (int64_t)row0 * d;
     UvtWs w = ws;            // the slab's partial-sum arrays, with the full problem's centring vectors
     w.rm = wf.rm + row0;
     w.cm = wf.cm;
-    w.vsplit = (ws.tiled && al16 && xv && !(d == 128 && g_uvt_wpe128 == 3)) ? wf.vsplit : nullptr;
+    w.vsplit = (ws.tiled && al16 && xv) ? wf.vsplit : nullptr;
     const int nn = nrows;
     if (tiled) {
         // short passes (C2: 37 us), three launches: column sums, centring vectors (+ split table), main kernel — whose
@@ -1411,8 +1386,7 @@ int run_uvt(const float *U, const float *V, const float *Xs, int n, int m, int d
         const UvtTail tail{row_stats, w.blk, scal, fold ? w.cnt : nullptr, s};
         int rc = 0;
         if (d == 256) rc = launch_tiled<256, 4, 32>(w, Us, V, Xs, nn, m, (float)s, xv, what, tail, st);
-        else if (d == 128 && g_uvt_wpe128 == 3) rc = launch_tiled<128, 4, 32, 3, false>(w, Us, V, Xs, nn, m, (float)s, xv, what, tail, st);
-        else if (d == 128) rc = launch_tiled<128, 4, 64, 2, true>(w, Us, V, Xs, nn, m, (float)s, xv, what, tail, st);
+        else if (d == 128) rc = launch_tiled<128, 4, 64>(w, Us, V, Xs, nn, m, (float)s, xv, what, tail, st);
         else if (d == 64) rc = launch_tiled<64, 4, 64>(w, Us, V, Xs, nn, m, (float)s, xv, what, tail, st);
         else rc = launch_tiled<32, 4, 128>(w, Us, V, Xs, nn, m, (float)s, xv, what, tail, st);
         if (rc) return rc;

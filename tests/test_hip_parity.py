@@ -330,10 +330,18 @@ def test_empty_and_error_paths(dev):
     assert L.mfcd_error_string(-2).decode().startswith("mfcd: workspace")
 
 
-@pytest.mark.parametrize("n,m,d", [(4096, 4096, 64), (1000, 777, 8), (300, 5000, 128), (257, 95, 2), (96, 64, 256),
-                                   (130, 70, 24), (301, 203, 64), (1003, 333, 256), (70, 517, 32), (33, 40, 128)])
-def test_uvt_stats_match_oracle(dev, orc, n, m, d):
-    from mfcd import metrics
+_UVT_SHAPES = [(4096, 4096, 64), (1000, 777, 8), (300, 5000, 128), (257, 95, 2), (96, 64, 256),
+               (130, 70, 24), (301, 203, 64), (1003, 333, 256), (70, 517, 32), (33, 40, 128)]
+# split = 0 (d in {32, 64, 128, 256}): the fp32 MFMA product instead of the default bf16x3 split, the reference's own
+# arithmetic (mfcd_set_tuning(MFCD_TUNE_UVT_SPLIT, 0))
+_UVT_CASES = [(n, m, d, 1) for n, m, d in _UVT_SHAPES] + \
+             [(n, m, d, 0) for n, m, d in _UVT_SHAPES if d in (32, 64, 128, 256)]
+
+
+@pytest.mark.parametrize("n,m,d,split", _UVT_CASES,
+                         ids=[f"{n}-{m}-{d}" + ("" if split else "-fp32") for n, m, d, split in _UVT_CASES])
+def test_uvt_stats_match_oracle(dev, orc, n, m, d, split):
+    from mfcd import engine, metrics
     rng = np.random.default_rng(n + m + d)
     U = (rng.standard_normal((n, d)) / np.sqrt(d)).astype(np.float32)
     V = (rng.standard_normal((m, d)) / np.sqrt(d)).astype(np.float32)
@@ -341,8 +349,12 @@ def test_uvt_stats_match_oracle(dev, orc, n, m, d):
     Bm = rng.standard_normal((m, d)).astype(np.float32)
     X = (A @ Bm.T / np.sqrt(d) * 0.5 + 0.1).astype(np.float32)
     s = 1.7
-    rs, scal = metrics.uvt_stats(torch.from_numpy(U).to(dev), torch.from_numpy(V).to(dev), torch.from_numpy(X).to(dev), s)
-    rs, scal = rs.cpu().numpy(), scal.cpu().numpy()
+    try:
+        engine.set_tuning(uvt_split=split)
+        rs, scal = metrics.uvt_stats(torch.from_numpy(U).to(dev), torch.from_numpy(V).to(dev), torch.from_numpy(X).to(dev), s)
+        rs, scal = rs.cpu().numpy(), scal.cpu().numpy()
+    finally:
+        engine.set_tuning(uvt_split=1)
     if n * m <= 1 << 21:
         ref_rs, err2, ref2 = orc.uvt_stats(U, V, X, s)
     else:  # f64 numpy statement of the same sums for the large case

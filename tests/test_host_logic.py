@@ -27,6 +27,8 @@ def test_library_exports_every_declared_symbol():
     # an unregistered workspace is refused before anything touches the device; tuning setters validate their input
     assert L.mfcd_set_tuning(_lib.TUNE_KEYS["resident_lookahead"], 17) == -1
     assert L.mfcd_set_tuning(_lib.TUNE_KEYS["resident_lookahead"], -1) == 0
+    for key, former_default in ((1, 0), (2, 16), (4, 0), (6, 3), (7, 2), (8, 0), (12, 1)):   # retired keys
+        assert L.mfcd_set_tuning(key, former_default) == -1, key
     assert L.mfcd_train_workspace_release(None) == 0
     assert L.mfcd_error_string(-6).decode().startswith("mfcd: workspace not initialised")
     plan = _lib.TrainPlan()

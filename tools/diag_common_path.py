@@ -10,7 +10,7 @@ from mfcd import engine
 dev = torch.device("cuda:0")
 size = [a for a in sys.argv[1:] if "=" not in a]
 knobs = [a for a in sys.argv[1:] if "=" in a]
-if knobs:     # e.g. resident_q=4 resident_lookahead=8
+if knobs:     # e.g. resident_lookahead=8 resident_spin_limit=65536
     engine.set_tuning(**{k: int(v) for k, v in (a.split("=") for a in knobs)})
 n = m = 4096; d = 64
 if size and size[0] == "C3":
