@@ -36,7 +36,6 @@ constexpr int kWavesPerSimd = 128 / kRows;           // 1 (512 registers per lan
 constexpr int kWaves = 1024 * kWavesPerSimd;         // over the 1 024 SIMDs of the 256 CUs
 constexpr int kSlots = kRows == 128 ? 16 : (kRows == 64 ? 8 : 6);   // distinct rows of a wave one batch may touch (more: the call is refused)
 static_assert(kRows == 128 || kRows == 64 || kRows == 32, "slices of 128, 64 or 32 rows");
-constexpr unsigned kSpinLimit = 1u << 22;
 
 struct BigArgs {
     float *U, *V, *mU, *vU, *mV, *vV;
@@ -152,7 +151,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
                     }
                     if (__all(ok)) break;
                     ++spins;
-                    if (spins > kSpinLimit ||
+                    if (spins > mfcd_detail::kSpinLimitDefault ||
                         ((spins & 255u) == 0 && __hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
                         if (lane == 0) __hip_atomic_fetch_max(a.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         alive = false;
@@ -266,19 +265,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     }
 }
 
-// mean of the batch's BCE terms in the fixed order of the streaming form's batch_mean_kernel (one wave per step)
-__global__ __launch_bounds__(64) void big_batch_mean_kernel(const float *__restrict__ terms, long long N, int B,
-                                                            float *__restrict__ out)
-{
-    const int lane = threadIdx.x;
-    const long long off = (long long)blockIdx.x * B;
-    const int b = (int)((N - off) < B ? (N - off) : B);
-    float acc = 0.0f;
-    for (int t = lane; t < b; t += MFCD_WAVE) acc += terms[off + t];
-    acc = wave_sum64(acc);
-    if (lane == 0) out[blockIdx.x] = acc / (float)b;
-}
-
 // per step: row references of the batch per wave slice (an upper bound of the distinct rows a wave must hold gradient
 // slots for); the maximum over the call goes to *max_out
 __global__ __launch_bounds__(256) void big_check_kernel(const mfcd_sample *__restrict__ samples, long long N, int B, int n,
@@ -305,23 +291,16 @@ __global__ __launch_bounds__(256) void big_check_kernel(const mfcd_sample *__res
     if ((threadIdx.x & 63) == 0 && mx > 0) atomicMax(max_out, mx);
 }
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 constexpr size_t kLds = sizeof(float) * ((size_t)4 * kRows * kD + (size_t)4 * kSlots * kD);
 
 }  // namespace
-
-namespace mfcd_detail {
-// train.hip: host-side Adam constants (f64 as Python computes them, rounded where ATen rounds)
-AdamStatic big_adam_static(double beta1, double beta2, double eps, double wd);
-StepScalars big_step_scalars(double lr, double beta1, double beta2, int64_t step);
-}  // namespace mfcd_detail
 
 extern "C" size_t mfcd_train_big_workspace_bytes(int64_t N, int B)
 {
     if (N <= 0 || B <= 0 || B > 64) return 0;
     const size_t K = (size_t)((N + B - 1) / B);
-    return 256 + up256(sizeof(StepScalars) * K) + up256(sizeof(float) * (size_t)N) + up256(sizeof(u64) * (size_t)N * 3 * kD);
+    return 256 + align_up(sizeof(StepScalars) * K) + align_up(sizeof(float) * (size_t)N) +
+           align_up(sizeof(u64) * (size_t)N * 3 * kD);
 }
 
 extern "C" int mfcd_train_steps_big(float *U, float *V, float *mU, float *vU, float *mV, float *vV,
@@ -352,22 +331,19 @@ extern "C" int mfcd_train_steps_big(float *U, float *V, float *mU, float *vU, fl
     char *ws = (char *)workspace;
     int *status = (int *)ws;
     StepScalars *sc_dev = (StepScalars *)(ws + 256);
-    float *terms = (float *)((char *)sc_dev + up256(sizeof(StepScalars) * (size_t)K));
-    u64 *mailbox = (u64 *)((char *)terms + up256(sizeof(float) * (size_t)N));
+    float *terms = (float *)((char *)sc_dev + align_up(sizeof(StepScalars) * (size_t)K));
+    u64 *mailbox = (u64 *)((char *)terms + align_up(sizeof(float) * (size_t)N));
     std::vector<StepScalars> sc((size_t)K);
-    for (int k = 0; k < K; ++k) sc[(size_t)k] = mfcd_detail::big_step_scalars(lr, beta1, beta2, step0 + k + 1);
+    for (int k = 0; k < K; ++k) sc[(size_t)k] = step_scalars(lr, beta1, beta2, step0 + k + 1);
     MFCD_HIP_TRY(hipMemcpyAsync(sc_dev, sc.data(), sizeof(StepScalars) * (size_t)K, hipMemcpyHostToDevice, st));
     MFCD_HIP_TRY(hipStreamSynchronize(st));          // (the table is on this call's stack)
     MFCD_HIP_TRY(hipMemsetAsync(status, 0, 256, st));
     MFCD_HIP_TRY(hipMemsetAsync(mailbox, 0, sizeof(u64) * (size_t)N * 3 * kD, st));
     BigArgs a{U, V, mU, vU, mV, vV, samples, (long long)N, B, K, n, m, sc_dev,
-              mfcd_detail::big_adam_static(beta1, beta2, eps, weight_decay), mailbox, terms, status};
+              adam_static(beta1, beta2, eps, weight_decay), mailbox, terms, status};
     hipLaunchKernelGGL(kernel, dim3(kWaves / 4), dim3(256), kLds, st, a);
     MFCD_HIP_TRY(hipGetLastError());
-    if (loss_per_step) {
-        hipLaunchKernelGGL(big_batch_mean_kernel, dim3((unsigned)K), dim3(64), 0, st, terms, (long long)N, B, loss_per_step);
-        MFCD_HIP_TRY(hipGetLastError());
-    }
+    if (loss_per_step) return mfcd_detail::launch_batch_means(terms, nullptr, N, B, loss_per_step, st);
     return 0;
 }
 

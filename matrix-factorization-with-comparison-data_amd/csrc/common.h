@@ -12,6 +12,9 @@
 
 #define MFCD_WAVE 64
 
+// workspace regions start on 256-byte boundaries
+inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) & ~(a - 1); }
+
 #define MFCD_HIP_TRY(expr)                        \
     do {                                          \
         hipError_t e__ = (expr);                  \

@@ -225,7 +225,7 @@ int long_carve(int block_rows, int m, void *base, LongCarve &c)
         return MFCD_EINVAL;
     char *p = (char *)base;
     size_t off = 0;
-    auto take = [&](size_t bytes) { char *q = p ? p + off : nullptr; off += (bytes + 255) & ~(size_t)255; return (void *)q; };
+    auto take = [&](size_t bytes) { char *q = p ? p + off : nullptr; off += align_up(bytes); return (void *)q; };
     c.k_in = (unsigned *)take(E * 4); c.c_in = (unsigned *)take(E * 4);
     c.kA = (unsigned *)take(E * 4); c.cA = (unsigned *)take(E * 4);
     c.kX = (unsigned *)take(E * 4); c.cX = (unsigned *)take(E * 4);

@@ -190,8 +190,6 @@ struct Carve {
     size_t temp_bytes, total_bytes;
 };
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int carve(int64_t A, int64_t E, void *base, Carve &c)
 {
     const size_t T = (size_t)(A + E);
@@ -202,7 +200,7 @@ int carve(int64_t A, int64_t E, void *base, Carve &c)
                                 rocprim::plus<int32_t>(), (hipStream_t)0) != hipSuccess) return MFCD_EINVAL;
     char *p = (char *)base;
     size_t off = 0;
-    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += up256(bytes); return (void *)r; };
+    auto take = [&](size_t bytes) { char *r = p ? p + off : nullptr; off += align_up(bytes); return (void *)r; };
     c.keys_in = (uint64_t *)take(T * 8);
     c.keys_out = (uint64_t *)take(T * 8);
     c.vals_in = (uint32_t *)take(T * 4);

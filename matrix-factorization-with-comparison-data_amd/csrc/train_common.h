@@ -1,4 +1,5 @@
-// Shared between the streaming (train.hip) and resident (resident.hip) forms of the optimiser step.
+// Shared between the forms of the optimiser step: streaming (streaming.hip), resident (resident.hip), local (local.hip),
+// big (big.hip), the fused-step entry (train.hip) and the multi-GPU loops (dist.hip).
 #pragma once
 #include "common.h"
 
@@ -18,6 +19,53 @@ struct StepScalars {
     float inv_bc2_sqrt;   // 1 / sqrt(1 - beta2^t), rounded from f64 (used by the fast flavour only)
     float pad;
 };
+
+struct AdamConst {
+    AdamStatic st;
+    StepScalars sc;
+};
+
+// host-side Adam constants (f64 as Python computes them, rounded where ATen rounds)
+inline AdamStatic adam_static(double beta1, double beta2, double eps, double wd)
+{
+    AdamStatic a;
+    a.w1 = (float)(1.0 - beta1);
+    a.b2 = (float)beta2;
+    a.w2 = (float)(1.0 - beta2);
+    a.eps = (float)eps;
+    a.wd = (float)wd;
+    return a;
+}
+
+inline StepScalars step_scalars(double lr, double beta1, double beta2, int64_t step)
+{
+    // bias corrections in f64 as Python does (adam.py: 1 - beta**step, lr / bc1, bc2 ** 0.5)
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    StepScalars s;
+    s.neg_step_size = (float)(-(lr / bc1));
+    s.bc2_sqrt = (float)sqrt(bc2);
+    s.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+    s.pad = 0.0f;
+    return s;
+}
+
+inline AdamConst adam_const(double lr, double beta1, double beta2, double eps, double wd, int64_t step)
+{
+    AdamConst ac;
+    ac.st = adam_static(beta1, beta2, eps, wd);
+    ac.sc = step_scalars(lr, beta1, beta2, step);
+    return ac;
+}
+
+constexpr size_t kStatusBytes = 256;  // workspace[0..3] = int32 status word (sticky: set by an aborting resident launch)
+
+// the table arguments every training entry point checks first
+inline int check_common(const void *U, const void *V, int n, int m, int d)
+{
+    if (!U || !V || n <= 0 || m <= 0 || d <= 0 || d > MFCD_MAX_D) return MFCD_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(U) & 3u) || (reinterpret_cast<uintptr_t>(V) & 3u)) return MFCD_EALIGN;
+    return 0;
+}
 
 // One element of torch.optim.Adam's single-tensor step (coupled L2).  The operation sequence is pinned
 // (explicit fmaf, contraction off) so that every inlined copy rounds identically — the resident kernel relies on
@@ -161,7 +209,7 @@ int launch_local_multi(const LocalArgs *tab_dev, int R, int ql, bool small_batch
 constexpr int kLocalSmallBatch = 1024;   // batches of at most this many records: one staging slot per thread
 
 // one segment of a flat multi-model grid: blocks [blk_begin, next segment's blk_begin) belong to one model
-struct MeanSeg {       // batch_mean_kernel (train.hip): the per-step batch means of one model
+struct MeanSeg {       // batch_mean_kernel (streaming.hip): the per-step batch means of one model
     const float *terms;
     const mfcd_sample *samples;
     float *out;
@@ -191,6 +239,28 @@ __device__ __forceinline__ int find_seg(const Seg *segs, int nseg, int64_t blk)
 }
 
 int launch_eval_multi(const EvalSeg *segs_dev, int nseg, int64_t blocks, int max_B, hipStream_t st);
+
+// ---- streaming form (streaming.hip): one launch of train_step_kernel per optimiser step ----
+struct Plan {
+    int vec, chunks, E, blocksU, blocksV;
+    size_t lds;
+};
+// ptrs: the arrays the step reads and writes (vec = 4 needs every one of them 16-byte aligned)
+Plan make_plan(const void *const *ptrs, int nptrs, int n, int m, int d);
+
+// One train_step_kernel<VEC, CHUNKS, MODE, TP> launch with the plan's instance (MODE: see the kernel).  Instantiated for
+// MODE 0 and 3 with fp32 and bf16 tables, 1 and 2 with fp32.  Error checking is the caller's (hipGetLastError).
+template <int MODE, typename TP>
+void launch_streaming_step(const Plan &pl, hipStream_t st, const TP *Uin, const TP *Vin, TP *Uout, TP *Vout, float *mU,
+                           float *vU, float *mV, float *vV, const mfcd_sample *batch, const float *g_in, int Bk,
+                           float inv_batch, int n, int m, int d, const AdamConst &ac, float *loss_terms,
+                           float *Gu = nullptr, float *Gv = nullptr, int g_stride = 1, int u_off = 0, int v_off = 0);
+
+// batch_mean_kernel: out[k] = mean of the BCE terms of batch k of N samples, k < ceil(N / B); terms[] holds sigmoid
+// outputs p when `samples` is set, ready BCE terms otherwise
+int launch_batch_means(const float *terms, const mfcd_sample *samples, int64_t N, int B, float *out, hipStream_t st);
+// the same over a flat multi-model grid of `blocks` batches (segs_dev: device copy of the segment table)
+int launch_batch_means_multi(const MeanSeg *segs_dev, int nseg, int64_t blocks, hipStream_t st);
 
 struct ResidentPlan {
     bool ok;

@@ -1183,8 +1183,6 @@ struct UvtWs {
     size_t bytes;
 };
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct TiledCfg {
     int NW, TC;   // waves per workgroup (32 rows each), columns per LDS stage; NW == 0: no tiled form for this d
 };
@@ -1246,7 +1244,7 @@ UvtWs plan_ws(char *base, int n, int m, int d)
     w.n_err = w.splits * rtiles;
     w.nblk = (n + 255) / 256;
     size_t off = 0;
-    auto take = [&](size_t b) { char *p = base ? base + off : nullptr; off += al(b); return p; };
+    auto take = [&](size_t b) { char *p = base ? base + off : nullptr; off += align_up(b); return p; };
     w.colpart = (double *)take(sizeof(double) * 2 * kSlices * (size_t)d);
     w.bar = (float *)take(sizeof(float) * 2 * (size_t)d);
     w.rm = (float *)take(sizeof(float) * (size_t)n);

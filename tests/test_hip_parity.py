@@ -2148,3 +2148,41 @@ def test_abandoned_staged_prologue_leaves_no_trace(dev):
         engine.set_train_path("auto")
     for x, y in zip(*outs):
         assert torch.equal(x, y)
+
+
+@pytest.mark.gpu
+def test_staged_prologue_follows_a_changed_learning_rate(dev):
+    """A staged prologue's step table holds the step scalars of the lr / betas current when it was staged.  A caller
+    that changes the learning rate between staging and the call (a schedule writing param_groups) gets a new prepared
+    call; that call must build its own prologue, not take the staged table: stage at lr = a, switch to lr = b, run:
+    BIT-identical to the same call run unstaged at lr = b, losses and both moments included."""
+    from mfcd import engine
+    n, m, d, N = 4096, 4096, 64, 64 * 150 + 17
+    U0, V0, u, i, j, z = _synthetic(n, m, d, 2 * N, seed=35)
+    recs = [_records(u[k * N:(k + 1) * N], i[k * N:(k + 1) * N], j[k * N:(k + 1) * N], z[k * N:(k + 1) * N], n, m, dev).dev
+            for k in range(2)]
+    side = torch.cuda.Stream(device=dev)
+    engine.set_train_path("resident")
+    try:
+        assert engine.train_plan(N, 64, n, m, d)["resident_lookahead"] > 0   # the form whose prologue is staged
+        outs = []
+        for staged in (True, False):
+            model, opt = _model_from(U0, V0, dev, 1e-3, 1e-5)
+            bind = engine.AdamBinding(model, opt)
+            nb = (N + 63) // 64
+            loss = [torch.empty(nb, device=dev) for _ in range(2)]
+            engine.train_steps(bind, recs[0], 64, loss_out=loss[0])          # makes the prepared call at lr = a
+            torch.cuda.synchronize()
+            if staged:
+                assert engine.stage_next_call(bind, recs[1], 64, loss[1], side)      # step table built at lr = a
+                torch.cuda.synchronize()
+            opt.param_groups[0]["lr"] = 3e-3                                     # lr = b
+            engine.train_steps(bind, recs[1], 64, loss_out=loss[1])
+            torch.cuda.synchronize()
+            st = [opt.state[p][k].clone() for p in (model.U, model.V) for k in ("exp_avg", "exp_avg_sq")]
+            outs.append([loss[1].clone(), model.U.data.clone(), model.V.data.clone()] + st)
+        engine.check_status()
+    finally:
+        engine.set_train_path("auto")
+    for x, y in zip(*outs):
+        assert torch.equal(x, y)
