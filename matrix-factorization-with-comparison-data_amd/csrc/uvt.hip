@@ -20,22 +20,6 @@
 // Roofline: MFMA-bound for d >= 64 (2*n*m*d flop vs 4*n*m bytes of X), HBM-bound (X read) below.
 #include "common.h"
 
-#ifndef MFCD_UVT_STAMPS
-#define MFCD_UVT_STAMPS 0   // diagnostic builds only (tools/diag_uvt_stamps.py): in-kernel cycle accounting per phase
-#endif
-#if MFCD_UVT_STAMPS
-__device__ unsigned long long mfcd_uvt_dbg[8];   // chain, epilogue, sync, dma-issue cycles; tiles; waves
-// MFCD_UVT_STAMPS=2: no per-phase stamp (the kernel keeps its timing); only the clock of the stage loop:
-// [6] += shader cycles, [7] += 100 MHz real-time ticks, per wave
-#if MFCD_UVT_STAMPS == 1
-#define MFCD_STAMP(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#else
-#define MFCD_STAMP(var) const unsigned long long var = 0
-#endif
-#else
-#define MFCD_STAMP(var)
-#endif
-
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -461,9 +445,24 @@ __device__ __forceinline__ void split_read_batch(f32x4 (&t)[4], unsigned abase, 
     }
 }
 
-// PFX: fetch a tile's X values one tile ahead (needs ~45 more registers: two register sets, two copies of the tile
-// body).  On for d <= 128, where an HBM round trip outlasts a tile's MFMA chain; off for d = 256, whose 128-MFMA chain
-// covers it and whose 128-register operand leaves no room.
+// The tiled kernel's shape per factor width: NW waves per workgroup (32 rows each), TC columns per LDS stage.
+struct TiledShape {
+    int NW, TC;   // NW == 0: no tiled form for this d
+};
+constexpr TiledShape tiled_shape(int d)
+{
+    return d == 256 ? TiledShape{4, 32}     // 64 KiB of stages: two workgroups (two waves per SIMD) per CU
+         : d == 128 ? TiledShape{4, 64}     // two tiles per stage: the X prefetch alternates between two register sets
+         : d == 64 ? TiledShape{4, 64}
+         : d == 32 ? TiledShape{4, 128}
+         : TiledShape{0, 0};
+}
+
+// uvt_tiled_kernel<D, XV, WHAT, SPLIT>.  XV: X rows are 16-byte aligned (16-byte X pieces).
+// PFX, derived as XV && (SPLIT || D <= 128): fetch a tile's X values one tile ahead (needs ~45 more registers: two
+// register sets, two copies of the tile body).  On for d <= 128 and for the split product, where an HBM round trip
+// outlasts a tile's MFMA chain; off for the fp32 product at d = 256, whose 128-MFMA chain covers it and whose
+// 128-register operand leaves no room; off for scalar X, as it is built for four 16-byte loads per request.
 // WHAT: 1 = per-row sums only (compute_alpha_and_norm_ratios never reads the global error), 2 = global error sum only
 // (compute_reconstruction_error never reads the rows), 3 = both.  The epilogue's vector work runs on the lanes the fp32
 // MFMA uses, so what the caller does not need is not computed: 7 / 3 / 10 packed operations per pair of outputs.
@@ -477,15 +476,104 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // What the tiled kernel's TAIL needs (round 3: the final reduction is no launch of its own).  The workgroups of a row
 // block (one per column split) count themselves in at cnt[1 + row block] once their partial sums are written; the one
-// that arrives last re-centres the block's rows in f64 (the arithmetic of the former uvt_final_tiled_kernel) and writes
-// the block's share of the two global sums; row blocks count themselves in at cnt[0], and the last one adds the shares
-// in block order.  Every sum has a fixed order, whichever workgroup happens to form it: results do not depend on timing.
+// that arrives last re-centres the block's rows in f64 (finish_row below, as uvt_final_tiled_kernel does for long
+// passes) and writes the block's share of the two global sums; row blocks count themselves in at cnt[0], and the last
+// one adds the shares in block order.  Every sum has a fixed order, whichever workgroup happens to form it: results do
+// not depend on timing.
 // Partial sums travel between workgroups (possibly of different XCDs, whose L2s are not coherent with each other) as
 // agent-scope stores and loads: they go to the memory side themselves, so no release / acquire FENCE is needed — a fence
 // at agent scope writes back and invalidates the XCD's whole L2 on this chip, and one per finishing workgroup threw the
 // V rows the other workgroups were reading out of it (the pass took twice as long).
 __device__ __forceinline__ void st_agent(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double ld_agent(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// The tiled kernel's per-(split, row) sums are relative to the split's shift x0 (and to nothing for U V^T): they are
+// re-centred in f64.  Per split s with n_s columns and c' = x - x0_s:  sum x = S_c' + n_s x0;
+// sum x^2 = S_c'c' + 2 x0 S_c' + n_s x0^2;  with the fp32-rounded row mean xm the reference centres with
+// (structure.py:987) and t = xm - x0_s:  sum (x - xm)^2 = S_c'c' - 2 t S_c' + n_s t^2,  sum a (x - xm) = S_ac' - t S_a.
+// finish_row writes row_stats[r] from them and returns sum x^2.  The tail of the tiled kernel and uvt_final_tiled_kernel
+// both finish rows here, so a row's result does not depend on which of them did.  ONE pass over the splits, LOADS
+// splits' sums requested together (independent loads), added in split order: the sums above are polynomials in mu, so
+// their coefficients are accumulated first and mu (which needs sum x) is applied at the end, all in f64.
+// AGENT: the sums were written by other workgroups of the running kernel (the tail), so they are read at agent scope;
+// the final kernel reads them with plain loads (one 16-byte load per two doubles, not one atomic load per double).
+template <int LOADS, bool AGENT>
+__device__ __forceinline__ double finish_row(const double *part_rows, const float *rm, int n, int m, int splits,
+                                             int cols_per_split, int r, double *row_stats)
+{
+    double sx = 0.0, s_ac = 0.0, s_a = 0.0, s_ax0 = 0.0, aa = 0.0, s_cc = 0.0, s_c = 0.0, s_cx0 = 0.0, s_n = 0.0,
+           s_nx0 = 0.0, s_nx00 = 0.0;
+    for (int sp0 = 0; sp0 < splits; sp0 += LOADS) {
+        double tv[LOADS][kTiledRowSums];
+#pragma unroll
+        for (int x = 0; x < LOADS; ++x) {
+            const double *t = part_rows + ((size_t)min(sp0 + x, splits - 1) * n + r) * kTiledRowSums;
+#pragma unroll
+            for (int y = 0; y < kTiledRowSums; ++y) tv[x][y] = AGENT ? ld_agent(t + y) : t[y];
+        }
+#pragma unroll
+        for (int x = 0; x < LOADS; ++x) {
+            const int sp = sp0 + x;
+            if (sp < splits) {
+                const int c0 = sp * cols_per_split;
+                const double ns = (double)(min(m, c0 + cols_per_split) - c0);
+                const double t0 = tv[x][0], t1 = tv[x][1], t2 = tv[x][2], t3 = tv[x][3], t4 = tv[x][4], x0 = tv[x][5];
+                sx += t3 + ns * x0;
+                s_ac += t0; s_a += t2; s_ax0 += x0 * t2;
+                aa += t1;
+                s_cc += t4; s_c += t3; s_cx0 += x0 * t3;
+                s_n += ns; s_nx0 += ns * x0; s_nx00 += ns * x0 * x0;
+            }
+        }
+    }
+    const float xmean = (float)(sx / (double)m);
+    const double mu = (double)xmean;
+    const double ac = s_ac - mu * s_a + s_ax0;                                           // sum a (x - mu)
+    const double cc = s_cc - 2.0 * (mu * s_c - s_cx0) + (mu * mu * s_n - 2.0 * mu * s_nx0 + s_nx00);   // sum (x - mu)^2
+    const double qr = s_cc + 2.0 * s_cx0 + s_nx00;                                       // sum x^2
+    double *o = row_stats + (size_t)r * 8;
+    o[0] = ac; o[1] = aa; o[2] = fmax(0.0, cc); o[3] = (double)rm[r]; o[4] = mu;
+    o[5] = qr; o[6] = 0.0; o[7] = 0.0;
+    return qr;
+}
+
+// a and b summed over the workgroup's first nt threads (nt a power of two) in a fixed tree, through red[0, nt) and
+// red[stride, stride + nt): the sums land in red[0] and red[stride].  Every thread of the workgroup calls it.
+__device__ __forceinline__ void block_sum2(double *red, int stride, int nt, double a, double b)
+{
+    const int tid = threadIdx.x;
+    red[tid] = a;
+    red[stride + tid] = b;
+    __syncthreads();
+    for (int w = nt >> 1; w > 0; w >>= 1) {
+        if (tid < w) {
+            red[tid] += red[tid + w];
+            red[stride + tid] += red[stride + tid + w];
+        }
+        __syncthreads();
+    }
+}
+
+// the pass's two global sums: the squared error and sum x^2
+__device__ __forceinline__ void write_scal(double *scal, double err2, double xx, double s)
+{
+    scal[0] = err2;
+    scal[1] = s * s * xx;   // ||sX||_F^2  (structure.py:946)
+    scal[2] = 0.0;
+    scal[3] = 0.0;
+}
+
+// this workgroup's share (an even cut over the grid, nthr threads) of part_err[0, n_err), and of part_xx where given
+__device__ __forceinline__ void block_share(const double *part_err, const double *part_xx, int n_err, int nthr,
+                                            double &e, double &q)
+{
+    const int per = (n_err + gridDim.x - 1) / gridDim.x;
+    const int k1 = min(n_err, ((int)blockIdx.x + 1) * per);
+    for (int k = blockIdx.x * per + threadIdx.x; k < k1; k += nthr) {
+        e += part_err[k];
+        if (part_xx) q += part_xx[k];
+    }
+}
 
 struct UvtTail {
     double *row_stats;   // [n][8] (WHAT & 1)
@@ -495,15 +583,17 @@ struct UvtTail {
     double s;
 };
 
-template <int D, int NW, int TC, bool XV, int WPE = 2, bool PFX = (D <= 128), int WHAT = 3, bool SPLIT = false>
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE)))
+template <int D, bool XV, int WHAT, bool SPLIT>
+__global__ __launch_bounds__(tiled_shape(D).NW * 64) __attribute__((amdgpu_waves_per_eu(2)))
 void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, const float *__restrict__ X,
                       const float *__restrict__ rm, const float *__restrict__ cm, int n,
                       int m, float s, int cols_per_split, int splits, int row_blocks, double *part_rows,
                       double *part_err, double *part_xx, UvtTail tail)
 {
+    constexpr int NW = tiled_shape(D).NW, TC = tiled_shape(D).TC;
+    constexpr bool PFX = XV && (SPLIT || D <= 128);
     constexpr int CPR = D / 4, PIECES = TC * D / 256, PPW = PIECES / NW, CMW = (TC + 63) / 64, PF = SPLIT ? 256 : 260;
-    static_assert(!SPLIT || (D % 32 == 0 && D <= 256 && PFX && XV), "split-product form: d in {32, 64, 128, 256}, prefetch form");
+    static_assert(!SPLIT || (D % 32 == 0 && D <= 256 && XV), "split-product form: d in {32, 64, 128, 256}, 16-byte X");
     static_assert(PIECES % NW == 0 && TC % 32 == 0 && CMW <= NW, "stage must split evenly over the waves");
     __shared__ __attribute__((aligned(16))) float vts[2][PIECES * PF];   // [buffer][piece][256 + 4 pad]
     __shared__ __attribute__((aligned(16))) float cmss[2][CMW * 64];      // column means of U V^T, stage's columns
@@ -595,12 +685,6 @@ void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
 
-#if MFCD_UVT_STAMPS
-    unsigned long long cyc_chain = 0, cyc_epi = 0, cyc_sync = 0, cyc_dma = 0, n_tiles = 0;
-#endif
-#if MFCD_UVT_STAMPS
-    const unsigned long long clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
     int buf = 0;
     // X values of this lane's row for the tile at column cb: columns cb + 8g + 4*half + {0,1,2,3}, g = 0..3.
     // They are fetched ONE TILE AHEAD (round 1 issued them at the top of their own tile): an HBM round trip is ~2 us,
@@ -620,14 +704,12 @@ void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, 
             for (int r = 0; r < 16; ++r) xq[r >> 2][r & 3] = xrow0[min(cb + tile_row(r, half), m - 1)];
         }
     };
-    static_assert(!PFX || XV, "the prefetch form is built for 16-byte X pieces (four loads per request)");
     constexpr int kPend = 4;   // vector-memory operations one X prefetch puts in flight
     f32x4 xa[4], xb[4];
     if (PFX && active) load_x(c_begin, xa);
 
     auto tile = [&](int cb, int ncb, int j, const float *cms, f32x4 (&xq)[4], f32x4 (&xn)[4]) __attribute__((always_inline)) {
                 const bool full = cb + 32 <= c_end;   // wave-uniform
-                MFCD_STAMP(tt0);
                 asm volatile("" ::: "memory");   // the stage's LDS-DMA (issued above) stays OLDER than this prefetch
                 if constexpr (PFX) load_x(ncb, xn);   // the NEXT tile's values (a dummy re-read of this tile at the very end)
                 else load_x(cb, xq);                 // this tile's own values, in flight under its MFMA chain
@@ -709,7 +791,6 @@ void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, 
                     }
                 }
                 }
-                MFCD_STAMP(tt1);
                 // the X values become visible to the epilogue arithmetic only here: otherwise the scheduler moves
                 // x - xm, s*x up into the MFMA chain and with them the wait for the X loads (and, as an LDS-DMA is in
                 // flight, for everything: vmcnt(0)) to the top of the chain
@@ -781,13 +862,6 @@ void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, 
                 ssa += (double)psa;
                 ssc += (double)psc;
                 sscc += (double)pscc;
-#if MFCD_UVT_STAMPS
-                asm volatile("" : "+v"(sac), "+v"(saa), "+v"(err2));
-                MFCD_STAMP(tt2);
-                cyc_chain += tt1 - tt0;
-                cyc_epi += tt2 - tt1;
-                n_tiles += 1;
-#endif
     };
 
     if constexpr (PFX && TC == 32) {
@@ -811,12 +885,7 @@ void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, 
     } else {
     for (int c0 = c_begin; c0 < c_end; c0 += TC) {
         const float *cms = cmss[buf];
-        MFCD_STAMP(td0);
         if (c0 + TC < c_end) issue_stage(c0 + TC, vts[buf ^ 1], cmss[buf ^ 1]);
-        MFCD_STAMP(td1);
-#if MFCD_UVT_STAMPS
-        cyc_dma += td1 - td0;
-#endif
         if (active) {
             if constexpr (PFX) {
                 // tiles in PAIRS, straight-line: the first uses xa and requests the second's values into xb, the second
@@ -842,31 +911,14 @@ void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, 
                 }
             }
         }
-        MFCD_STAMP(ts0);
         // this wave's pieces of the next stage have landed: everything but the X prefetch of the stage's last tile,
         // which is younger than the DMA (vmcnt counts in issue order) and stays in flight across the barrier
         if (PFX && active) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPend) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                      // ... and everybody's; this buffer may be overwritten
-        MFCD_STAMP(ts1);
-#if MFCD_UVT_STAMPS
-        cyc_sync += ts1 - ts0;
-#endif
         buf ^= 1;
     }
     }
-#if MFCD_UVT_STAMPS
-    if (lane == 0 && active) {
-        atomicAdd(&mfcd_uvt_dbg[0], cyc_chain);
-        atomicAdd(&mfcd_uvt_dbg[1], cyc_epi);
-        atomicAdd(&mfcd_uvt_dbg[2], cyc_sync);
-        atomicAdd(&mfcd_uvt_dbg[3], cyc_dma);
-        atomicAdd(&mfcd_uvt_dbg[4], n_tiles);
-        atomicAdd(&mfcd_uvt_dbg[5], 1ull);
-        atomicAdd(&mfcd_uvt_dbg[6], (unsigned long long)__builtin_amdgcn_s_memtime() - clk0);
-        atomicAdd(&mfcd_uvt_dbg[7], (unsigned long long)__builtin_amdgcn_s_memrealtime() - rt0);
-    }
-#endif
     if (active) {
     // a row's columns are split over the two lane halves
     sac += __shfl_xor(sac, 32, MFCD_WAVE);
@@ -896,10 +948,6 @@ void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, 
     }
 
     // ---------------- tail: the last workgroup of a row block finishes its rows (see UvtTail) ----------------
-    // The tiled kernel's per-(split, row) sums are relative to the split's shift x0 (and to nothing for U V^T): they are
-    // re-centred in f64.  Per split s with n_s columns and c' = x - x0_s:  sum x = S_c' + n_s x0;
-    // sum x^2 = S_c'c' + 2 x0 S_c' + n_s x0^2;  with the fp32-rounded row mean xm the reference centres with
-    // (structure.py:987) and t = xm - x0_s:  sum (x - xm)^2 = S_c'c' - 2 t S_c' + n_s t^2,  sum a (x - xm) = S_ac' - t S_a
     if (tail.cnt == nullptr) return;       // large pass: uvt_final_tiled_kernel finishes (whole workgroup, wave-uniform)
     __shared__ int tail_last;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's partial sums have reached the memory side ...
@@ -914,44 +962,7 @@ void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, 
     double q = 0.0, e = 0.0;
     if constexpr ((WHAT & 1) != 0) {
         const int r = rb * NW * 32 + tid;
-        if (tid < NW * 32 && r < n) {
-            // ONE pass over the splits (independent loads): the sums above are polynomials in mu, so their coefficients
-            // are accumulated first and mu (which needs sum x) is applied at the end, all in f64
-            double sx = 0.0, s_ac = 0.0, s_a = 0.0, s_ax0 = 0.0, aa = 0.0, s_cc = 0.0, s_c = 0.0, s_cx0 = 0.0, s_n = 0.0,
-                   s_nx0 = 0.0, s_nx00 = 0.0;
-            for (int sp0 = 0; sp0 < splits; sp0 += 8) {    // eight splits' sums requested together, added in split order
-                double tv[8][kTiledRowSums];
-#pragma unroll
-                for (int x = 0; x < 8; ++x) {
-                    const double *t = part_rows + ((size_t)min(sp0 + x, splits - 1) * n + r) * kTiledRowSums;
-#pragma unroll
-                    for (int y = 0; y < kTiledRowSums; ++y) tv[x][y] = ld_agent(t + y);
-                }
-#pragma unroll
-                for (int x = 0; x < 8; ++x) {
-                    const int sp = sp0 + x;
-                    if (sp < splits) {
-                        const int c0 = sp * cols_per_split;
-                        const double ns = (double)(min(m, c0 + cols_per_split) - c0);
-                        const double t0 = tv[x][0], t1 = tv[x][1], t2 = tv[x][2], t3 = tv[x][3], t4 = tv[x][4], x0 = tv[x][5];
-                        sx += t3 + ns * x0;
-                        s_ac += t0; s_a += t2; s_ax0 += x0 * t2;
-                        aa += t1;
-                        s_cc += t4; s_c += t3; s_cx0 += x0 * t3;
-                        s_n += ns; s_nx0 += ns * x0; s_nx00 += ns * x0 * x0;
-                    }
-                }
-            }
-            const float xmean = (float)(sx / (double)m);
-            const double mu = (double)xmean;
-            const double ac = s_ac - mu * s_a + s_ax0;                                           // sum a (x - mu)
-            const double cc = s_cc - 2.0 * (mu * s_c - s_cx0) + (mu * mu * s_n - 2.0 * mu * s_nx0 + s_nx00);   // sum (x - mu)^2
-            const double qr = s_cc + 2.0 * s_cx0 + s_nx00;                                       // sum x^2
-            double *o = tail.row_stats + (size_t)r * 8;
-            o[0] = ac; o[1] = aa; o[2] = fmax(0.0, cc); o[3] = (double)rm[r]; o[4] = mu;
-            o[5] = qr; o[6] = 0.0; o[7] = 0.0;
-            q = qr;
-        }
+        if (tid < NW * 32 && r < n) q = finish_row<8, true>(part_rows, rm, n, m, splits, cols_per_split, r, tail.row_stats);
     }
     if constexpr ((WHAT & 2) != 0) {
         // the block's share of the two global sums: its waves' error sums (and, error-only pass, their sum x^2), split-major
@@ -962,16 +973,7 @@ void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, 
                 if constexpr (WHAT == 2) q += ld_agent(part_xx + (size_t)sp * rtiles + t);
             }
         }
-        tred[tid] = e;
-        tred[NW * 64 + tid] = q;
-        __syncthreads();
-        for (int w = NW * 32; w > 0; w >>= 1) {
-            if (tid < w) {
-                tred[tid] += tred[tid + w];
-                tred[NW * 64 + tid] += tred[NW * 64 + tid + w];
-            }
-            __syncthreads();
-        }
+        block_sum2(tred, NW * 64, NW * 64, e, q);
         if (tid == 0) {
             st_agent(tail.blk + 2 * rb + 0, tred[0]);
             st_agent(tail.blk + 2 * rb + 1, tred[NW * 64]);
@@ -986,23 +988,8 @@ void uvt_tiled_kernel(const float *__restrict__ U, const float *__restrict__ V, 
             e += ld_agent(tail.blk + 2 * k + 0);
             q += ld_agent(tail.blk + 2 * k + 1);
         }
-        __syncthreads();
-        tred[tid] = e;
-        tred[NW * 64 + tid] = q;
-        __syncthreads();
-        for (int w = NW * 32; w > 0; w >>= 1) {
-            if (tid < w) {
-                tred[tid] += tred[tid + w];
-                tred[NW * 64 + tid] += tred[NW * 64 + tid + w];
-            }
-            __syncthreads();
-        }
-        if (tid == 0) {
-            tail.scal[0] = tred[0];
-            tail.scal[1] = tail.s * tail.s * tred[NW * 64];   // ||sX||_F^2  (structure.py:946)
-            tail.scal[2] = 0.0;
-            tail.scal[3] = 0.0;
-        }
+        block_sum2(tred, NW * 64, NW * 64, e, q);
+        if (tid == 0) write_scal(tail.scal, tred[0], tred[NW * 64], tail.s);
     }
 }
 
@@ -1030,30 +1017,16 @@ __global__ __launch_bounds__(256) void uvt_final_kernel(const double *__restrict
         o[0] = ac; o[1] = aa; o[2] = scc[r]; o[3] = (double)rm[r]; o[4] = (double)xm[r];
         o[5] = q; o[6] = 0.0; o[7] = 0.0;
     }
-    const int per = (n_err + gridDim.x - 1) / gridDim.x;
-    const int k1 = min(n_err, ((int)blockIdx.x + 1) * per);
-    for (int k = blockIdx.x * per + threadIdx.x; k < k1; k += 256) e += part_err[k];
-    red[0][threadIdx.x] = e;
-    red[1][threadIdx.x] = q;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + w];
-            red[1][threadIdx.x] += red[1][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
+    block_share(part_err, nullptr, n_err, 256, e, q);
+    block_sum2(&red[0][0], 256, 256, e, q);
     if (threadIdx.x == 0) {
         blk[2 * blockIdx.x + 0] = red[0][0];
         blk[2 * blockIdx.x + 1] = red[1][0];
     }
 }
 
-// The tiled kernel's per-(split, row) sums are relative to the split's shift x0 (and to nothing for U V^T): this
-// kernel (LARGE passes; short ones finish in the tiled kernel's tail, same arithmetic) re-centres them in f64 and writes the same row_stats / block shares as uvt_final_kernel.  Per split s with
-// n_s columns and c' = x - x0_s:  sum x = S_c' + n_s x0;  sum x^2 = S_c'c' + 2 x0 S_c' + n_s x0^2;  with the fp32-rounded
-// row mean xm the reference centres with (structure.py:987) and t = xm - x0_s:
-//   sum (x - xm)^2 = S_c'c' - 2 t S_c' + n_s t^2        sum a (x - xm) = S_ac' - t S_a
+// LARGE passes (short ones finish in the tiled kernel's tail): row_stats from the tiled kernel's per-(split, row) sums
+// (finish_row) and the same block shares as uvt_final_kernel.
 // scal != nullptr: ONE workgroup does all rows and writes the two global sums itself (small n: saves a launch).
 __global__ __launch_bounds__(1024) void uvt_final_tiled_kernel(const double *__restrict__ part_rows,
                                                               const double *__restrict__ part_err,
@@ -1066,54 +1039,13 @@ __global__ __launch_bounds__(1024) void uvt_final_tiled_kernel(const double *__r
     __shared__ double red[2][1024];
     const int nthr = blockDim.x;   // 256 (one workgroup per 256 rows) or 1024 (single-workgroup form)
     double q = 0.0, e = 0.0;
-    for (int r = blockIdx.x * nthr + threadIdx.x; (what & 1) && r < n; r += gridDim.x * nthr) {
-        // ONE pass over the splits (independent loads): the sums above are polynomials in mu, so their coefficients are
-        // accumulated first and mu (which needs sum x) is applied at the end, all in f64
-        double sx = 0.0, s_ac = 0.0, s_a = 0.0, s_ax0 = 0.0, aa = 0.0, s_cc = 0.0, s_c = 0.0, s_cx0 = 0.0, s_n = 0.0,
-               s_nx0 = 0.0, s_nx00 = 0.0;
-        for (int sp = 0; sp < splits; ++sp) {
-            const double *t = part_rows + ((size_t)sp * n + r) * kTiledRowSums;
-            const int c0 = sp * cols_per_split;
-            const double ns = (double)(min(m, c0 + cols_per_split) - c0);
-            const double t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], t4 = t[4], x0 = t[5];
-            sx += t3 + ns * x0;
-            s_ac += t0; s_a += t2; s_ax0 += x0 * t2;
-            aa += t1;
-            s_cc += t4; s_c += t3; s_cx0 += x0 * t3;
-            s_n += ns; s_nx0 += ns * x0; s_nx00 += ns * x0 * x0;
-        }
-        const float xmean = (float)(sx / (double)m);
-        const double mu = (double)xmean;
-        const double ac = s_ac - mu * s_a + s_ax0;                                           // sum a (x - mu)
-        const double cc = s_cc - 2.0 * (mu * s_c - s_cx0) + (mu * mu * s_n - 2.0 * mu * s_nx0 + s_nx00);   // sum (x - mu)^2
-        const double qr = s_cc + 2.0 * s_cx0 + s_nx00;                                       // sum x^2
-        double *o = row_stats + (size_t)r * 8;
-        o[0] = ac; o[1] = aa; o[2] = fmax(0.0, cc); o[3] = (double)rm[r]; o[4] = mu;
-        o[5] = qr; o[6] = 0.0; o[7] = 0.0;
-        q += qr;
-    }
-    const int per = (n_err + gridDim.x - 1) / gridDim.x;
-    const int k1 = min(n_err, ((int)blockIdx.x + 1) * per);
-    for (int k = blockIdx.x * per + threadIdx.x; (what & 2) && k < k1; k += nthr) {
-        e += part_err[k];
-        if (!(what & 1)) q += part_xx[k];
-    }
-    red[0][threadIdx.x] = e;
-    red[1][threadIdx.x] = q;
-    __syncthreads();
-    for (int w = nthr >> 1; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + w];
-            red[1][threadIdx.x] += red[1][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
+    for (int r = blockIdx.x * nthr + threadIdx.x; (what & 1) && r < n; r += gridDim.x * nthr)
+        q += finish_row<1, false>(part_rows, rm, n, m, splits, cols_per_split, r, row_stats);
+    if (what & 2) block_share(part_err, (what & 1) ? nullptr : part_xx, n_err, nthr, e, q);
+    block_sum2(&red[0][0], 1024, nthr, e, q);
     if (threadIdx.x == 0) {
         if (scal) {
-            scal[0] = red[0][0];
-            scal[1] = s * s * red[1][0];  // ||sX||_F^2  (structure.py:946)
-            scal[2] = 0.0;
-            scal[3] = 0.0;
+            write_scal(scal, red[0][0], red[1][0], s);
         } else {
             blk[2 * blockIdx.x + 0] = red[0][0];
             blk[2 * blockIdx.x + 1] = red[1][0];
@@ -1131,22 +1063,8 @@ __global__ __launch_bounds__(256) void uvt_scal_kernel(const double *__restrict_
         e += blk[2 * k + 0];
         q += blk[2 * k + 1];
     }
-    red[0][threadIdx.x] = e;
-    red[1][threadIdx.x] = q;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + w];
-            red[1][threadIdx.x] += red[1][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        scal[0] = red[0][0];
-        scal[1] = s * s * red[1][0];  // ||sX||_F^2  (structure.py:946)
-        scal[2] = 0.0;
-        scal[3] = 0.0;
-    }
+    block_sum2(&red[0][0], 256, 256, e, q);
+    if (threadIdx.x == 0) write_scal(scal, red[0][0], red[1][0], s);
 }
 
 // k rows of UV^T (structure.py:389-392): one wave per (row, 64-column chunk)
@@ -1183,21 +1101,6 @@ struct UvtWs {
     size_t bytes;
 };
 
-struct TiledCfg {
-    int NW, TC;   // waves per workgroup (32 rows each), columns per LDS stage; NW == 0: no tiled form for this d
-};
-
-TiledCfg tiled_cfg(int d)
-{
-    switch (d) {
-    case 256: return {4, 32};    // 64 KiB of stages: two workgroups (two waves per SIMD) per CU
-    case 128: return {4, 64};    // two tiles per stage: the X prefetch alternates between two register sets
-    case 64: return {4, 64};
-    case 32: return {4, 128};
-    default: return {0, 0};
-    }
-}
-
 int g_uvt_split = 1;           // mfcd_set_tuning(MFCD_TUNE_UVT_SPLIT): 1 = bf16x3 split-product main kernel where it applies
 bool split_form_applies(int d) { return g_uvt_split != 0 && (d == 32 || d == 64 || d == 128 || d == 256); }
 
@@ -1210,7 +1113,7 @@ UvtWs plan_ws(char *base, int n, int m, int d)
 {
     UvtWs w;
     const int rtiles = (n + 31) / 32;
-    const TiledCfg tc = n >= 32 && (int64_t)m * d < (int64_t)0x7fff0000 ? tiled_cfg(d) : TiledCfg{0, 0};
+    const TiledShape tc = n >= 32 && (int64_t)m * d < (int64_t)0x7fff0000 ? tiled_shape(d) : TiledShape{0, 0};
     if (tc.NW) {
         // tiled form: several rounds of workgroups over the chip (the hardware balances them), a split's V rows
         // small enough for one XCD's L2 (4 MiB), >= 2 stages per split; 8 or more splits (a multiple of 8 where the
@@ -1272,38 +1175,32 @@ UvtWs plan_ws(char *base, int n, int m, int d)
     return w;
 }
 
-template <int DD, int NW, int TC, bool PFX, int WHAT>
-void launch_tiled_what(const UvtWs &w, const float *U, const float *V, const float *X, int n, int m, float s, bool xv,
-                       const UvtTail &tail, hipStream_t st)
+using TiledKernel = decltype(&uvt_tiled_kernel<32, true, 3, true>);
+
+// the 12 instances of one width: [split product, fp32 with 16-byte X, fp32 with scalar X][what - 1]
+template <int D>
+TiledKernel tiled_kernel(bool split, bool xv, int what)
 {
-    const int row_blocks = (n + NW * 32 - 1) / (NW * 32);
-    const unsigned blocks = (unsigned)row_blocks * (w.splits >= 8 ? 8u * ((w.splits + 7) / 8) : (unsigned)w.splits);
-    {
-        if (xv && w.vsplit) {   // bf16x3 split product: V comes from the split table centre_vectors_kernel wrote
-            hipLaunchKernelGGL((uvt_tiled_kernel<DD, NW, TC, true, 2, true, WHAT, true>), dim3(blocks), dim3(NW * 64), 0, st, U,
-                               (const float *)w.vsplit, X, w.rm, w.cm, n, m, s, w.cols_per_split, w.splits, row_blocks,
-                               w.part_rows, w.part_err, w.part_xx, tail);
-            return;
-        }
-    }
-    if (xv)
-        hipLaunchKernelGGL((uvt_tiled_kernel<DD, NW, TC, true, 2, PFX, WHAT>), dim3(blocks), dim3(NW * 64), 0, st, U, V,
-                           X, w.rm, w.cm, n, m, s, w.cols_per_split, w.splits, row_blocks, w.part_rows, w.part_err,
-                           w.part_xx, tail);
-    else
-        hipLaunchKernelGGL((uvt_tiled_kernel<DD, NW, TC, false, 2, false, WHAT>), dim3(blocks), dim3(NW * 64), 0, st, U,
-                           V, X, w.rm, w.cm, n, m, s, w.cols_per_split, w.splits, row_blocks, w.part_rows, w.part_err,
-                           w.part_xx, tail);
+    const TiledKernel k[3][3] = {
+        {uvt_tiled_kernel<D, true, 1, true>, uvt_tiled_kernel<D, true, 2, true>, uvt_tiled_kernel<D, true, 3, true>},
+        {uvt_tiled_kernel<D, true, 1, false>, uvt_tiled_kernel<D, true, 2, false>, uvt_tiled_kernel<D, true, 3, false>},
+        {uvt_tiled_kernel<D, false, 1, false>, uvt_tiled_kernel<D, false, 2, false>, uvt_tiled_kernel<D, false, 3, false>}};
+    return k[split ? 0 : xv ? 1 : 2][what - 1];
 }
 
-template <int DD, int NW, int TC, bool PFX = (DD <= 128)>
-int launch_tiled(const UvtWs &w, const float *U, const float *V, const float *X, int n, int m, float s, bool xv,
-                 int what, const UvtTail &tail, hipStream_t st)
+// the tiled main kernel for d in {32, 64, 128, 256}; the bf16x3 split product wherever the plan made its table
+void launch_tiled(const UvtWs &w, const float *U, const float *V, const float *X, int n, int m, int d, float s, bool xv,
+                  int what, const UvtTail &tail, hipStream_t st)
 {
-    if (what == 1) launch_tiled_what<DD, NW, TC, PFX, 1>(w, U, V, X, n, m, s, xv, tail, st);
-    else if (what == 2) launch_tiled_what<DD, NW, TC, PFX, 2>(w, U, V, X, n, m, s, xv, tail, st);
-    else launch_tiled_what<DD, NW, TC, PFX, 3>(w, U, V, X, n, m, s, xv, tail, st);
-    return 0;
+    const bool split = xv && w.vsplit;   // V then comes from the split table centre_vectors_kernel wrote
+    const TiledKernel k = d == 256 ? tiled_kernel<256>(split, xv, what)
+                        : d == 128 ? tiled_kernel<128>(split, xv, what)
+                        : d == 64 ? tiled_kernel<64>(split, xv, what)
+                        : tiled_kernel<32>(split, xv, what);
+    const int NW = tiled_shape(d).NW, row_blocks = (n + NW * 32 - 1) / (NW * 32);
+    const unsigned blocks = (unsigned)row_blocks * (w.splits >= 8 ? 8u * ((w.splits + 7) / 8) : (unsigned)w.splits);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(NW * 64), 0, st, U, split ? (const float *)w.vsplit : V, X, w.rm, w.cm, n, m,
+                       s, w.cols_per_split, w.splits, row_blocks, w.part_rows, w.part_err, w.part_xx, tail);
 }
 
 }  // namespace
@@ -1345,12 +1242,23 @@ extern "C" size_t mfcd_uvt_slab_workspace_bytes(int n, int m, int d, int nrows)
 
 namespace {
 
+// argument checks of the two pass entries (the slab entry checks its row range on top)
+bool uvt_args_ok(const float *U, const float *V, const float *X, int n, int m, int d, int what, const double *row_stats,
+                 const double *scal, const void *workspace)
+{
+    return U && V && X && workspace && n > 0 && m > 0 && d > 0 && d <= MFCD_MAX_D && what >= 1 && what <= 3 &&
+           (!(what & 1) || row_stats) && (!(what & 2) || scal);
+}
+
 // The pass over rows [row0, row0 + nrows) of U against the slab Xs [nrows][m]; the centring vectors come from ALL n rows
 // of U (wf: the plan for n rows holds rm, cm; ws: the plan for nrows rows holds the slab's partial sums; the two are the
-// same plan when the slab is the whole matrix).
+// same plan when the slab is the whole matrix).  What the caller did not ask for goes to ws's scratch (generic form)
+// or is not written at all (tiled form).
 int run_uvt(const float *U, const float *V, const float *Xs, int n, int m, int d, double s, int what, int row0,
             int nrows, double *row_stats, double *scal, const UvtWs &wf, const UvtWs &ws, hipStream_t st)
 {
+    if (!(what & 1)) row_stats = ws.dummy_rows;
+    if (!(what & 2)) scal = ws.dummy_scal;
     const bool xv = (reinterpret_cast<uintptr_t>(Xs) & 15u) == 0 && m % 4 == 0;
     const bool al16 = ((reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(V)) & 15u) == 0;
     // fused form: X read ONCE, 3 launches (round 1: 8 launches, X read twice; round 2: 4-5); tables off a 16-byte boundary take the
@@ -1382,12 +1290,7 @@ int run_uvt(const float *U, const float *V, const float *Xs, int n, int m, int d
         // of a workgroup's ~150) and the finishing workgroups at the very end cost C3 2.5 % and C5 4 %.
         const bool fold = (int64_t)nn * m <= ((int64_t)1 << 26);
         const UvtTail tail{row_stats, w.blk, scal, fold ? w.cnt : nullptr, s};
-        int rc = 0;
-        if (d == 256) rc = launch_tiled<256, 4, 32>(w, Us, V, Xs, nn, m, (float)s, xv, what, tail, st);
-        else if (d == 128) rc = launch_tiled<128, 4, 64>(w, Us, V, Xs, nn, m, (float)s, xv, what, tail, st);
-        else if (d == 64) rc = launch_tiled<64, 4, 64>(w, Us, V, Xs, nn, m, (float)s, xv, what, tail, st);
-        else rc = launch_tiled<32, 4, 128>(w, Us, V, Xs, nn, m, (float)s, xv, what, tail, st);
-        if (rc) return rc;
+        launch_tiled(w, Us, V, Xs, nn, m, d, (float)s, xv, what, tail, st);
         if (fold) {
             MFCD_HIP_TRY(hipGetLastError());
             return 0;
@@ -1432,13 +1335,9 @@ extern "C" int mfcd_uvt_stats_select(const float *U, const float *V, const float
                                      int what, double *row_stats, double *scal, void *workspace, size_t workspace_bytes,
                                      void *stream)
 {
-    if (!U || !V || !X || !workspace || n <= 0 || m <= 0 || d <= 0 || d > MFCD_MAX_D || what < 1 || what > 3)
-        return MFCD_EINVAL;
-    if (((what & 1) && !row_stats) || ((what & 2) && !scal)) return MFCD_EINVAL;
+    if (!uvt_args_ok(U, V, X, n, m, d, what, row_stats, scal, workspace)) return MFCD_EINVAL;
     const UvtWs w = plan_ws((char *)workspace, n, m, d);
     if (workspace_bytes < w.bytes) return MFCD_EWORKSPACE;
-    if (!(what & 1)) row_stats = w.dummy_rows;   // not asked for: written to scratch (generic form) or not at all (tiled)
-    if (!(what & 2)) scal = w.dummy_scal;
     return run_uvt(U, V, X, n, m, d, s, what, 0, n, row_stats, scal, w, w, (hipStream_t)stream);
 }
 
@@ -1452,29 +1351,14 @@ extern "C" int mfcd_uvt_stats_slab(const float *U, const float *V, const float *
                                    int what, int row0, int nrows, double *row_stats_slab, double *scal_slab,
                                    void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!U || !V || !X_slab || !workspace || n <= 0 || m <= 0 || d <= 0 || d > MFCD_MAX_D || what < 1 || what > 3)
+    if (!uvt_args_ok(U, V, X_slab, n, m, d, what, row_stats_slab, scal_slab, workspace) || row0 < 0 || nrows <= 0 ||
+        (int64_t)row0 + nrows > n)
         return MFCD_EINVAL;
-    if (row0 < 0 || nrows <= 0 || (int64_t)row0 + nrows > n) return MFCD_EINVAL;
-    if (((what & 1) && !row_stats_slab) || ((what & 2) && !scal_slab)) return MFCD_EINVAL;
     const UvtWs wf = plan_ws((char *)workspace, n, m, d);
     const UvtWs ws = plan_ws((char *)workspace + wf.bytes, nrows, m, d);
     if (workspace_bytes < wf.bytes + ws.bytes) return MFCD_EWORKSPACE;
-    if (!(what & 1)) row_stats_slab = ws.dummy_rows;
-    if (!(what & 2)) scal_slab = ws.dummy_scal;
     return run_uvt(U, V, X_slab, n, m, d, s, what, row0, nrows, row_stats_slab, scal_slab, wf, ws, (hipStream_t)stream);
 }
-
-#if MFCD_UVT_STAMPS
-// diagnostic build only: read and clear the in-kernel cycle accounting (not declared in include/mfcd.h)
-extern "C" int mfcd_uvt_debug_read(unsigned long long *out8_host)
-{
-    MFCD_HIP_TRY(hipDeviceSynchronize());
-    MFCD_HIP_TRY(hipMemcpyFromSymbol(out8_host, HIP_SYMBOL(mfcd_uvt_dbg), 8 * sizeof(unsigned long long)));
-    unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    MFCD_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(mfcd_uvt_dbg), zero, sizeof(zero)));
-    return 0;
-}
-#endif
 
 extern "C" int mfcd_uvt_rows(const float *U, const float *V, const int32_t *row_ids, int k, int n, int m, int d,
                              float *out, void *stream)

@@ -813,6 +813,12 @@ def test_uvt_stats_at_baseline_full_sizes(dev, orc, name, n, m, d):
         del G, Xb
     assert float(sc[0]) == pytest.approx(float(err2), rel=2e-5)
     assert float(sc[1]) == pytest.approx(float(ref2), rel=2e-5)
+    # the rows-only and error-only passes at these sizes finish in the separate final kernels (no fold into the tail)
+    rs1, _ = metrics.uvt_stats(U, V, X, s, what=1)
+    _, sc2 = metrics.uvt_stats(U, V, X, s, what=2)
+    assert torch.equal(rs1, rs)
+    assert float(sc2[0]) == pytest.approx(float(sc[0]), rel=1e-12)
+    assert float(sc2[1]) == pytest.approx(float(sc[1]), rel=1e-6)
 
 
 def _sampled_stream(strategy, n, m, d, want, seed, steps, B=64):
