@@ -588,6 +588,34 @@ int mfcd_train_big_status(const void *workspace, int *status_out, void *stream);
 int mfcd_train_big_slots(void);
 int mfcd_train_big_check(const mfcd_sample *samples, int64_t N, int B, int n, int m, int *max_out_dev, void *stream);
 
+/*
+ * The k best and / or k worst columns of requested rows of a score matrix, without forming the matrix (no reference
+ * counterpart as one function: the samplers call torch.topk(row, k) per attempt, generation_data.py:36-37, 212-213;
+ * the recommendation extensions of structure.py need the same lists of U V^T).  Scores are either dense,
+ * X [n][ldx] fp32, or (X == NULL) the fp32 products A[r] . B[c] of factors A [n][d], B [m][d], 1 <= d <= MFCD_MAX_D,
+ * formed on the exact fp32 MFMA, once per (row, column): selection and the returned values see the same number.
+ *   row_ids    `rows` row numbers (device), any order, repeats allowed; NULL = rows 0 .. rows-1.  A number outside
+ *              [0, n) yields an empty result (index -1, value NaN) for that row.
+ *   ends       1 best, 2 worst, 3 both (the scores are formed once).
+ *   best_*     [rows][k]: the k largest scores of the row in descending order; worst_* the k smallest in ascending
+ *              order.  Equal scores are ordered by ascending column; -0.0 equals +0.0.  NaN ranks above +inf for
+ *              `best` (torch.topk's convention) and after every number for `worst`.  *_val (nullable) is the score
+ *              that was compared.  Deterministic: two calls are bit-equal.
+ *   excl_off, excl_items   optional CSR (device): columns excl_items[excl_off[r] .. excl_off[r + 1]) (ascending) are
+ *              absent for requested row r, for both ends.  If fewer than k columns remain, the tail is -1 / NaN.
+ * Limits: 1 <= k <= min(m, mfcd_topk_max_k()) (8192), m <= 4 194 304, any `rows` (the entry loops over slabs of rows).
+ * MFCD_EINVAL outside them, with nothing launched.
+ * workspace: mfcd_topk_rows_workspace_bytes(rows, m, d, k, ends) bytes, 256-byte aligned (d = 0 for the dense mode,
+ * which needs none: 256 is returned; 0 = sizes out of range).  Factor mode: one slab of whole score rows of at most
+ * 128 MiB (at least 128 rows); nothing of size n x m exists.  No allocation and no host wait.
+ */
+int mfcd_topk_max_k(void);
+size_t mfcd_topk_rows_workspace_bytes(int rows, int m, int d, int k, int ends);
+int mfcd_topk_rows(const float *X, int64_t ldx, const float *A, const float *B, int d, const int32_t *row_ids,
+                   int rows, int n, int m, int k, int ends, const int64_t *excl_off, const int32_t *excl_items,
+                   int32_t *best_idx, float *best_val, int32_t *worst_idx, float *worst_val, void *workspace,
+                   size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,11 @@ def _advance_generators(t_state, n_state, torch_words, n, numpy_words):
 def _user_item_tables(X, users, kk, worst):
     """Rows of torch.topk indices (the reference's per-user lists) for the distinct users of a block."""
     uu, inv = np.unique(users, return_inverse=True)
+    if isinstance(X, FactoredMatrix):   # no dense rows: the lists come from the factors on the GPU (mfcd_topk_rows)
+        from mfcd import topk as _topk
+        got = _topk.topk_rows(X, kk, rows=uu, ends="both" if worst else "best")
+        best, low = got if worst else (got, None)
+        return inv, best.cpu().numpy(), low.cpu().numpy() if worst else None
     rows = X[torch.from_numpy(uu).to(X.device)]
     best = torch.topk(rows, k=kk, dim=1)[1].cpu().numpy()
     low = torch.topk(-rows, k=kk, dim=1)[1].cpu().numpy() if worst else None
@@ -176,7 +181,7 @@ def choose_items_by_proximity(X, num_triplets, exclude, k=100):
     n, m = X.shape
     kk = min(k, m)
     exclude = exclude or set()
-    if kk < 2 or n >= 2 ** 32 or num_triplets <= 0 or not torch.is_tensor(X):
+    if kk < 2 or n >= 2 ** 32 or num_triplets <= 0 or not (torch.is_tensor(X) or isinstance(X, FactoredMatrix)):
         return _choose_items_by_proximity_serial(X, num_triplets, exclude, k)
     barred = _barred_keys(exclude, m)
     t_state, n_state = torch.get_rng_state(), np.random.get_state()
@@ -501,7 +506,7 @@ def choose_items_top_k(X, num_triplets, exclude, k=None):
     exclude = exclude or set()
     if k is None:
         k = min(m, max(5, int(0.1 * m)))
-    if k < 2 or n >= 2 ** 32 or num_triplets <= 0 or not torch.is_tensor(X):
+    if k < 2 or n >= 2 ** 32 or num_triplets <= 0 or not (torch.is_tensor(X) or isinstance(X, FactoredMatrix)):
         return _choose_items_top_k_serial(X, num_triplets, exclude, k)
     barred = _barred_keys(exclude, m)
     t_state, n_state = torch.get_rng_state(), np.random.get_state()

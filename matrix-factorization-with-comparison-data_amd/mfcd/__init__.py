@@ -4,7 +4,8 @@
 `batching` DataLoader -> packed records + per-epoch order, RNG-stream compatible with the reference.
 `engine`   fused training epochs / evaluation on the device, in place on the caller's model + Adam.
 `metrics`  dense UV^T reconstruction / alignment metrics from the MFMA pass.
+`topk`     the k best / worst columns of rows of a dense or factored score matrix (mfcd_topk_rows).
 """
-from . import _lib, batching, engine, metrics  # noqa: F401
+from . import _lib, batching, engine, metrics, topk  # noqa: F401
 
-__all__ = ["_lib", "batching", "engine", "metrics"]
+__all__ = ["_lib", "batching", "engine", "metrics", "topk"]

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import topk as _topk
 
 LAW_UNIFORM, LAW_ITEM_CDF, LAW_LISTS = 0, 1, 2
 DEVICE_STRATEGIES = ("random", "margin", "popularity", "variance", "proximity", "top_k", "svd")
@@ -79,15 +80,23 @@ def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha
         c.cdf = law.hold(torch.from_numpy(cdf).to(device))
         return law
     if strategy in ("proximity", "top_k"):
-        Xd = _dense_on(X, device)
+        # a factored X never becomes dense: its lists come from mfcd_topk_rows over the factors (one call, all n rows)
+        fac = (X.A.to(device).contiguous(), X.B.to(device).contiguous()) if _is_factored(X) else None
+        Xd = None if fac else _dense_on(X, device)
         if strategy == "proximity":                                     # generation_data.py:36-37
             kk = min(100 if k is None else int(k), m)
-            best = torch.topk(Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
-            worst = torch.topk(-Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
+            if fac:
+                best, worst = _topk.topk_rows(fac, kk, ends="both")
+            else:
+                best = torch.topk(Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
+                worst = torch.topk(-Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
             c.list_i, c.list_j, c.pair_rule = law.hold(best), law.hold(worst), 0
         else:                                                            # generation_data.py:198-213
             kk = min(m, max(5, int(0.1 * m))) if k is None else int(k)
-            best = torch.topk(Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
+            if fac:
+                best = _topk.topk_rows(fac, kk, ends="best")
+            else:
+                best = torch.topk(Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
             c.list_i = c.list_j = law.hold(best)
             c.pair_rule = 1
             law.budget = 3 * int(num_triplets)

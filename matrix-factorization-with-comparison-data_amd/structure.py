@@ -23,6 +23,7 @@ import generation_data as _gd
 from mfcd import engine as _engine
 from mfcd import metrics as _metrics
 from mfcd import sampling as _sampling
+from mfcd import topk as _topk
 
 if torch.get_num_threads() > 16:  # imported after torch: keep the host-side pool small (GPU boxes expose 100s of cores)
     torch.set_num_threads(4)
@@ -116,6 +117,35 @@ def compute_reconstruction_error(model, X, s):
 def compute_alpha_and_norm_ratios(model, X_init):
     """ref:958-1082 → the 14-tuple in the reference's order."""
     return _metrics.alpha_and_norm_ratios(model.U.data, model.V.data, X_init)
+
+
+def recommend_items(model, users=None, k=10, exclude=None):
+    """Extension (not in the reference): the k items the model ranks highest for each of `users` (None: every user), best
+    first → int32 [len(users), k] tensor on the model's device (include/mfcd.h mfcd_topk_rows over U, V: the rows of
+    U V^T are never formed).  Equal scores are ordered by item number.  `exclude`: a set / array / tensor of (u, i) or
+    (u, i, j) rows — what u has been shown; a triplet bars both of its items for its user — which are left out; a user
+    with fewer than k items left gets -1 in the tail."""
+    _need_gpu(model.U.device)
+    return _topk.topk_rows((model.U.data, model.V.data), k, rows=users, ends="best", exclude=exclude)
+
+
+def compute_topk_overlap(model, X, k=10):
+    """Extension (not in the reference): how much of X's top-k per user the model's top-k recovers →
+    (mean over users, per-user float64 numpy array) of |top-k(U V^T row) ∩ top-k(X row)| / k.  X: a dense GPU tensor or a
+    `FactoredMatrix` (nothing n x m is formed for either side).  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    dev = model.U.device
+    mine = _topk.topk_rows((model.U.data, model.V.data), k, ends="best").long()
+    if torch.is_tensor(X):
+        X = X.to(dev)
+    theirs = _topk.topk_rows(X, k, ends="best", device=dev).long()
+    if mine.shape != theirs.shape:
+        raise ValueError(f"X must be [{model.U.shape[0]},{model.V.shape[0]}], got {tuple(X.shape)}")
+    m = model.V.shape[0]
+    row = torch.arange(mine.shape[0], device=dev).unsqueeze(1) * m
+    hit = torch.isin((mine + row).reshape(-1), (theirs + row).reshape(-1)).reshape(mine.shape)
+    per_user = (hit.sum(1).double() / k).cpu().numpy()
+    return float(per_user.mean()), per_user
 
 
 def compute_ground_truth_metrics(test_loader, X, device):
@@ -274,7 +304,9 @@ def set_sampler_device(device):
     """Extension (not in the reference): draw triplets ON `device` (a GPU; include/mfcd.h mfcd_sample_triplets) from now
     on for the strategies that have a device law (random, margin, popularity, variance, proximity, top_k, svd); the
     others (cluster, user_similarity — "Not used" in the reference's own comments) and None (default) use the host
-    samplers, which consume torch's / numpy's generators exactly like the reference."""
+    samplers, which consume torch's / numpy's generators exactly like the reference.  A `FactoredMatrix` ground truth
+    is taken by random, margin, popularity, proximity and top_k (the last two read their per-user lists from
+    mfcd_topk_rows over the factors; a dense X keeps torch.topk and its tie order)."""
     global _SAMPLER_DEVICE
     if device is not None:
         _need_gpu(device)
