@@ -20,6 +20,97 @@ def _accept(t, i, j, exclude, found):
     return i != j and t not in exclude and t not in found
 
 
+class _Kept:
+    """The rejection bookkeeping of the bulk samplers: the first `want` distinct, allowed triplets in attempt order.
+    Triplets are compared through their keys (u*m + i)*m + j; `need` is how many are still missing."""
+
+    def __init__(self, m, want, exclude):
+        self.m, self.need = int(m), int(want)
+        self.rows, self.keys = [], np.empty(0, dtype=np.int64)
+        self.barred = np.sort(np.fromiter(((u * m + i) * m + j for u, i, j in exclude), dtype=np.int64,
+                                          count=len(exclude))) if exclude else None
+
+    def take(self, us, ii, jj, ok):
+        """Keeps, of a block of attempts (int64 arrays; `ok`: the strategy allows the attempt), those that add a
+        triplet — allowed, not barred, not kept before, first of their key — up to `need`, and returns how many attempts
+        of the block the one-at-a-time loop would have used: up to the one that completes the request, or all."""
+        at = np.flatnonzero(ok)                                                   # keys only where the strategy allows
+        key = (us[at] * self.m + ii[at]) * self.m + jj[at]
+        new = np.ones(at.size, dtype=bool)
+        if self.barred is not None:
+            new &= ~np.isin(key, self.barred)
+        if self.keys.size:
+            new &= ~np.isin(key, self.keys)
+        at, key = at[new], key[new]
+        _, first = np.unique(key, return_index=True)                              # first attempt of every new triplet
+        first = np.sort(first)[:self.need]
+        at, key = at[first], key[first]
+        self.rows.append(np.stack((us[at], ii[at], jj[at]), axis=1))
+        self.keys = np.concatenate((self.keys, key))
+        self.need -= at.size
+        return int(at[-1]) + 1 if self.need == 0 else us.size
+
+    def triplets(self):
+        """list(set) of the kept triplets inserted in attempt order: the order the reference's `list(triplets)` has
+        (the 80/10/10 split indexes into it, ref:705-718)."""
+        got = np.concatenate(self.rows) if self.rows else np.empty((0, 3), dtype=np.int64)
+        return list(set(zip(got[:, 0].tolist(), got[:, 1].tolist(), got[:, 2].tolist())))
+
+
+def _advance_generators(t_state, n_state, torch_words, n, numpy_words):
+    """Put torch's CPU generator `torch_words` draws of randint(0, n) and numpy's global generator `numpy_words` 32-bit
+    words (a uniform double is two) past the given states: where a one-attempt-at-a-time loop that used that many would
+    have left them.  `n_state` None: numpy's generator was not used."""
+    torch.set_rng_state(t_state)
+    if torch_words:
+        torch.randint(0, n, (torch_words,))
+    if n_state is not None:
+        np.random.set_state(n_state)
+        if numpy_words:
+            np.random.randint(0, 2 ** 32, size=numpy_words, dtype=np.uint32)
+
+
+# Each strategy's set-up (what the reference computes in front of its attempt loop) and its message for a short
+# result, shared by the bulk form, the one-at-a-time loop and the device path (mfcd/sampling.py).
+def _margin_threshold(X, num_triplets):
+    """Mean range of the first ten rows times the sampling density (ref:56-57)."""
+    n, m = X.shape
+    head = X.rows(0, min(10, n)) if isinstance(X, FactoredMatrix) else X[:min(10, n)].detach().cpu().numpy()
+    return np.mean(head.max(axis=1) - head.min(axis=1)) * num_triplets / (n * m)
+
+
+def _proximity_k(m, k=None):
+    return min(100 if k is None else k, m)
+
+
+def _top_k_k(m, k=None):
+    return min(m, max(5, int(0.1 * m))) if k is None else k
+
+
+def _svd_top_sets(X, num_triplets, top_fraction=0.3):
+    """Users and items with the largest truncated-SVD projection norms, the rank set by the sampling density
+    (ref:144-162) → (top_users, top_items), ascending by norm."""
+    import scipy.sparse.linalg as spla
+    n, m = X.shape
+    rank = int(num_triplets / (n * m) * max(n, m))
+    Us, S, Vt = spla.svds(X.detach().cpu().numpy(), k=rank)
+    top_users = np.argsort(np.linalg.norm(Us * S, axis=1))[-max(1, int(top_fraction * n)):]
+    top_items = np.argsort(np.linalg.norm(Vt.T * S, axis=1))[-max(2, int(top_fraction * m)):]
+    return top_users, top_items
+
+
+def _report_short(got, num_triplets, detail="", after=""):
+    """The reference's message for a request its attempt budget did not fill: printed, not raised."""
+    if got < num_triplets:
+        print(f"⚠️ Only {got} triplets generated (target={num_triplets}{detail}){after}")
+
+
+def _report_short_margin(X, got, num_triplets, margin, attempts):
+    if got < num_triplets:
+        top = float((X.A if isinstance(X, FactoredMatrix) else X).max())
+        _report_short(got, num_triplets, f", margin={margin:.4f}", f" after {attempts} attempts.maximum : {top}")
+
+
 def _choose_items_random_serial(n, m, num_triplets, exclude):
     found = set()
     while len(found) < num_triplets:
@@ -48,43 +139,20 @@ def choose_items_random(X, num_triplets, exclude):
         return _choose_items_random_serial(n, m, num_triplets, exclude)
     if num_triplets + len(exclude) > n * m * (m - 1):
         raise ValueError(f"cannot draw {num_triplets} distinct triplets from a {n} x {m} matrix")
-    enc = lambda a: (a[:, 0] * m + a[:, 1]) * m + a[:, 2]                       # noqa: E731
-    barred = np.sort(enc(np.asarray(list(exclude), dtype=np.int64).reshape(-1, 3))) if exclude else None
-    state0 = torch.get_rng_state()
-    taken, taken_keys, attempts, need = [], np.empty(0, dtype=np.int64), 0, int(num_triplets)
-    while need > 0:
-        block = max(4096, need + need // 8 + 64)
+    kept = _Kept(m, num_triplets, exclude)
+    state0, attempts = torch.get_rng_state(), 0
+    while kept.need > 0:
+        block = max(4096, kept.need + kept.need // 8 + 64)
         w = torch.randint(0, L, (3 * block,)).numpy().reshape(block, 3)
-        cand = np.stack((w[:, 0] % n, w[:, 1] % m, w[:, 2] % m), axis=1)
-        key = enc(cand)
-        ok = cand[:, 1] != cand[:, 2]
-        if barred is not None:
-            ok &= ~np.isin(key, barred)
-        if taken_keys.size:
-            ok &= ~np.isin(key, taken_keys)
-        idx = np.flatnonzero(ok)
-        _, first = np.unique(key[idx], return_index=True)                      # first attempt of every new triplet
-        idx = idx[np.sort(first)]
-        if idx.size >= need:
-            idx = idx[:need]
-            attempts += int(idx[-1]) + 1
-        else:
-            attempts += block
-        taken.append(cand[idx])
-        taken_keys = np.concatenate((taken_keys, key[idx]))
-        need -= idx.size
-    torch.set_rng_state(state0)
-    torch.randint(0, L, (3 * attempts,))                                        # leave the generator where the loop would
-    rows = np.concatenate(taken)
-    found = set()
-    for t in zip(rows[:, 0].tolist(), rows[:, 1].tolist(), rows[:, 2].tolist()):
-        found.add(t)
-    return list(found)
+        us, ii, jj = w[:, 0] % n, w[:, 1] % m, w[:, 2] % m
+        attempts += kept.take(us, ii, jj, ii != jj)
+    _advance_generators(state0, None, 3 * attempts, L, 0)
+    return kept.triplets()
 
 
 def _choose_items_by_proximity_serial(X, num_triplets, exclude, k=100):
     n, m = X.shape
-    kk = min(k, m)
+    kk = _proximity_k(m, k)
     found, cache = set(), {}
     while len(found) < num_triplets:
         u = int(torch.randint(0, n, (1,)))
@@ -117,17 +185,6 @@ def _legacy_choice_block(k, nwords):
     return val[pos].astype(np.int64), pos
 
 
-def _advance_generators(t_state, n_state, torch_words, n, numpy_words):
-    """Put torch's CPU generator `torch_words` draws of randint(0, n) and numpy's global generator `numpy_words` 32-bit
-    words past the given states: where a one-attempt-at-a-time loop that used that many would have left them."""
-    torch.set_rng_state(t_state)
-    np.random.set_state(n_state)
-    if torch_words:
-        torch.randint(0, n, (torch_words,))
-    if numpy_words:
-        np.random.randint(0, 2 ** 32, size=numpy_words, dtype=np.uint32)
-
-
 def _user_item_tables(X, users, kk, worst):
     """Rows of torch.topk indices (the reference's per-user lists) for the distinct users of a block."""
     uu, inv = np.unique(users, return_inverse=True)
@@ -142,33 +199,6 @@ def _user_item_tables(X, users, kk, worst):
     return inv, best, low
 
 
-def _first_new(key, ok, barred, found_keys):
-    """Indices (ascending) of the attempts that add a triplet: allowed, not barred, first occurrence of their key."""
-    if barred is not None:
-        ok = ok & ~np.isin(key, barred)
-    if found_keys.size:
-        ok = ok & ~np.isin(key, found_keys)
-    idx = np.flatnonzero(ok)
-    _, first = np.unique(key[idx], return_index=True)
-    first.sort()
-    return idx[first]
-
-
-def _barred_keys(exclude, m):
-    if not exclude:
-        return None
-    return np.sort(np.fromiter(((u * m + i) * m + j for u, i, j in exclude), dtype=np.int64, count=len(exclude)))
-
-
-def _as_tuple_list(rows):
-    """list(set) of the rows inserted in attempt order: the order the reference's `list(triplets)` has."""
-    got = np.concatenate(rows) if rows else np.empty((0, 3), dtype=np.int64)
-    found = set()
-    for t in zip(got[:, 0].tolist(), got[:, 1].tolist(), got[:, 2].tolist()):
-        found.add(t)
-    return list(found)
-
-
 def choose_items_by_proximity(X, num_triplets, exclude, k=100):
     """"Min-Max": i among the user's k best items, j among the k worst (ref:29-43): per attempt one torch.randint(n),
     two torch.topk over the user's row and two legacy `np.random.choice(list)` calls.
@@ -179,38 +209,27 @@ def choose_items_by_proximity(X, num_triplets, exclude, k=100):
     lists have k entries, so the two calls share range and mask).  Both generators are left where the
     one-at-a-time loop would leave them.  The reference recomputes both topk for every attempt (O(m) each)."""
     n, m = X.shape
-    kk = min(k, m)
+    kk = _proximity_k(m, k)
     exclude = exclude or set()
     if kk < 2 or n >= 2 ** 32 or num_triplets <= 0 or not (torch.is_tensor(X) or isinstance(X, FactoredMatrix)):
         return _choose_items_by_proximity_serial(X, num_triplets, exclude, k)
-    barred = _barred_keys(exclude, m)
+    kept = _Kept(m, num_triplets, exclude)
     t_state, n_state = torch.get_rng_state(), np.random.get_state()
-    rows, found_keys = [], np.empty(0, dtype=np.int64)
     attempts = words = 0
-    need = int(num_triplets)
     span = 1 << (kk - 1).bit_length()                                            # words per accepted draw ~ span / kk
-    while need > 0:
-        A = max(4096, need + need // 4 + 64)
+    while kept.need > 0:
+        A = max(4096, kept.need + kept.need // 4 + 64)
         idx_stream, pos = _legacy_choice_block(kk, int(2 * A * span / kk * 1.05) + 256)
         A = min(A, idx_stream.size // 2)
         us = torch.randint(0, n, (A,)).numpy()
         inv, best, low = _user_item_tables(X, us, kk, worst=True)
         ii = best[inv, idx_stream[0:2 * A:2]].astype(np.int64)
         jj = low[inv, idx_stream[1:2 * A:2]].astype(np.int64)
-        key = (us.astype(np.int64) * m + ii) * m + jj
-        idx = _first_new(key, ii != jj, barred, found_keys)
-        if idx.size >= need:
-            idx = idx[:need]
-            used = int(idx[-1]) + 1
-        else:
-            used = A
+        used = kept.take(us, ii, jj, ii != jj)
         attempts += used
         words += int(pos[2 * used - 1]) + 1
-        rows.append(np.stack((us[idx], ii[idx], jj[idx]), axis=1))
-        found_keys = np.concatenate((found_keys, key[idx]))
-        need -= idx.size
         _advance_generators(t_state, n_state, attempts, n, words)
-    return _as_tuple_list(rows)
+    return kept.triplets()
 
 
 def _x_pair_diff(X, us, ii, jj):
@@ -252,18 +271,12 @@ def choose_items_by_margin(X, num_triplets, exclude, max_attempts=5000_000):
     Many blocks are drawn and filtered per numpy pass (the reference walks every attempt in Python); the attempt
     counter still advances in blocks of 500 and stops with the block that completes the request."""
     n, m = X.shape
-    exclude = exclude or set()
-    head = X.rows(0, min(10, n)) if isinstance(X, FactoredMatrix) else X[:min(10, n)].cpu().numpy()
-    margin = np.mean(head.max(axis=1) - head.min(axis=1)) * num_triplets / (n * m)
+    margin = _margin_threshold(X, num_triplets)
     Xn = X if isinstance(X, FactoredMatrix) else X.cpu().numpy()
     rng = np.random.default_rng()
-    enc = lambda u, i, j: (u.astype(np.int64) * m + i) * m + j                   # noqa: E731
-    barred = np.sort(np.fromiter(((u * m + i) * m + j for u, i, j in exclude), dtype=np.int64, count=len(exclude))) \
-        if exclude else None
-    found_keys = np.empty(0, dtype=np.int64)
-    rows, attempts, block = [], 0, 500
-    need = int(num_triplets)
-    while need > 0 and attempts < max_attempts:
+    kept = _Kept(m, num_triplets, exclude)
+    attempts, block = 0, 500
+    while kept.need > 0 and attempts < max_attempts:
         nblk = max(1, min(400, (max_attempts - attempts + block - 1) // block))   # blocks in this pass
         us = rng.integers(0, n, size=nblk * block)
         ij = rng.integers(0, m, size=(nblk * block, 2))
@@ -271,34 +284,11 @@ def choose_items_by_margin(X, num_triplets, exclude, max_attempts=5000_000):
         close = ii != jj
         cand = np.flatnonzero(close)
         close[cand] = np.abs(_x_pair_diff(Xn, us[cand], ii[cand], jj[cand])) <= margin
-        idx = np.flatnonzero(close)
-        key = enc(us[idx], ii[idx], jj[idx])
-        ok = np.ones(idx.size, dtype=bool)
-        if barred is not None:
-            ok &= ~np.isin(key, barred)
-        if found_keys.size:
-            ok &= ~np.isin(key, found_keys)
-        idx, key = idx[ok], key[ok]
-        _, first = np.unique(key, return_index=True)                              # first attempt of every new triplet
-        first.sort()
-        idx, key = idx[first], key[first]
-        if idx.size >= need:                                                      # the request completes inside this pass
-            idx, key = idx[:need], key[:need]
-            attempts += (int(idx[-1]) // block + 1) * block
-        else:
-            attempts += nblk * block
-        rows.append(np.stack((us[idx], ii[idx], jj[idx]), axis=1))
-        found_keys = np.concatenate((found_keys, key))
-        need -= idx.size
-    got = np.concatenate(rows) if rows else np.empty((0, 3), dtype=np.int64)
-    found = set()
-    for t in zip(got[:, 0].tolist(), got[:, 1].tolist(), got[:, 2].tolist()):
-        found.add(t)
-    if len(found) < num_triplets:
-        top = float(np.max(X.A.numpy()) if isinstance(X, FactoredMatrix) else np.max(Xn))
-        print(f"⚠️ Only {len(found)} triplets generated (target={num_triplets}, margin={margin:.4f}) "
-              f"after {attempts} attempts.maximum : {top}")
-    return list(found)
+        used = kept.take(us, ii, jj, close)
+        attempts += -(-used // block) * block                                     # to the end of the completing block
+    found = kept.triplets()
+    _report_short_margin(X, len(found), num_triplets, margin, attempts)
+    return found
 
 
 def choose_items_by_variance(X, num_triplets, exclude):
@@ -358,16 +348,12 @@ def choose_items_by_popularity(X, num_triplets, exclude, method="zipf", alpha=1.
         return _choose_items_by_popularity_serial(n, m, probs, num_triplets, exclude)
     cdf = np.cumsum(probs)
     cdf /= cdf[-1]
-    enc = lambda u, i, j: (u.astype(np.int64) * m + i) * m + j                   # noqa: E731
-    barred = np.sort(np.fromiter(((u * m + i) * m + j for u, i, j in exclude), dtype=np.int64, count=len(exclude))) \
-        if exclude else None
+    kept = _Kept(m, num_triplets, exclude)
     t_state, n_state = torch.get_rng_state(), np.random.get_state()
-    rows, found_keys = [], np.empty(0, dtype=np.int64)
     attempts = uniforms = 0
-    need = int(num_triplets)
     cdf_without = {}
-    while need > 0:
-        A = max(4096, need + need // 4 + 64)
+    while kept.need > 0:
+        A = max(4096, kept.need + kept.need // 4 + 64)
         us = torch.randint(0, n, (A,)).numpy()
         x = np.random.random_sample(3 * A)
         first = cdf.searchsorted(x, side="right")
@@ -393,41 +379,13 @@ def choose_items_by_popularity(X, num_triplets, exclude, method="zipf", alpha=1.
                         cdf_without[item] = c2
                 sel = ii[coll] == item
                 jj[coll[sel]] = c2.searchsorted(extra[sel], side="right")
-        key = enc(us, ii, jj)
-        ok = ii != jj
-        if barred is not None:
-            ok &= ~np.isin(key, barred)
-        if found_keys.size:
-            ok &= ~np.isin(key, found_keys)
-        idx = np.flatnonzero(ok)
-        _, fst = np.unique(key[idx], return_index=True)
-        fst.sort()
-        idx = idx[fst]
-        if idx.size >= need:
-            idx = idx[:need]
-            last = int(idx[-1])
-            attempts += last + 1
-            uniforms += int(starts[last]) + (3 if same[int(starts[last])] else 2)
-        else:
-            attempts += A
-            uniforms += pos
-            # the next block must continue where this one ended in BOTH streams
-            torch.set_rng_state(t_state)
-            np.random.set_state(n_state)
-            torch.randint(0, n, (attempts,))
-            np.random.random_sample(uniforms)
-        rows.append(np.stack((us[idx], ii[idx], jj[idx]), axis=1))
-        found_keys = np.concatenate((found_keys, key[idx]))
-        need -= idx.size
-    torch.set_rng_state(t_state)
-    np.random.set_state(n_state)
-    torch.randint(0, n, (attempts,))                                              # leave both generators where the
-    np.random.random_sample(uniforms)                                             # one-at-a-time loop would
-    got = np.concatenate(rows)
-    found = set()
-    for t in zip(got[:, 0].tolist(), got[:, 1].tolist(), got[:, 2].tolist()):
-        found.add(t)
-    return list(found)
+        used = kept.take(us, ii, jj, ii != jj)
+        last = int(starts[used - 1])                                              # first uniform of the last one used
+        attempts += used
+        uniforms += last + (3 if same[last] else 2)
+        # both generators go where the one-at-a-time loop would be: the next block continues from there
+        _advance_generators(t_state, n_state, attempts, n, 2 * uniforms)
+    return kept.triplets()
 
 
 def choose_items_by_svd_projection(X, num_triplets, exclude, rank=10, top_fraction=0.3):
@@ -435,35 +393,22 @@ def choose_items_by_svd_projection(X, num_triplets, exclude, rank=10, top_fracti
     from the sampling density and at most 5*num_triplets attempts are made: u uniform over the top users, (i, j) an
     ordered pair of distinct top items.  The attempts come from an UNSEEDED numpy Generator in the reference (no draw
     order to keep), so they are drawn and filtered in one numpy pass each block instead of one Python iteration each."""
-    import scipy.sparse.linalg as spla
     n, m = X.shape
-    exclude = exclude or set()
-    rank = int(num_triplets / (n * m) * max(n, m))
-    Us, S, Vt = spla.svds(X.cpu().numpy(), k=rank)
-    u_norm = np.linalg.norm(Us * S, axis=1)
-    i_norm = np.linalg.norm((Vt.T * S), axis=1)
-    top_users = np.argsort(u_norm)[-max(1, int(top_fraction * n)):]
-    top_items = np.argsort(i_norm)[-max(2, int(top_fraction * m)):]
+    top_users, top_items = _svd_top_sets(X, num_triplets, top_fraction)
     rng = np.random.default_rng()
-    barred = _barred_keys(exclude, m)
-    rows, found_keys = [], np.empty(0, dtype=np.int64)
-    need, budget = int(num_triplets), 5 * int(num_triplets)
-    while need > 0 and budget > 0:
-        A = min(budget, max(4096, need + need // 4 + 64))
+    kept = _Kept(m, num_triplets, exclude)
+    budget = 5 * int(num_triplets)
+    while kept.need > 0 and budget > 0:
+        A = min(budget, max(4096, kept.need + kept.need // 4 + 64))
         us = top_users[rng.integers(0, top_users.size, size=A)].astype(np.int64)
         a = rng.integers(0, top_items.size, size=A)
         b = rng.integers(0, top_items.size - 1, size=A)
         b += b >= a                                                              # uniform over the ordered distinct pairs
         ii, jj = top_items[a].astype(np.int64), top_items[b].astype(np.int64)
-        key = (us * m + ii) * m + jj
-        idx = _first_new(key, ii != jj, barred, found_keys)[:need]
+        kept.take(us, ii, jj, ii != jj)
         budget -= A
-        rows.append(np.stack((us[idx], ii[idx], jj[idx]), axis=1))
-        found_keys = np.concatenate((found_keys, key[idx]))
-        need -= idx.size
-    found = _as_tuple_list(rows)
-    if len(found) < num_triplets:
-        print(f"⚠️ Only {len(found)} triplets generated (target={num_triplets})")
+    found = kept.triplets()
+    _report_short(len(found), num_triplets)
     return found
 
 
@@ -473,8 +418,7 @@ def estimate_k(num_triplets):
 
 def _choose_items_top_k_serial(X, num_triplets, exclude, k=None):
     n, m = X.shape
-    if k is None:
-        k = min(m, max(5, int(0.1 * m)))
+    k = _top_k_k(m, k)
     found, cache = set(), {}
     for _ in range(num_triplets * 3):
         u = int(torch.randint(0, n, (1,)))
@@ -490,8 +434,7 @@ def _choose_items_top_k_serial(X, num_triplets, exclude, k=None):
             found.add(t)
         if len(found) >= num_triplets:
             break
-    if len(found) < num_triplets:
-        print(f"⚠️ Only {len(found)} triplets generated (target={num_triplets}, k={k})")
+    _report_short(len(found), num_triplets, f", k={k}")
     return list(found)
 
 
@@ -504,18 +447,15 @@ def choose_items_top_k(X, num_triplets, exclude, k=None):
     (a cheap integer pass); the users are one randint call, their lists one batched topk."""
     n, m = X.shape
     exclude = exclude or set()
-    if k is None:
-        k = min(m, max(5, int(0.1 * m)))
+    k = _top_k_k(m, k)
     if k < 2 or n >= 2 ** 32 or num_triplets <= 0 or not (torch.is_tensor(X) or isinstance(X, FactoredMatrix)):
         return _choose_items_top_k_serial(X, num_triplets, exclude, k)
-    barred = _barred_keys(exclude, m)
+    kept = _Kept(m, num_triplets, exclude)
     t_state, n_state = torch.get_rng_state(), np.random.get_state()
-    rows, found_keys = [], np.empty(0, dtype=np.int64)
-    attempts = words = 0
-    need, budget = int(num_triplets), 3 * int(num_triplets)
+    attempts, words, budget = 0, 0, 3 * int(num_triplets)
     span = 1 << (k - 1).bit_length()
-    while need > 0 and attempts < budget:
-        A = min(budget - attempts, max(4096, need + need // 4 + 64))
+    while kept.need > 0 and attempts < budget:
+        A = min(budget - attempts, max(4096, kept.need + kept.need // 4 + 64))
         idx_stream, pos = _legacy_choice_block(k, int(2 * A * (1 + 2.0 / k) * span / k * 1.05) + 256)
         stream = idx_stream.tolist()
         i_at, j_at = [], []
@@ -535,22 +475,12 @@ def choose_items_top_k(X, num_triplets, exclude, k=None):
         inv, best, _ = _user_item_tables(X, us, k, worst=False)
         ii = best[inv, idx_stream[i_at]].astype(np.int64)
         jj = best[inv, idx_stream[j_at]].astype(np.int64)
-        key = (us.astype(np.int64) * m + ii) * m + jj
-        idx = _first_new(key, np.ones(A, dtype=bool), barred, found_keys)
-        if idx.size >= need:
-            idx = idx[:need]
-            used = int(idx[-1]) + 1
-        else:
-            used = A
+        used = kept.take(us, ii, jj, ii != jj)                                    # distinct positions: always allowed
         attempts += used
         words += int(pos[j_at[used - 1]]) + 1
-        rows.append(np.stack((us[idx], ii[idx], jj[idx]), axis=1))
-        found_keys = np.concatenate((found_keys, key[idx]))
-        need -= idx.size
         _advance_generators(t_state, n_state, attempts, n, words)
-    found = _as_tuple_list(rows)
-    if len(found) < num_triplets:
-        print(f"⚠️ Only {len(found)} triplets generated (target={num_triplets}, k={k})")
+    found = kept.triplets()
+    _report_short(len(found), num_triplets, f", k={k}")
     return found
 
 

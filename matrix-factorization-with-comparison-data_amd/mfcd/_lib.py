@@ -165,6 +165,12 @@ def ptr(t):
     return t.data_ptr()
 
 
+def is_factored(X):
+    """X is kept as its factors, X = A @ B.T (a generation_data.FactoredMatrix, told by its shape: this package does
+    not import that module)."""
+    return not torch.is_tensor(X) and hasattr(X, "A") and hasattr(X, "B")
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)   # the handle without building a Stream object
 
 

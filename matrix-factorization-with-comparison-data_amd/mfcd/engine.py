@@ -259,13 +259,13 @@ def generate_labels(triplets, X, scale=1.0, K=1, soft=False, seed=0, device=None
             raise IndexError("triplet index out of range for X")          # as X[u, i] would (structure.py:509)
         trip = torch.from_numpy(idx.astype(np.int32)).to(device)
     out = torch.empty((T if soft else T * K, 4), dtype=torch.int32, device=device)
-    if isinstance(X, torch.Tensor):
-        Xd = X.detach().to(device=device, dtype=torch.float32).contiguous()
-        args = (_lib.ptr(Xd), n, m, None, None, 0)
-    else:                                                              # FactoredMatrix
+    if _lib.is_factored(X):
         A = X.A.to(device).contiguous()
         B = X.B.to(device).contiguous()
         args = (None, n, m, _lib.ptr(A), _lib.ptr(B), A.shape[1])
+    else:
+        Xd = X.detach().to(device=device, dtype=torch.float32).contiguous()
+        args = (_lib.ptr(Xd), n, m, None, None, 0)
     _lib.check(L.mfcd_generate_labels(_lib.ptr(trip) if T else None, T, *args, float(scale), int(K), int(bool(soft)),
                                       int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(out) if out.numel() else None,
                                       _lib.stream_ptr(device)))

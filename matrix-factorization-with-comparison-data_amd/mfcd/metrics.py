@@ -78,10 +78,6 @@ def uvt_stats_factored(U, V, FX, s=1.0, what=3, slab_rows=4096):
     return row_stats, scal
 
 
-def _is_factored(X):
-    return hasattr(X, "A") and hasattr(X, "B") and not isinstance(X, torch.Tensor)
-
-
 def uvt_rows(U, V, row_ids):
     """Rows `row_ids` of UV^T as a [k, m] fp32 device tensor (structure.py:389-392 without the full GEMM)."""
     L = _lib.load()
@@ -100,7 +96,7 @@ def uvt_rows(U, V, row_ids):
 
 def reconstruction_error(U, V, X, s):
     """compute_reconstruction_error (structure.py:925-955) → float."""
-    _, scal = uvt_stats_factored(U, V, X, s, what=2) if _is_factored(X) else uvt_stats(U, V, X, s, what=2)
+    _, scal = uvt_stats_factored(U, V, X, s, what=2) if _lib.is_factored(X) else uvt_stats(U, V, X, s, what=2)
     e2, r2 = scal[:2].cpu().tolist()
     return float(np.sqrt(e2) / np.sqrt(r2)) if r2 > 0 else float("nan") if e2 == 0 else float("inf")
 

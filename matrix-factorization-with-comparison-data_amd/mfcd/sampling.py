@@ -34,35 +34,32 @@ class _Law:
         self.keep = []
         self.budget = None           # attempt budget of the strategy (None: until the request is met)
         self.block_multiple = 1      # the margin strategy counts attempts in blocks of 500
+        self.report = lambda got, attempts: None   # the strategy's message for a short result (the reference's own)
 
     def hold(self, t):
         self.keep.append(t)
         return _lib.ptr(t)
 
 
-def _is_factored(X):
-    return hasattr(X, "pair_diff") and hasattr(X, "A")
-
-
 def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha=1.5, k=None, max_attempts=5_000_000):
-    """The reference's per-strategy set-up (everything in front of its attempt loop) → a device law."""
+    """The reference's per-strategy set-up (everything in front of its attempt loop, as generation_data defines it) → a
+    device law."""
     import generation_data as _gd
     n, m = X.shape
     law = _Law(n, m, device)
     c = law.c
     if strategy == "random":
         return law
-    if strategy == "margin":                                             # generation_data.py:56-57
-        head = X.rows(0, min(10, n)) if _is_factored(X) else X[:min(10, n)].detach().cpu().numpy()
+    if strategy == "margin":
         c.use_margin = 1
-        c.margin = float(np.mean(head.max(axis=1) - head.min(axis=1)) * num_triplets / (n * m))
-        if _is_factored(X):
+        c.margin = float(_gd._margin_threshold(X, num_triplets))
+        if _lib.is_factored(X):
             A, B = X.A.to(device).contiguous(), X.B.to(device).contiguous()
             c.A, c.B, c.dx = law.hold(A), law.hold(B), A.shape[1]
         else:
             c.X = law.hold(_dense_on(X, device))
         law.budget, law.block_multiple = int(max_attempts), 500
-        law.margin = c.margin
+        law.report = lambda got, attempts: _gd._report_short_margin(X, got, num_triplets, c.margin, attempts)
         return law
     if strategy in ("popularity", "variance"):
         if strategy == "popularity":                                    # generation_data.py:110-119
@@ -81,18 +78,18 @@ def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha
         return law
     if strategy in ("proximity", "top_k"):
         # a factored X never becomes dense: its lists come from mfcd_topk_rows over the factors (one call, all n rows)
-        fac = (X.A.to(device).contiguous(), X.B.to(device).contiguous()) if _is_factored(X) else None
+        fac = (X.A.to(device).contiguous(), X.B.to(device).contiguous()) if _lib.is_factored(X) else None
         Xd = None if fac else _dense_on(X, device)
-        if strategy == "proximity":                                     # generation_data.py:36-37
-            kk = min(100 if k is None else int(k), m)
+        if strategy == "proximity":
+            kk = int(_gd._proximity_k(m, k))
             if fac:
                 best, worst = _topk.topk_rows(fac, kk, ends="both")
             else:
                 best = torch.topk(Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
                 worst = torch.topk(-Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
             c.list_i, c.list_j, c.pair_rule = law.hold(best), law.hold(worst), 0
-        else:                                                            # generation_data.py:198-213
-            kk = min(m, max(5, int(0.1 * m))) if k is None else int(k)
+        else:
+            kk = int(_gd._top_k_k(m, k))
             if fac:
                 best = _topk.topk_rows(fac, kk, ends="best")
             else:
@@ -100,20 +97,17 @@ def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha
             c.list_i = c.list_j = law.hold(best)
             c.pair_rule = 1
             law.budget = 3 * int(num_triplets)
-            law.k = kk
+            law.report = lambda got, attempts: _gd._report_short(got, num_triplets, f", k={kk}")
         c.law, c.k, c.list_row_stride = LAW_LISTS, kk, kk
         return law
-    if strategy == "svd":                                                # generation_data.py:144-162
-        import scipy.sparse.linalg as spla
-        rank = int(num_triplets / (n * m) * max(n, m))
-        Us, S, Vt = spla.svds(X.detach().cpu().numpy(), k=rank)
-        top_users = np.argsort(np.linalg.norm(Us * S, axis=1))[-max(1, int(0.3 * n)):]
-        top_items = np.argsort(np.linalg.norm(Vt.T * S, axis=1))[-max(2, int(0.3 * m)):]
+    if strategy == "svd":
+        top_users, top_items = _gd._svd_top_sets(X, num_triplets)
         items = torch.from_numpy(top_items.astype(np.int32)).to(device)
         c.law, c.k, c.list_row_stride, c.pair_rule = LAW_LISTS, int(items.numel()), 0, 1
         c.list_i = c.list_j = law.hold(items)
         c.users, c.n_users = law.hold(torch.from_numpy(top_users.astype(np.int32)).to(device)), int(top_users.size)
         law.budget = 5 * int(num_triplets)
+        law.report = lambda got, attempts: _gd._report_short(got, num_triplets)
         return law
     raise ValueError(f"no device law for triplet sampling strategy: {strategy}")
 
@@ -183,13 +177,5 @@ def sample_triplets(X, num_triplets, strategy="random", exclude=None, device=Non
         seed = int(torch.empty((), dtype=torch.int64).random_().item())
     law = build_law(X, int(num_triplets), strategy, device, **kw)
     trip, attempts = run_law(law, num_triplets, exclude, seed)
-    if trip.shape[0] < num_triplets:                                     # the reference's own messages
-        if strategy == "margin":
-            top = float(X.A.max()) if _is_factored(X) else float(X.max())
-            print(f"⚠️ Only {trip.shape[0]} triplets generated (target={num_triplets}, margin={law.margin:.4f}) "
-                  f"after {attempts} attempts.maximum : {top}")
-        elif strategy == "top_k":
-            print(f"⚠️ Only {trip.shape[0]} triplets generated (target={num_triplets}, k={law.k})")
-        elif strategy == "svd":
-            print(f"⚠️ Only {trip.shape[0]} triplets generated (target={num_triplets})")
+    law.report(trip.shape[0], attempts)
     return trip

@@ -44,7 +44,7 @@ def _resolve(X, device):
         return Xd, None, None, Xd.shape[0], Xd.shape[1], 0, Xd.device
     if isinstance(X, (tuple, list)) and len(X) == 2:
         A, B = _gpu_f32(X[0], "A").contiguous(), _gpu_f32(X[1], "B").contiguous()
-    elif hasattr(X, "A") and hasattr(X, "B"):      # FactoredMatrix: a host object, its factors move per call
+    elif _lib.is_factored(X):                      # a host object, its factors move per call
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if dev.type != "cuda":
             raise _lib.MfcdError("topk_rows needs a GPU device (there is no CPU fallback)")

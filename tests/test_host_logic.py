@@ -312,6 +312,51 @@ def test_bulk_samplers_equal_their_one_at_a_time_loops(strategy, n, m, want, n_e
     assert np.array_equal(now[1], state[1][1]) and now[2] == state[1][2]
 
 
+@pytest.mark.parametrize("n,m,want,n_excl,max_attempts", [
+    (40, 30, 300, 0, 5_000_000), (40, 30, 300, 80, 5_000_000), (40, 30, 600, 0, 400), (6, 5, 110, 20, 200_700)])
+@pytest.mark.parametrize("factored", [False, True])
+def test_margin_sampler_equals_a_per_attempt_walk_over_the_same_draws(factored, n, m, want, n_excl, max_attempts,
+                                                                      monkeypatch, capsys):
+    """generation_data.py:46-84 draws from an unseeded numpy Generator; with `default_rng` replaced by a seeded one, the
+    bulk form returns the list and prints the message of a walk, one attempt at a time, over the same draws: the same
+    pass sizes, every attempt tested against `exclude` and the set so far, the counter advanced by blocks of 500 and
+    stopped with the block that completes the request.  The last two cases spend their budget (in one pass, and in two
+    with more asked than `exclude` leaves), so the warning is compared too."""
+    import generation_data as G
+    gen = torch.Generator().manual_seed(n + m + want)
+    A, B = torch.randn(n, 4, generator=gen), torch.randn(m, 4, generator=gen)
+    X = G.FactoredMatrix(A, B) if factored else A @ B.t()
+    monkeypatch.setattr(np.random, "default_rng", lambda: np.random.Generator(np.random.PCG64(want + n_excl)))
+    excl = set(G.choose_items_by_margin(X, want, set(), max_attempts=max_attempts)[:n_excl])
+    assert len(excl) == n_excl
+    capsys.readouterr()
+    got = G.choose_items_by_margin(X, want, excl, max_attempts=max_attempts)
+    printed = capsys.readouterr().out
+
+    head = X.rows(0, min(10, n)) if factored else X[:min(10, n)].numpy()
+    margin = np.mean(head.max(axis=1) - head.min(axis=1)) * want / (n * m)
+    rng = np.random.default_rng()
+    found, attempts = set(), 0
+    while len(found) < want and attempts < max_attempts:
+        size = 500 * max(1, min(400, -(-(max_attempts - attempts) // 500)))
+        us = rng.integers(0, n, size=size)
+        ij = rng.integers(0, m, size=(size, 2))
+        close = np.abs(G._x_pair_diff(X, us, ij[:, 0], ij[:, 1])) <= margin
+        for a, t in enumerate(zip(us.tolist(), ij[:, 0].tolist(), ij[:, 1].tolist())):
+            if a % 500 == 0:
+                if len(found) >= want:
+                    break
+                attempts += 500
+            if len(found) < want and t[1] != t[2] and close[a] and t not in excl and t not in found:
+                found.add(t)
+    expect = "" if len(found) >= want else (
+        f"⚠️ Only {len(found)} triplets generated (target={want}, margin={margin:.4f}) after {attempts} "
+        f"attempts.maximum : {float((A if factored else X).max())}\n")
+    assert got == list(found)
+    assert printed == expect
+    assert (len(found) < want) == (max_attempts < 5_000_000)
+
+
 def test_svd_sampler_draws_distinct_allowed_triplets_from_the_top_sets():
     """generation_data.py:131-179 (unseeded numpy Generator: no draw order to keep): every triplet comes from the
     top-30 % users / items by projection norm, is unique, respects `exclude`, and a request larger than the support
