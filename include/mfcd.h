@@ -533,6 +533,14 @@ int mfcd_spearman_rows_long(const float *A, int64_t lda, const float *X, int64_t
  *              MFCD_LAW_LISTS     i = list_i[u * list_row_stride + U[0,k)], j likewise from list_j; pair_rule 1 makes
  *                                 the two positions distinct (top_k, svd); list_row_stride = k for per-user tables
  *                                 (proximity, top_k), 0 for one list shared by all users (svd)
+ *              MFCD_LAW_GROUPS    (g1, g2) a uniform ordered pair of distinct groups among k >= 2, i uniform in group
+ *                                 g1, j uniform in group g2 (cluster, generation_data.py:241-243).  The struct's fields
+ *                                 are reused: list_i = the list_row_stride item ids grouped (ascending inside a group),
+ *                                 list_j = k + 1 ascending int32 offsets into it, k = the number of groups.  The
+ *                                 caller validates the tables (mfcd/sampling.py: group_tables); on the device a group
+ *                                 of length <= 0, a position outside [0, list_row_stride) or an item id outside [0, m)
+ *                                 rejects the attempt and nothing is read outside the tables.  Uses a third Philox
+ *                                 draw group; the draws of the other laws are unchanged by it.
  *   users      NULL (u over all n users) or n_users user ids to draw u from (svd: the top users)
  *   use_margin keep only |X[u][i] - X[u][j]| <= margin (fp32 difference, as generation_data.py:72-73); X dense
  *              [n][m] fp32, or NULL with the factors A [n][dx], B [m][dx] of X = A B^T
@@ -546,6 +554,7 @@ int mfcd_spearman_rows_long(const float *A, int64_t lda, const float *X, int64_t
 #define MFCD_LAW_UNIFORM 0
 #define MFCD_LAW_ITEM_CDF 1
 #define MFCD_LAW_LISTS 2
+#define MFCD_LAW_GROUPS 3
 
 typedef struct mfcd_sampler {
     int32_t law, n, m, pair_rule;
@@ -615,6 +624,29 @@ int mfcd_topk_rows(const float *X, int64_t ldx, const float *A, const float *B, 
                    int rows, int n, int m, int k, int ends, const int64_t *excl_off, const int32_t *excl_items,
                    int32_t *best_idx, float *best_val, int32_t *worst_idx, float *worst_val, void *workspace,
                    size_t workspace_bytes, void *stream);
+
+/*
+ * The two steps of Lloyd's k-means over row-major fp32 points [P][dim] (the `cluster` sampling strategy,
+ * generation_data.py:229-247: sklearn KMeans over the item columns; the points are the columns of a dense X, or the
+ * rows of B R^T with A^T A = R^T R for X = A B^T, which have the same pairwise distances).  The iteration, k-means++
+ * and the empty-cluster rule are the host's (mfcd/cluster.py).
+ *   assign   labels[p] = the nearest of the k centres [k][dim], the lowest index among equals, chosen as the argmax of
+ *            p . c - |c|^2 / 2 with the products on the exact fp32 MFMA; nothing of size P x k is stored.  dist2
+ *            (nullable) [P] = the fp32 squared distance to the chosen centre.  changed (nullable, device int32) = how
+ *            many labels differ from the `labels` passed in.
+ *   update   centres[c] = the mean of the points labelled c, summed in f64 in a fixed order and rounded once to fp32;
+ *            counts[c] = their number.  A cluster without members keeps its centre and gets count 0; a label outside
+ *            [0, k) is skipped.  No floating-point atomics: two calls are bit-equal.
+ * Limits: 1 <= k <= the max_k entry below (64), 1 <= dim <= 2^30, 1 <= P <= 4 194 304, P * dim < 2^40; MFCD_EINVAL
+ * outside them, with nothing launched.  workspace: as the workspace_bytes entry says (0 = sizes out of range), 256-byte
+ * aligned, the same buffer for both steps.  No allocation and no host wait.
+ */
+int mfcd_kmeans_max_k(void);
+size_t mfcd_kmeans_workspace_bytes(int64_t P, int64_t dim, int k);
+int mfcd_kmeans_assign(const float *points, int64_t P, int64_t dim, const float *centres, int k, int32_t *labels,
+                       float *dist2, int32_t *changed, void *workspace, size_t workspace_bytes, void *stream);
+int mfcd_kmeans_update(const float *points, int64_t P, int64_t dim, const int32_t *labels, int k, float *centres,
+                       int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

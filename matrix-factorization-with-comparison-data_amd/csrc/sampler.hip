@@ -16,6 +16,11 @@
 //                      the user's k best / k worst items; top_k :208-213: the k best twice, pair_rule 1 = positions
 //                      distinct, which is the law of the reference's redraw-while-equal loop) or one list shared by
 //                      all users (row stride 0; svd :168-169 with `users` = the top users)
+//   MFCD_LAW_GROUPS    (g1, g2) a uniform ordered pair of distinct groups of items, i uniform in g1, j uniform in g2
+//                      (cluster :241-243: np.random.choice(ids, 2, replace=False), then one choice per cluster).
+//                      list_i = the list_row_stride item ids grouped, list_j = k + 1 offsets into it.  Nothing read
+//                      from either table is used as an address before it is clamped to the table's length: an empty
+//                      or reversed group and an item id outside [0, m) reject the attempt.
 // Optional filter: |X[u][i] - X[u][j]| <= margin (generation_data.py:72-73), X dense fp32 or A B^T by its factors.
 // Randomness: Philox4x32-10 keyed by the caller's seed, counter = (attempt index, draw group): a function of
 // (seed, attempt index) alone.  It is NOT the reference's Mersenne-Twister stream: parity is distributional (same law
@@ -84,6 +89,22 @@ __global__ __launch_bounds__(256) void sample_attempts_kernel(mfcd_sampler law, 
             if (j == i) j = i + 1 < law.m ? i + 1 : i - 1;       // x landed on i's upper edge after rounding
             ok = (1.0 - mass) > 0.0 && j >= 0;
         }
+    } else if (law.law == MFCD_LAW_GROUPS) {
+        unsigned c2[4] = {(unsigned)t, (unsigned)(t >> 32), 2u, 0x73616d70u};      // this law's own draw group
+        philox4x32_10(c2, seed_lo, seed_hi);
+        const int k = law.k, len = law.list_row_stride;
+        const int g1 = (int)below(b0, k);                  // in [0, k): offsets g, g + 1 are inside the k + 1 entries
+        int g2 = (int)below(b1, k - 1);
+        g2 += g2 >= g1;
+        const int lo1 = law.list_j[g1], n1 = law.list_j[g1 + 1] - lo1;
+        const int lo2 = law.list_j[g2], n2 = law.list_j[g2 + 1] - lo2;
+        ok = n1 > 0 && n2 > 0;
+        const int64_t pi = (int64_t)lo1 + below(pair64(c2[0], c2[1]), ok ? n1 : 1);
+        const int64_t pj = (int64_t)lo2 + below(pair64(c2[2], c2[3]), ok ? n2 : 1);
+        i = law.list_i[pi < 0 ? 0 : pi < len ? pi : len - 1];
+        j = law.list_i[pj < 0 ? 0 : pj < len ? pj : len - 1];
+        ok = ok && pi >= 0 && pi < len && pj >= 0 && pj < len && i >= 0 && i < law.m && j >= 0 && j < law.m;
+        if (!ok) i = j = 0;                                 // (the margin filter below is skipped with it)
     } else {
         const int k = law.k;
         const int64_t row = (int64_t)u * law.list_row_stride;
@@ -222,6 +243,8 @@ extern "C" int mfcd_sample_triplets(const mfcd_sampler *law, const int64_t *barr
     } else if (L.law == MFCD_LAW_LISTS) {
         if (!L.list_i || !L.list_j || L.k < 1 || (L.pair_rule == 1 && L.k < 2) || L.list_row_stride < 0)
             return MFCD_EINVAL;
+    } else if (L.law == MFCD_LAW_GROUPS) {
+        if (!L.list_i || !L.list_j || L.k < 2 || L.list_row_stride < 1) return MFCD_EINVAL;
     } else if (L.law != MFCD_LAW_UNIFORM) {
         return MFCD_EINVAL;
     }

@@ -291,10 +291,19 @@ def choose_items_by_margin(X, num_triplets, exclude, max_attempts=5000_000):
     return found
 
 
+def _factored_column_variances(X):
+    """torch.var(X, dim=0) of X = A @ B.T from the factors → float64 CPU tensor [m]: the unbiased variance of column c
+    is B[c]^T cov(A) B[c] with the unbiased d x d covariance of A's rows, in f64; nothing n x m is formed."""
+    A, B = X.A.double(), X.B.double()
+    Ac = A - A.mean(dim=0, keepdim=True)
+    cov = Ac.t() @ Ac / (A.shape[0] - 1)              # one user: 0 / 0 = NaN, as torch.var
+    return ((B @ cov) * B).sum(dim=1)
+
+
 def choose_items_by_variance(X, num_triplets, exclude):
     """Items drawn proportionally to their variance across users (ref:87-99)."""
     n, m = X.shape
-    var = torch.var(X, dim=0)
+    var = _factored_column_variances(X) if isinstance(X, FactoredMatrix) else torch.var(X, dim=0)
     probs = var / var.sum()
     found = set()
     while len(found) < num_triplets:
@@ -485,10 +494,16 @@ def choose_items_top_k(X, num_triplets, exclude, k=None):
 
 
 def choose_items_cluster_based(X, num_triplets, exclude, n_clusters=20):
-    """i and j from two different k-means clusters of the item columns (ref:229-247)."""
+    """i and j from two different k-means clusters of the item columns (ref:229-247).  A FactoredMatrix has no X.T:
+    its items are clustered through B R^T (mfcd.cluster.item_points), which has the columns' pairwise distances."""
     from sklearn.cluster import KMeans
     n, m = X.shape
-    labels = KMeans(n_clusters=n_clusters, n_init="auto").fit_predict(X.T.cpu().numpy())
+    if isinstance(X, FactoredMatrix):
+        from mfcd import cluster as _cluster
+        points = _cluster.item_points(X, "cpu").numpy()
+    else:
+        points = X.T.cpu().numpy()
+    labels = KMeans(n_clusters=n_clusters, n_init="auto").fit_predict(points)
     members = {c: np.where(labels == c)[0] for c in range(n_clusters)}
     ids = list(members)
     found = set()

@@ -87,6 +87,10 @@ SIGNATURES = {
     "mfcd_topk_max_k": (_i32, []),
     "mfcd_topk_rows_workspace_bytes": (_sz, [_i32] * 5),
     "mfcd_topk_rows": (_i32, [_vp, _i64, _vp, _vp, _i32, _vp] + [_i32] * 5 + [_vp] * 7 + [_sz, _vp]),
+    "mfcd_kmeans_max_k": (_i32, []),
+    "mfcd_kmeans_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "mfcd_kmeans_assign": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mfcd_kmeans_update": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 TUNE_KEYS = {"resident_lookahead": 3, "resident_spin_limit": 5, "uvt_target_wgs": 9, "uvt_min_stages": 10,

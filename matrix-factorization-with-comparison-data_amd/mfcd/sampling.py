@@ -14,10 +14,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import cluster as _cluster
 from . import topk as _topk
 
-LAW_UNIFORM, LAW_ITEM_CDF, LAW_LISTS = 0, 1, 2
-DEVICE_STRATEGIES = ("random", "margin", "popularity", "variance", "proximity", "top_k", "svd")
+LAW_UNIFORM, LAW_ITEM_CDF, LAW_LISTS, LAW_GROUPS = 0, 1, 2, 3
+DEVICE_STRATEGIES = ("random", "margin", "popularity", "variance", "proximity", "top_k", "svd", "cluster")
 
 
 def _dense_on(X, device):
@@ -41,9 +42,27 @@ class _Law:
         return _lib.ptr(t)
 
 
-def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha=1.5, k=None, max_attempts=5_000_000):
+def group_tables(labels, k):
+    """The tables of the groups law from one label per item → (members int32 [m]: the item ids grouped by label,
+    ascending inside a group; offsets int32 [k + 1] into them), on the labels' device.  ValueError for a label outside
+    [0, k) and for a group without items (numpy's choice on an empty array raises there, generation_data.py:242)."""
+    lab = torch.as_tensor(labels).reshape(-1).long()
+    k = int(k)
+    if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= k):
+        raise ValueError(f"label outside [0, {k})")
+    counts = torch.bincount(lab, minlength=k)
+    if k < 1 or int(counts.min()) == 0:
+        raise ValueError(f"cluster {int(counts.argmin()) if k >= 1 else 0} of {k} has no items: 'a' cannot be empty")
+    members = torch.sort(lab, stable=True)[1].to(torch.int32).contiguous()
+    offsets = torch.zeros(k + 1, dtype=torch.int32, device=lab.device)
+    offsets[1:] = torch.cumsum(counts, 0)
+    return members, offsets
+
+
+def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha=1.5, k=None, max_attempts=5_000_000,
+              n_clusters=10, seed=0):
     """The reference's per-strategy set-up (everything in front of its attempt loop, as generation_data defines it) → a
-    device law."""
+    device law.  `seed`: the request's seed, for a set-up that draws (the k-means++ of `cluster`)."""
     import generation_data as _gd
     n, m = X.shape
     law = _Law(n, m, device)
@@ -66,7 +85,8 @@ def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha
             probs = _gd._popularity_probs(m, popularity_method, alpha)
             c.pair_rule = 0
         else:                                                            # generation_data.py:90-91
-            var = torch.var(_dense_on(X, device), dim=0).double().cpu().numpy()
+            var = _gd._factored_column_variances(X).numpy() if _lib.is_factored(X) else \
+                torch.var(_dense_on(X, device), dim=0).double().cpu().numpy()
             probs = var / var.sum()
             c.pair_rule = 1
             if not np.isfinite(probs).all() or (probs < 0).any():      # e.g. one user: the unbiased variance is NaN
@@ -108,6 +128,15 @@ def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha
         c.users, c.n_users = law.hold(torch.from_numpy(top_users.astype(np.int32)).to(device)), int(top_users.size)
         law.budget = 5 * int(num_triplets)
         law.report = lambda got, attempts: _gd._report_short(got, num_triplets)
+        return law
+    if strategy == "cluster":                                           # generation_data.py:229-239
+        kk = int(n_clusters)
+        if kk < 2:
+            raise ValueError("Cannot take a larger sample than population when 'replace=False'")   # numpy's (ref:241)
+        labels = _cluster.kmeans(_cluster.item_points(X, device), kk, (int(seed) ^ 0x6B6D65616E73) & (2 ** 63 - 1))[0]
+        members, offsets = group_tables(labels, kk)
+        c.law, c.k, c.list_row_stride = LAW_GROUPS, kk, int(members.numel())
+        c.list_i, c.list_j = law.hold(members), law.hold(offsets)
         return law
     raise ValueError(f"no device law for triplet sampling strategy: {strategy}")
 
@@ -175,7 +204,7 @@ def sample_triplets(X, num_triplets, strategy="random", exclude=None, device=Non
         device = torch.device("cuda", torch.cuda.current_device())
     if seed is None:
         seed = int(torch.empty((), dtype=torch.int64).random_().item())
-    law = build_law(X, int(num_triplets), strategy, device, **kw)
+    law = build_law(X, int(num_triplets), strategy, device, seed=seed, **kw)
     trip, attempts = run_law(law, num_triplets, exclude, seed)
     law.report(trip.shape[0], attempts)
     return trip

@@ -302,11 +302,14 @@ _SAMPLER_DEVICE = None
 
 def set_sampler_device(device):
     """Extension (not in the reference): draw triplets ON `device` (a GPU; include/mfcd.h mfcd_sample_triplets) from now
-    on for the strategies that have a device law (random, margin, popularity, variance, proximity, top_k, svd); the
-    others (cluster, user_similarity — "Not used" in the reference's own comments) and None (default) use the host
-    samplers, which consume torch's / numpy's generators exactly like the reference.  A `FactoredMatrix` ground truth
-    is taken by random, margin, popularity, proximity and top_k (the last two read their per-user lists from
-    mfcd_topk_rows over the factors; a dense X keeps torch.topk and its tie order)."""
+    on for the strategies that have a device law (random, margin, popularity, variance, proximity, top_k, svd, cluster);
+    user_similarity ("Not used" in the reference's own comments) and None (default) use the host samplers, which consume
+    torch's / numpy's generators exactly like the reference.  `cluster` runs k-means on the device (mfcd/cluster.py:
+    k-means++ seeded from the request's seed, Lloyd steps in HIP) where the host form calls sklearn's KMeans: the same
+    law per attempt given a partition, but the partition is not sklearn's where k-means has several optima.  A
+    `FactoredMatrix` ground truth is taken by random, margin, popularity, variance, proximity, top_k and cluster
+    (proximity / top_k read their per-user lists from mfcd_topk_rows over the factors, variance and cluster work from
+    the factors' d x d Gram forms; a dense X keeps torch.topk / torch.var and their tie order)."""
     global _SAMPLER_DEVICE
     if device is not None:
         _need_gpu(device)
@@ -319,7 +322,8 @@ def get_triplets_from_X(X, num_triplets, strategy="random", exclude=None, popula
     if strategy not in _STRATEGIES:
         raise ValueError(f"Unknown triplet sampling strategy: {strategy}")
     if _SAMPLER_DEVICE is not None and strategy in _sampling.DEVICE_STRATEGIES:
-        kw = dict(popularity_method=popularity_method, alpha=alpha) if strategy == "popularity" else {}
+        kw = dict(popularity_method=popularity_method, alpha=alpha) if strategy == "popularity" else \
+            dict(n_clusters=n_clusters) if strategy == "cluster" else {}
         rows = _sampling.sample_triplets(X, num_triplets, strategy, exclude, device=_SAMPLER_DEVICE, **kw).cpu().numpy()
         return set(zip(rows[:, 0].tolist(), rows[:, 1].tolist(), rows[:, 2].tolist()))
     found = _STRATEGIES[strategy](X, num_triplets, exclude or set(), popularity_method=popularity_method,
