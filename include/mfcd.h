@@ -648,6 +648,41 @@ int mfcd_kmeans_assign(const float *points, int64_t P, int64_t dim, const float 
 int mfcd_kmeans_update(const float *points, int64_t P, int64_t dim, const int32_t *labels, int k, float *centres,
                        int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Exact all-pairs statistics of score rows against ground-truth rows (no reference counterpart: the reference estimates
+ * the test loss and accuracy of a model from a split of a few hundred sampled triplets, structure.py:369-390; these are
+ * the population values those estimate, with the exact Kendall counts from the same pass).  Row r of A [rows][lda] holds
+ * model scores a (the caller forms rows of U V^T with a plain library GEMM), row r of X [rows][ldx] the ground truth x,
+ * m columns each, fp32, rows may be strided.  Everything is over the n0 = m (m - 1) / 2 unordered pairs i < j of a row.
+ *   what     1 counts only, 2 sums only, 3 both; outputs are per row
+ *   counts   [rows][4] int64, exact: C concordant ((a_i < a_j and x_i < x_j) or (a_i > a_j and x_i > x_j)), D discordant,
+ *            Ta pairs with a_i == a_j, Tx pairs with x_i == x_j (a pair tied in both rows is in Ta and in Tx).  Decided by
+ *            comparing the values themselves, never by the sign of a difference or of a product; -0.0 equals +0.0, +-inf
+ *            compare as numbers; a NaN anywhere in either row sets the row's four counts to -1.  Kendall's
+ *            tau-b = (C - D) / sqrt((n0 - Ta)(n0 - Tx)), pairwise accuracy = C / (n0 - Tx).
+ *   sums     [rows][4] f64, with da = a_i - a_j, t = scale (x_i - x_j), q = sigmoid(t),
+ *            softplus(v) = max(v, 0) + log1p(exp(-|v|)):
+ *              risk        softplus(da) - q da: the BCE of p = sigmoid(da) against the label law q, unclamped (ATen clamps
+ *                          the logs at -100, which differs only for |da| > 100)
+ *              bayes_risk  softplus(t) - q t
+ *              exp_acc     q if a_i > a_j, 1 - q if a_i < a_j, 0.5 if equal: the expectation of (p > 0.5) == z over hard
+ *                          labels z and both orders of the pair
+ *              bayes_acc   max(q, 1 - q)
+ *            Per-pair arithmetic is fp32 (hardware exp / log / reciprocal, arranged so that no term cancels), at most
+ *            64 terms are added in fp32 before widening, the rest is f64.  Any non-finite entry in either row makes
+ *            the row's four sums NaN (the counts still follow their own rule).
+ * One 256-thread workgroup per (row, tile of 1024 columns) visits the tile's pairs with itself and every later tile and
+ * writes one fixed-size partial; a finishing kernel adds a row's partials in a fixed order.  No floating-point atomics:
+ * two calls are bit-equal, and what = 1 / what = 2 are bit-equal to the matching half of what = 3.
+ * Limits: rows >= 0 (0 = success, nothing launched), 1 <= m <= 1 048 576, lda, ldx >= m, what in {1, 2, 3}, scale finite;
+ * MFCD_EINVAL outside them, a missing output of a requested `what` included, before anything touches the device.
+ * workspace: as the workspace_bytes entry says (80 bytes per (row, tile), at most 80 MiB: longer inputs go through in
+ * blocks of rows; 0 = sizes out of range), 256-byte aligned.  No allocation and no host wait.
+ */
+size_t mfcd_pair_stats_workspace_bytes(int rows, int m);
+int mfcd_pair_stats_rows(const float *A, int64_t lda, const float *X, int64_t ldx, int rows, int m, double scale, int what,
+                         int64_t *counts, double *sums, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,287 @@
+// pairs.hip — exact all-pairs statistics of a score row against a ground-truth row on gfx950.
+//
+// For row r of A (model scores a) and row r of X (ground truth x), over the n0 = m (m - 1) / 2 unordered pairs i < j:
+//   counts  C, D, Ta, Tx — concordant, discordant, tied in a, tied in x — as exact integers: every decision is a plain
+//           comparison of the two values themselves (never the sign of a difference or of a product), every sum an
+//           integer sum.  Kendall's tau-b and the pairwise accuracy are functions of these four numbers.
+//   sums    of the BTL population risk softplus(da) - q da, its Bayes floor softplus(t) - q t, the expected accuracy and
+//           its Bayes ceiling, with da = a_i - a_j, t = scale (x_i - x_j), q = sigmoid(t).  Per-pair arithmetic is fp32;
+//           a thread adds at most 64 terms in fp32 before it widens to f64 (a run of equal terms, which a row of few
+//           levels produces, rounds the same way every time: the bound on that drift is 64 half-ulps, 2e-6 relative).
+// There is no sort and no shortcut: the risk is not a function of the ranks, so all pairs are visited, and the counts
+// ride in the same pass.
+//
+// One workgroup of 256 threads per (row, tile I) of kPairTile = 1024 columns.  Tile I sits in registers, four (a, x)
+// elements per thread (element k of thread t is column 1024 I + 256 k + t: coalesced loads); the tiles J >= I stream
+// through 8 KiB of LDS and every lane reads the same (a_j, x_j) — a broadcast, conflict-free.  Tiles J > I need no
+// mask.  The diagonal tile is walked in four runs of 256 columns: in run c the elements k < c of every thread pair
+// with all of the run, element k == c is masked to i < j, elements k > c are skipped (6 + 4/2 of 16 sub-blocks do work
+// that counts, instead of all 16 under a mask).
+//
+// Per pair the sums take five transcendentals — exp(-|da|), exp(-|t|), two logs of 1 + e, one reciprocal — and are
+// written so that nothing cancels: with e = exp(-|t|), q_hi = 1 / (1 + e) and q_lo = e q_hi are sigmoid(|t|) and
+// sigmoid(-|t|), so q and 1 - q are both selected, never subtracted, and
+//   softplus(da) - q da = log1p(exp(-|da|)) + |da| (da > 0 ? 1 - q : q),   softplus(t) - q t = log1p(e) + |t| q_lo.
+// Which of q_hi, q_lo is selected depends on one bit, whether the scores order the pair against the side the label
+// law leans to.  The logs are taken in base 2 (the hardware's) and summed apart from the linear parts; ln 2 is applied
+// once per workgroup, in f64.  Only exp of a non-positive argument is taken, so no row range overflows and there is
+// no second formulation.
+//
+// Counters: a thread meets at most 4 m <= 2^22 pairs in a launch, so 32-bit per-thread counters cannot wrap; they are
+// widened to 64 bits once, for the workgroup's sum.  No floating-point atomics: every workgroup writes one fixed-size
+// partial per (row, tile I) into the workspace, and a one-wave finishing kernel per row adds the partials in a fixed
+// order.  Two calls are therefore bit-equal, and the counts-only and sums-only kernels execute the same operations in
+// the same order as the matching half of the combined kernel.
+#include <cmath>
+
+#include "common.h"
+
+namespace {
+
+constexpr int kPairThreads = 256;
+constexpr int kPairIpt = 4;                            // elements of tile I per thread
+constexpr int kPairTile = kPairThreads * kPairIpt;     // 1024 columns (mfcd/pairs.py: TILE)
+constexpr int kPairFlush = 16;                         // columns between two widenings of the fp32 sums to f64
+constexpr int kPairMaxCols = 1 << 20;
+constexpr int64_t kPairMaxBlocks = 1 << 20;            // (row, tile) workgroups per launch: bounds the workspace at 80 MiB
+
+struct PairPartial {
+    long long c[4];     // C, D, pairs strictly ordered in a, in x, of this (row, tile I)
+    long long bad[2];   // NaN entries, non-finite entries (NaN included) among tile I's elements
+    double s[4];        // risk, bayes_risk, exp_acc, bayes_acc
+};
+static_assert(sizeof(PairPartial) == 80, "workspace layout");
+
+inline int pair_tiles(int m) { return (m + kPairTile - 1) / kPairTile; }
+inline int pair_chunk_rows(int rows, int T)
+{
+    const int64_t R = kPairMaxBlocks / T;              // >= 1024
+    return (int)(rows < R ? rows : R);
+}
+
+// One pair.  f: the run's fp32 accumulators — log2(1 + e) and the linear part of the two risks apart (ln 2 is applied
+// once, in f64), exp_acc, bayes_acc.
+template <int WHAT, bool MASKED>
+__device__ __forceinline__ void pair_term(float ai, float xi, float aj, float xj, bool valid, float scale,
+                                          unsigned (&cnt)[4], float (&f)[6])
+{
+    const bool la = ai < aj, ga = ai > aj, lx = xi < xj, gx = xi > xj;
+    const bool v = !MASKED || valid;
+    if (WHAT & 1) {                                    // comparison masks combine on the scalar unit
+        cnt[0] += (unsigned)(v && ((la && lx) || (ga && gx)));
+        cnt[1] += (unsigned)(v && ((la && gx) || (ga && lx)));
+        cnt[2] += (unsigned)(v && (la || ga));         // strictly ordered in a: Ta = n0 - this, in the finishing kernel
+        cnt[3] += (unsigned)(v && (lx || gx));         // (a row with a NaN is voided there)
+    }
+    if (WHAT & 2) {
+        const float da = ai - aj, t = scale * (xi - xj);
+        const float ada = v ? fabsf(da) : 0.0f, at = v ? fabsf(t) : 0.0f;
+        const float ea = __builtin_amdgcn_exp2f(-1.4426950408889634f * ada);       // exp(-|da|): v_exp_f32
+        const float et = __builtin_amdgcn_exp2f(-1.4426950408889634f * at);
+        const float l2a = __builtin_amdgcn_logf(1.0f + ea), l2t = __builtin_amdgcn_logf(1.0f + et);   // v_log_f32: log2
+        const float qhi = __builtin_amdgcn_rcpf(1.0f + et), qlo = et * qhi;       // sigmoid(|t|), sigmoid(-|t|)
+        // the scores order the pair against the side the label law leans to: then 1 - q (for da > 0) or q (da < 0) is
+        // q_hi and the pair is right with probability q_lo; otherwise the other way round
+        const bool against = ga != (t >= 0.0f);
+        const float miss = against ? qhi : qlo, hit = against ? qlo : qhi;
+        const float eacc = (ga || la) ? hit : 0.5f;
+        f[0] += v ? l2a : 0.0f;
+        f[1] = fmaf(ada, miss, f[1]);
+        f[2] += v ? l2t : 0.0f;
+        f[3] = fmaf(at, qlo, f[3]);
+        f[4] += v ? eacc : 0.0f;
+        f[5] += v ? qhi : 0.0f;
+    }
+}
+
+// Columns [j0, j1) of the LDS tile against this thread's elements: k < KFULL unmasked, k == KMASK (the run of the
+// diagonal tile that holds element k itself, first column j0) only where the element's column is below j.
+template <int WHAT, int KFULL, int KMASK>
+__device__ __forceinline__ void pair_run(const float2 *tile, int j0, int j1, const float (&ai)[kPairIpt],
+                                         const float (&xi)[kPairIpt], int tid, float scale, unsigned (&cnt)[4],
+                                         double (&acc)[6])
+{
+    for (int jb = j0; jb < j1; jb += kPairFlush) {
+        const int je = jb + kPairFlush < j1 ? jb + kPairFlush : j1;
+        float f[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // at most kPairFlush columns x 4 elements = 64 terms each
+#pragma unroll 4
+        for (int j = jb; j < je; ++j) {
+            const float2 v = tile[j];
+#pragma unroll
+            for (int k = 0; k < kPairIpt; ++k) {
+                if (k < KFULL) pair_term<WHAT, false>(ai[k], xi[k], v.x, v.y, true, scale, cnt, f);
+                else if (k == KMASK) pair_term<WHAT, true>(ai[k], xi[k], v.x, v.y, tid < j - j0, scale, cnt, f);
+            }
+        }
+        if (WHAT & 2) {
+#pragma unroll
+            for (int q = 0; q < 6; ++q) acc[q] += (double)f[q];
+        }
+    }
+}
+
+template <typename V>
+__device__ __forceinline__ V pair_wave_sum(V v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, MFCD_WAVE);
+    return v;
+}
+
+template <int WHAT>
+__global__ __launch_bounds__(kPairThreads) void pair_tiles_kernel(const float *__restrict__ A, int64_t lda,
+                                                                  const float *__restrict__ X, int64_t ldx, int m, int T,
+                                                                  float scale, PairPartial *__restrict__ part)
+{
+    __shared__ float2 tile[kPairTile];
+    __shared__ long long red_c[kPairThreads / 64][6];
+    __shared__ double red_s[kPairThreads / 64][6];
+    const int tid = threadIdx.x;
+    const int64_t r = blockIdx.x / T;
+    const int I = (int)(blockIdx.x - r * T);
+    const float *a = A + r * lda, *x = X + r * ldx;
+
+    float ai[kPairIpt], xi[kPairIpt];
+    unsigned n_nan = 0, n_inf = 0;
+#pragma unroll
+    for (int k = 0; k < kPairIpt; ++k) {
+        const int p = I * kPairTile + k * kPairThreads + tid;
+        ai[k] = 0.0f;
+        xi[k] = 0.0f;
+        if (p < m) {
+            ai[k] = a[p];
+            xi[k] = x[p];
+            n_nan += (unsigned)(ai[k] != ai[k] || xi[k] != xi[k]);
+            n_inf += (unsigned)((__float_as_uint(ai[k]) & 0x7f800000u) == 0x7f800000u ||
+                                (__float_as_uint(xi[k]) & 0x7f800000u) == 0x7f800000u);
+        }
+    }
+
+    unsigned cnt[4] = {0u, 0u, 0u, 0u};                // <= 4 m <= 2^22 pairs per thread
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int J = I; J < T; ++J) {
+        __syncthreads();                               // the previous tile's readers are done
+#pragma unroll
+        for (int k = 0; k < kPairIpt; ++k) {
+            const int e = k * kPairThreads + tid, p = J * kPairTile + e;
+            float2 v = make_float2(ai[k], xi[k]);      // J == I: the tile is this workgroup's own elements
+            if (J != I) v = p < m ? make_float2(a[p], x[p]) : make_float2(0.0f, 0.0f);
+            tile[e] = v;
+        }
+        __syncthreads();
+        const int jn = m - J * kPairTile < kPairTile ? m - J * kPairTile : kPairTile;   // columns of tile J that exist
+        const auto end = [jn](int j1) { return j1 < jn ? j1 : jn; };
+        if (J != I) {
+            for (int c = 0; c < kPairIpt; ++c)
+                pair_run<WHAT, kPairIpt, kPairIpt>(tile, c * kPairThreads, end((c + 1) * kPairThreads), ai, xi, tid, scale,
+                                                   cnt, acc);
+        } else {                                       // an element past m only meets columns past m: j < jn bars both
+            pair_run<WHAT, 0, 0>(tile, 0, end(256), ai, xi, tid, scale, cnt, acc);
+            pair_run<WHAT, 1, 1>(tile, 256, end(512), ai, xi, tid, scale, cnt, acc);
+            pair_run<WHAT, 2, 2>(tile, 512, end(768), ai, xi, tid, scale, cnt, acc);
+            pair_run<WHAT, 3, 3>(tile, 768, end(1024), ai, xi, tid, scale, cnt, acc);
+        }
+    }
+
+    long long c6[6] = {(long long)cnt[0], (long long)cnt[1], (long long)cnt[2], (long long)cnt[3], (long long)n_nan,
+                       (long long)n_inf};
+#pragma unroll
+    for (int q = 0; q < 6; ++q) c6[q] = pair_wave_sum(c6[q]);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) acc[q] = pair_wave_sum(acc[q]);
+    if ((tid & 63) == 0) {
+        for (int q = 0; q < 6; ++q) red_c[tid >> 6][q] = c6[q];
+        for (int q = 0; q < 6; ++q) red_s[tid >> 6][q] = acc[q];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        PairPartial out;
+        for (int q = 0; q < 6; ++q) {
+            long long v = 0;
+            for (int w = 0; w < kPairThreads / 64; ++w) v += red_c[w][q];
+            if (q < 4) out.c[q] = v;
+            else out.bad[q - 4] = v;
+        }
+        double s6[6];
+        for (int q = 0; q < 6; ++q) {
+            s6[q] = 0.0;
+            for (int w = 0; w < kPairThreads / 64; ++w) s6[q] += red_s[w][q];   // fixed order
+        }
+        out.s[0] = 0.6931471805599453 * s6[0] + s6[1];
+        out.s[1] = 0.6931471805599453 * s6[2] + s6[3];
+        out.s[2] = s6[4];
+        out.s[3] = s6[5];
+        part[blockIdx.x] = out;
+    }
+}
+
+// One wave per row: lane l adds the partials of tiles l, l + 64, ... in order, then the lanes are added in a fixed tree.
+__global__ __launch_bounds__(64) void pair_finish_kernel(const PairPartial *__restrict__ part, int T, long long n0, int what,
+                                                         int64_t *__restrict__ counts, double *__restrict__ sums)
+{
+    const int64_t r = blockIdx.x;
+    long long c6[6] = {0, 0, 0, 0, 0, 0};
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int I = threadIdx.x; I < T; I += 64) {
+        const PairPartial &p = part[r * T + I];
+        for (int q = 0; q < 4; ++q) c6[q] += p.c[q];
+        c6[4] += p.bad[0];
+        c6[5] += p.bad[1];
+        for (int q = 0; q < 4; ++q) s[q] += p.s[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) c6[q] = pair_wave_sum(c6[q]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q] = pair_wave_sum(s[q]);
+    if (threadIdx.x == 0) {
+        if (what & 1)
+            for (int q = 0; q < 4; ++q) counts[r * 4 + q] = c6[4] ? -1 : q < 2 ? c6[q] : n0 - c6[q];
+        if (what & 2)
+            for (int q = 0; q < 4; ++q) sums[r * 4 + q] = c6[5] ? __longlong_as_double(0x7ff8000000000000ll) : s[q];
+    }
+}
+
+template <int WHAT>
+void pair_launch(const float *A, int64_t lda, const float *X, int64_t ldx, int nr, int m, int T, float scale,
+                 PairPartial *part, hipStream_t st)
+{
+    hipLaunchKernelGGL(pair_tiles_kernel<WHAT>, dim3((unsigned)((int64_t)nr * T)), dim3(kPairThreads), 0, st, A, lda, X,
+                       ldx, m, T, scale, part);
+}
+
+}  // namespace
+
+extern "C" size_t mfcd_pair_stats_workspace_bytes(int rows, int m)
+{
+    if (rows < 0 || m < 1 || m > kPairMaxCols) return 0;
+    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
+    return align_up((size_t)(R > 0 ? R : 1) * T * sizeof(PairPartial));
+}
+
+extern "C" int mfcd_pair_stats_rows(const float *A, int64_t lda, const float *X, int64_t ldx, int rows, int m,
+                                    double scale, int what, int64_t *counts, double *sums, void *workspace,
+                                    size_t workspace_bytes, void *stream)
+{
+    if (!A || !X || rows < 0 || m < 1 || m > kPairMaxCols || lda < m || ldx < m) return MFCD_EINVAL;
+    if (what < 1 || what > 3 || ((what & 1) && !counts) || ((what & 2) && !sums)) return MFCD_EINVAL;
+    if (!std::isfinite(scale) || !std::isfinite((float)scale)) return MFCD_EINVAL;
+    if (rows == 0) return 0;
+    if (!workspace) return MFCD_EINVAL;
+    if (workspace_bytes < mfcd_pair_stats_workspace_bytes(rows, m)) return MFCD_EWORKSPACE;
+    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
+    PairPartial *part = (PairPartial *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    for (int r0 = 0; r0 < rows; r0 += R) {             // stream order keeps one chunk's partials apart from the next's
+        const int nr = rows - r0 < R ? rows - r0 : R;
+        const float *a = A + (int64_t)r0 * lda, *x = X + (int64_t)r0 * ldx;
+        if (what == 1) pair_launch<1>(a, lda, x, ldx, nr, m, T, (float)scale, part, st);
+        else if (what == 2) pair_launch<2>(a, lda, x, ldx, nr, m, T, (float)scale, part, st);
+        else pair_launch<3>(a, lda, x, ldx, nr, m, T, (float)scale, part, st);
+        MFCD_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(pair_finish_kernel, dim3((unsigned)nr), dim3(64), 0, st, part, T,
+                           (long long)m * (m - 1) / 2, what,
+                           counts ? counts + (int64_t)r0 * 4 : nullptr, sums ? sums + (int64_t)r0 * 4 : nullptr);
+        MFCD_HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}

@@ -5,7 +5,8 @@
 `engine`   fused training epochs / evaluation on the device, in place on the caller's model + Adam.
 `metrics`  dense UV^T reconstruction / alignment metrics from the MFMA pass.
 `topk`     the k best / worst columns of rows of a dense or factored score matrix (mfcd_topk_rows).
+`pairs`    exact all-pairs BTL risk, pairwise accuracy and Kendall counts per row (mfcd_pair_stats_rows).
 """
-from . import _lib, batching, engine, metrics, topk  # noqa: F401
+from . import _lib, batching, engine, metrics, pairs, topk  # noqa: F401
 
-__all__ = ["_lib", "batching", "engine", "metrics", "topk"]
+__all__ = ["_lib", "batching", "engine", "metrics", "pairs", "topk"]

@@ -22,6 +22,7 @@ from generation_data import *  # noqa: F401,F403  (ref:17 re-exports every sampl
 import generation_data as _gd
 from mfcd import engine as _engine
 from mfcd import metrics as _metrics
+from mfcd import pairs as _pairs
 from mfcd import sampling as _sampling
 from mfcd import topk as _topk
 
@@ -146,6 +147,26 @@ def compute_topk_overlap(model, X, k=10):
     hit = torch.isin((mine + row).reshape(-1), (theirs + row).reshape(-1)).reshape(mine.shape)
     per_user = (hit.sum(1).double() / k).cpu().numpy()
     return float(per_user.mean()), per_user
+
+
+def compute_pairwise_metrics(model, X, s=1.0, users=None, row_block=2048):
+    """Extension (not in the reference): what the sampled test split estimates, computed exactly over ALL item pairs
+    i < j of a user (include/mfcd.h mfcd_pair_stats_rows), with the model's score row a = U[u] V^T, the ground truth
+    x = X[u] and the label law q = sigmoid(s (x_i - x_j)).  Returns a dict; every key also exists with the suffix
+    `_per_user` as a float64 numpy array holding NaN where the value is undefined, and the plain key is the mean over the
+    users where it is defined (0.0 if there are none, as the Spearman mean):
+      kendall_tau              Kendall's tau-b of a and x from the exact pair counts (NaN: a constant row, or a NaN in it)
+      pairwise_accuracy        share of the pairs that x orders which a orders the same way
+      expected_log_likelihood  minus the mean of q (-log p) + (1 - q)(-log(1 - p)), p = sigmoid(a_i - a_j): the expected
+                               value of the result dict's `log_likelihoods` over all pairs, unclamped
+      bayes_log_likelihood     the same for the ideal scores a = s x: no model can exceed it
+      expected_accuracy        expected accuracy of (p > 0.5) against hard labels drawn from q
+      bayes_accuracy           mean of max(q, 1 - q): its ceiling
+    X: a dense GPU tensor or a `FactoredMatrix` (rows are formed `row_block` at a time; nothing n x m is formed for a
+    factored X).  users: None = every user, else user numbers, returned in that order — the cost is O(m^2) per user, so
+    pass a sample at BASELINE C4 / C5 sizes.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _pairs.pairwise_metrics(model.U.data, model.V.data, X, s, users, row_block)
 
 
 def compute_ground_truth_metrics(test_loader, X, device):
