@@ -683,6 +683,26 @@ size_t mfcd_pair_stats_workspace_bytes(int rows, int m);
 int mfcd_pair_stats_rows(const float *A, int64_t lda, const float *X, int64_t ldx, int rows, int m, double scale, int what,
                          int64_t *counts, double *sums, void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * The gradient of the `risk` sum above with respect to the scores (no reference counterpart: the reference descends the
+ * BCE of sampled triplets, structure.py:845-852; this is the gradient of the population risk those samples estimate).
+ * Row r of G [rows][ldg] receives, for every column i < m,
+ *     g_i = sum over j != i of  sigmoid(a_i - a_j) - sigmoid(scale (x_i - x_j)),
+ * the derivative of sums[r][0] of mfcd_pair_stats_rows with respect to a_i; columns >= m of G are not written.
+ * One 256-thread workgroup per (row, tile of 1024 columns) visits the tile's pairs with EVERY tile of the row, so each
+ * thread owns its sums and stores them itself (each unordered pair is visited twice; there is no workspace, no
+ * finishing kernel and no atomic).  Per-pair arithmetic is fp32 on the hardware exp and reciprocal, with only exp of a
+ * non-positive argument taken and sigmoid(|v|) = 1 / (1 + e), sigmoid(-|v|) = e / (1 + e) selected by the sign, so no
+ * finite row overflows; an accumulator adds at most 64 terms in fp32 before it is widened to f64, and g_i is rounded to
+ * fp32 once, on the store.  A row with a non-finite entry in A or X gets an all-NaN row of G.  Two calls are bit-equal,
+ * and a row's result does not depend on the other rows of the call or on lda, ldx, ldg.
+ * Limits: rows >= 0 (0 = success, nothing launched), 1 <= m <= 1 048 576, lda, ldx, ldg >= m, scale finite (as a float
+ * too), G neither A nor X; MFCD_EINVAL outside them, before anything touches the device.  Long inputs go through in
+ * blocks of rows.  No allocation and no host wait.
+ */
+int mfcd_pair_grad_rows(const float *A, int64_t lda, const float *X, int64_t ldx, int rows, int m, double scale, float *G,
+                        int64_t ldg, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,83 @@ void pair_launch(const float *A, int64_t lda, const float *X, int64_t ldx, int n
                        ldx, m, T, scale, part);
 }
 
+// ---- the gradient of a row's risk sum (follow-on) ----
+// g_i = sum over j != i of sigmoid(a_i - a_j) - sigmoid(scale (x_i - x_j)): the derivative of the `risk` sum above with
+// respect to a_i.  Same decomposition as pair_tiles_kernel — one workgroup per (row, tile I), four elements per thread
+// in registers, tiles streamed through LDS and read as a broadcast — but EVERY tile J is visited, so a thread owns its
+// four sums completely and stores them itself: no scatter to the j side, no workspace, no finishing kernel, no atomics,
+// at the price of visiting each unordered pair twice.
+constexpr int kGradFlush = 64;                         // columns, = terms per accumulator, between two widenings to f64
+
+// sigmoid(v) from exp of a non-positive argument only: sigmoid(|v|) = 1 / (1 + e), sigmoid(-|v|) = e / (1 + e), selected
+// by the sign, never formed as 1 - sigmoid.  v = +-0 gives the same value for either sign.
+__device__ __forceinline__ float pair_sigmoid(float v)
+{
+    const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * fabsf(v));       // exp(-|v|) <= 1: v_exp_f32
+    const float hi = __builtin_amdgcn_rcpf(1.0f + e);
+    return v >= 0.0f ? hi : e * hi;
+}
+
+__device__ __forceinline__ bool pair_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+__global__ __launch_bounds__(kPairThreads) void pair_grad_kernel(const float *__restrict__ A, int64_t lda,
+                                                                 const float *__restrict__ X, int64_t ldx, int m, int T,
+                                                                 float scale, float *__restrict__ G, int64_t ldg)
+{
+    __shared__ float2 tile[kPairTile];
+    const int tid = threadIdx.x;
+    const int64_t r = blockIdx.x / T;
+    const int I = (int)(blockIdx.x - r * T);
+    const float *a = A + r * lda, *x = X + r * ldx;
+
+    float ai[kPairIpt], xi[kPairIpt];
+#pragma unroll
+    for (int k = 0; k < kPairIpt; ++k) {
+        const int p = I * kPairTile + k * kPairThreads + tid;
+        ai[k] = p < m ? a[p] : 0.0f;                   // an element past m is computed and never stored
+        xi[k] = p < m ? x[p] : 0.0f;
+    }
+
+    int bad = 0;                                       // the workgroup stages the whole row: it sees every entry
+    double acc[kPairIpt] = {0.0, 0.0, 0.0, 0.0};
+    for (int J = 0; J < T; ++J) {
+        __syncthreads();                               // the previous tile's readers are done
+#pragma unroll
+        for (int k = 0; k < kPairIpt; ++k) {
+            const int e = k * kPairThreads + tid, p = J * kPairTile + e;
+            const float2 v = p < m ? make_float2(a[p], x[p]) : make_float2(0.0f, 0.0f);
+            bad |= (int)(pair_nonfinite(v.x) || pair_nonfinite(v.y));
+            tile[e] = v;
+        }
+        __syncthreads();
+        // columns of tile J that exist: a zero-filled pad column would be a real term here.  The column j == i needs no
+        // mask: both differences are +-0 there, both sigmoids run the same instructions on the same e, and the term is
+        // exactly 0.
+        const int jn = m - J * kPairTile < kPairTile ? m - J * kPairTile : kPairTile;
+        for (int jb = 0; jb < jn; jb += kGradFlush) {
+            const int je = jb + kGradFlush < jn ? jb + kGradFlush : jn;
+            float f[kPairIpt] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 4
+            for (int j = jb; j < je; ++j) {
+                const float2 v = tile[j];
+#pragma unroll
+                for (int k = 0; k < kPairIpt; ++k)
+                    f[k] += pair_sigmoid(ai[k] - v.x) - pair_sigmoid(scale * (xi[k] - v.y));
+            }
+#pragma unroll
+            for (int k = 0; k < kPairIpt; ++k) acc[k] += (double)f[k];
+        }
+    }
+
+    bad = __syncthreads_or(bad);
+    float *g = G + r * ldg;
+#pragma unroll
+    for (int k = 0; k < kPairIpt; ++k) {
+        const int p = I * kPairTile + k * kPairThreads + tid;
+        if (p < m) g[p] = bad ? __uint_as_float(0x7fc00000u) : (float)acc[k];     // rounded to fp32 once
+    }
+}
+
 }  // namespace
 
 extern "C" size_t mfcd_pair_stats_workspace_bytes(int rows, int m)
@@ -281,6 +358,24 @@ extern "C" int mfcd_pair_stats_rows(const float *A, int64_t lda, const float *X,
         hipLaunchKernelGGL(pair_finish_kernel, dim3((unsigned)nr), dim3(64), 0, st, part, T,
                            (long long)m * (m - 1) / 2, what,
                            counts ? counts + (int64_t)r0 * 4 : nullptr, sums ? sums + (int64_t)r0 * 4 : nullptr);
+        MFCD_HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int mfcd_pair_grad_rows(const float *A, int64_t lda, const float *X, int64_t ldx, int rows, int m, double scale,
+                                   float *G, int64_t ldg, void *stream)
+{
+    if (!A || !X || !G || rows < 0 || m < 1 || m > kPairMaxCols || lda < m || ldx < m || ldg < m) return MFCD_EINVAL;
+    if (G == A || G == X) return MFCD_EINVAL;
+    if (!std::isfinite(scale) || !std::isfinite((float)scale)) return MFCD_EINVAL;
+    if (rows == 0) return 0;
+    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
+    for (int r0 = 0; r0 < rows; r0 += R) {
+        const int nr = rows - r0 < R ? rows - r0 : R;
+        hipLaunchKernelGGL(pair_grad_kernel, dim3((unsigned)((int64_t)nr * T)), dim3(kPairThreads), 0, (hipStream_t)stream,
+                           A + (int64_t)r0 * lda, lda, X + (int64_t)r0 * ldx, ldx, m, T, (float)scale,
+                           G + (int64_t)r0 * ldg, ldg);
         MFCD_HIP_TRY(hipGetLastError());
     }
     return 0;

@@ -4,7 +4,11 @@ Bayes floor, the expected accuracy and its Bayes ceiling over the m (m - 1) / 2 
 
 `pair_stats_rows` is the kernel call; `pairwise_from_counts` turns its outputs into per-row values on the host (f64);
 `pairwise_metrics` forms the score rows of a model block by block and is what structure.compute_pairwise_metrics
-returns.  There is no CPU form.
+returns.
+
+The risk can also be minimised: `pair_grad_rows` (mfcd_pair_grad_rows) is its gradient with respect to the score rows,
+`population_risk` the mean risk as a differentiable scalar of the factor tables, `fit_population` the fused loop of
+risk gradient and Adam step.  There is no CPU form of any of it.
 """
 import numpy as np
 import torch
@@ -53,6 +57,28 @@ def pair_stats_rows(A, X, scale=1.0, what="both"):
     return counts, sums
 
 
+def pair_grad_rows(A, X, scale=1.0):
+    """Two [rows, m] fp32 GPU matrices (rows may be strided views): scores A, ground truth X → G fp32 [rows, m] on the
+    device, g_i = sum over j != i of sigmoid(a_i - a_j) - sigmoid(scale (x_i - x_j)): the gradient of the `risk` sum of
+    `pair_stats_rows` with respect to the scores.  A row with a non-finite entry is all NaN.  Deterministic."""
+    if not torch.is_tensor(A) or not torch.is_tensor(X) or A.dim() != 2 or X.shape != A.shape \
+            or A.dtype != torch.float32 or X.dtype != torch.float32 or not A.is_cuda or not X.is_cuda:
+        raise _lib.MfcdError("pair_grad_rows needs two float32 GPU matrices of the same shape (no CPU fallback)")
+    L = _lib.load()
+    rows, m = A.shape
+    if A.stride(1) != 1 or X.stride(1) != 1:
+        A, X = A.contiguous(), X.contiguous()
+    G = torch.empty((rows, m), dtype=torch.float32, device=A.device)
+    if rows == 0:
+        return G
+    if not 1 <= m <= 1 << 20:
+        raise _lib.MfcdError(f"rows of {m} columns are outside the pair kernel's range [1, 1048576]")
+    _lib.check(L.mfcd_pair_grad_rows(A.data_ptr(), A.stride(0) if rows > 1 else m, X.data_ptr(),
+                                     X.stride(0) if rows > 1 else m, rows, m, float(scale), G.data_ptr(), m,
+                                     _lib.stream_ptr(A.device)))
+    return G
+
+
 def _host(t):
     return None if t is None else t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
 
@@ -86,43 +112,58 @@ _KEYS = ("kendall_tau", "pairwise_accuracy", "expected_log_likelihood", "bayes_l
          "bayes_accuracy")
 
 
+class _RowSource:
+    """The chosen users' score rows U[u] V^T and ground-truth rows X[u] (A[u] B^T for a factored X), formed `row_block`
+    users at a time by plain library GEMMs; nothing n x m is formed for a factored X."""
+
+    def __init__(self, U, V, X, users, row_block, what):
+        if not torch.is_tensor(U) or not U.is_cuda:
+            raise _lib.MfcdError(f"{what} need the model on a GPU (there is no CPU fallback)")
+        self.dev = dev = U.device
+        self.U, self.V = U.float(), V.float()
+        n, m = U.shape[0], V.shape[0]
+        if tuple(X.shape) != (n, m):
+            raise ValueError(f"X must be [{n},{m}], got {tuple(X.shape)}")
+        self.factored = _lib.is_factored(X)
+        if self.factored:
+            self.XA, self.XBt = X.A.to(dev), X.B.to(dev).t()
+        else:
+            if not torch.is_tensor(X):
+                raise TypeError("X must be a dense GPU tensor or a FactoredMatrix")
+            self.X = X.to(dev).float()
+        self.whole = users is None
+        if self.whole:
+            self.ids = torch.arange(n, device=dev)
+        else:
+            self.ids = torch.as_tensor(users).reshape(-1).to(device=dev, dtype=torch.int64)
+            if self.ids.numel() and (int(self.ids.min()) < 0 or int(self.ids.max()) >= n):
+                raise IndexError(f"user number out of range for a model of {n} users")
+        self.n, self.m, self.k = n, m, self.ids.numel()
+        self.row_block = max(1, int(row_block))
+        self.Vt = self.V.t()
+
+    def blocks(self):
+        return [(r0, min(r0 + self.row_block, self.k)) for r0 in range(0, self.k, self.row_block)]
+
+    def rows_of(self, table, r0, r1):
+        return table[r0:r1] if self.whole else table[self.ids[r0:r1]]
+
+    def scores(self, r0, r1):
+        return self.rows_of(self.U, r0, r1) @ self.Vt
+
+    def truth(self, r0, r1):
+        return self.rows_of(self.XA, r0, r1) @ self.XBt if self.factored else self.rows_of(self.X, r0, r1)
+
+
 def pairwise_metrics(U, V, X, s=1.0, users=None, row_block=2048):
     """structure.compute_pairwise_metrics on factor tables: score rows U[r0:r1] @ V^T (and A[r0:r1] @ B^T for a
     factored X) are formed `row_block` at a time by a plain library GEMM and go through `pair_stats_rows`."""
-    if not torch.is_tensor(U) or not U.is_cuda:
-        raise _lib.MfcdError("pairwise metrics need the model on a GPU (there is no CPU fallback)")
-    dev = U.device
-    U, V = U.detach().float(), V.detach().float()
-    n, m = U.shape[0], V.shape[0]
-    if tuple(X.shape) != (n, m):
-        raise ValueError(f"X must be [{n},{m}], got {tuple(X.shape)}")
-    factored = _lib.is_factored(X)
-    if factored:
-        XA, XB = X.A.to(dev), X.B.to(dev)
-    else:
-        if not torch.is_tensor(X):
-            raise TypeError("X must be a dense GPU tensor or a FactoredMatrix")
-        X = X.to(dev).float()
-    if users is None:
-        ids = torch.arange(n, device=dev)
-    else:
-        ids = torch.as_tensor(users).reshape(-1).to(device=dev, dtype=torch.int64)
-        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n):
-            raise IndexError(f"user number out of range for a model of {n} users")
-    k = ids.numel()
-    row_block = max(1, int(row_block))
-    counts = torch.empty((k, 4), dtype=torch.int64, device=dev)
-    sums = torch.empty((k, 4), dtype=torch.float64, device=dev)
-    Vt = V.t()
-    for r0 in range(0, k, row_block):
-        sel = ids[r0:r0 + row_block]
-        whole = users is None
-        scores = (U[r0:r0 + row_block] if whole else U[sel]) @ Vt
-        if factored:
-            truth = (XA[r0:r0 + row_block] if whole else XA[sel]) @ XB.t()
-        else:
-            truth = X[r0:r0 + row_block] if whole else X[sel]
-        counts[r0:r0 + row_block], sums[r0:r0 + row_block] = pair_stats_rows(scores, truth, s, "both")
+    src = _RowSource(U.detach(), V.detach(), X, users, row_block, "pairwise metrics")
+    m = src.m
+    counts = torch.empty((src.k, 4), dtype=torch.int64, device=src.dev)
+    sums = torch.empty((src.k, 4), dtype=torch.float64, device=src.dev)
+    for r0, r1 in src.blocks():
+        counts[r0:r1], sums[r0:r1] = pair_stats_rows(src.scores(r0, r1), src.truth(r0, r1), s, "both")
     per = pairwise_from_counts(counts, sums, m)
     per["expected_log_likelihood"] = -per.pop("risk")          # the sign of the result dict's log_likelihoods
     per["bayes_log_likelihood"] = -per.pop("bayes_risk")
@@ -133,3 +174,105 @@ def pairwise_metrics(U, V, X, s=1.0, users=None, row_block=2048):
         out[name] = float(good.mean()) if good.size else 0.0
         out[name + "_per_user"] = v
     return out
+
+
+class _PopulationRisk(torch.autograd.Function):
+    """mean over the users of a _RowSource and over the n0 pairs of the BTL risk, as a function of the factor tables.
+    Backward recomputes a block's scores instead of keeping n x m of them, takes dRisk/dscores from `pair_grad_rows`
+    and carries it to the tables with two library GEMMs per block, accumulating in block order."""
+
+    @staticmethod
+    def forward(ctx, U, V, src, s):
+        total = torch.zeros((), dtype=torch.float64, device=src.dev)
+        for r0, r1 in src.blocks():
+            total += pair_stats_rows(src.scores(r0, r1), src.truth(r0, r1), s, "sums")[1][:, 0].sum()
+        ctx.src, ctx.s = src, s
+        return (total / (src.k * (src.m * (src.m - 1) // 2))).float()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        src = ctx.src
+        coef = grad_out.float() / (src.k * (src.m * (src.m - 1) // 2))
+        dU_rows = torch.empty((src.k, src.U.shape[1]), dtype=torch.float32, device=src.dev)
+        dV = torch.zeros_like(src.V)
+        for r0, r1 in src.blocks():
+            G = pair_grad_rows(src.scores(r0, r1), src.truth(r0, r1), ctx.s).mul_(coef)
+            torch.mm(G, src.V, out=dU_rows[r0:r1])
+            dV.addmm_(G.t(), src.rows_of(src.U, r0, r1))
+        if src.whole:
+            dU = dU_rows
+        else:       # a user named twice counts twice; accumulate=True adds in the order of `users`
+            dU = torch.zeros_like(src.U).index_put_((src.ids,), dU_rows, accumulate=True)
+        return dU, dV, None, None
+
+
+def population_risk(U, V, X, s=1.0, users=None, row_block=2048):
+    """The exact BTL population risk of the model U V^T against the label law q = sigmoid(s (x_i - x_j)): the mean, over
+    the chosen users (None: every user; a user named twice counts twice) and over all m (m - 1) / 2 item pairs, of
+    q (-log p) + (1 - q)(-log(1 - p)) with p = sigmoid(a_i - a_j) → 0-dim fp32 device tensor, differentiable with respect
+    to fp32 `U` and `V`.  X: a dense GPU tensor or a FactoredMatrix.  Rows are formed `row_block` users at a time."""
+    if torch.is_tensor(U) and U.is_cuda and (U.dtype != torch.float32 or V.dtype != torch.float32):
+        raise _lib.MfcdError("the population risk takes float32 factor tables")
+    src = _RowSource(U.detach(), V.detach(), X, users, row_block, "the population risk")
+    if src.m < 2:
+        raise ValueError("the population risk needs at least two items (m >= 2)")
+    if src.k == 0:
+        raise ValueError("the population risk needs at least one user")
+    return _PopulationRisk.apply(U, V, src, float(s))
+
+
+def fit_population(binding, X, s, steps, log_every=0, row_block=2048):
+    """`steps` steps of Adam on the exact population risk of every user (see `population_risk`), fused: per step the
+    score blocks, `pair_grad_rows` and two library GEMMs per block into dense gradients, then one mfcd_adam_dense —
+    coupled-L2 Adam on the caller's torch.optim.Adam state, which stays valid (binding: an engine.AdamBinding, or a
+    (model, optimizer) pair one is made from; fp32 tables only).  Nothing waits for the device inside the loop.
+    log_every = k > 0: the risk after 0, k, 2k, ... steps (taken before the next step, from the same score blocks) and
+    after the last step is written to a device buffer and read once at the end → (steps taken, risks) as Python lists;
+    log_every = 0 → ([], [])."""
+    from . import engine
+    if not isinstance(binding, engine.AdamBinding):
+        binding = engine.AdamBinding(*binding)
+    for name, t in zip(("model.U", "model.V"), binding.tensors()[:2]):
+        engine._require_cuda_param(t, name)                    # fp32 only: bf16 tables are refused here
+    L = _lib.load()
+    U, V, mU, vU, mV, vV = binding.tensors()
+    src = _RowSource(U, V, X, None, row_block, "the population fit")
+    n, m, d, dev = src.n, src.m, U.shape[1], src.dev
+    if m < 2:
+        raise ValueError("the population risk needs at least two items (m >= 2)")
+    steps, k = int(steps), int(log_every)
+    n0 = m * (m - 1) // 2
+    inv = 1.0 / (n * n0)
+    at = ([t for t in range(0, steps, k)] + [steps]) if k > 0 else []
+    log = torch.zeros(max(len(at), 1), dtype=torch.float64, device=dev)
+    gU, gV = torch.empty_like(U), torch.empty_like(V)
+    ptrs = [_lib.ptr(t) for t in (U, V, mU, vU, mV, vV, gU, gV)]
+    lr, b1, b2, eps, wd = binding.hyper()
+    stream = _lib.stream_ptr(dev)
+    blocks = src.blocks()
+
+    def risk_into(slot, scores, truth):
+        slot += pair_stats_rows(scores, truth, s, "sums")[1][:, 0].sum()
+
+    try:
+        for t in range(steps):
+            logging = k > 0 and t % k == 0
+            for b, (r0, r1) in enumerate(blocks):
+                scores, truth = src.scores(r0, r1), src.truth(r0, r1)
+                if logging:
+                    risk_into(log[t // k], scores, truth)
+                G = pair_grad_rows(scores, truth, s).mul_(inv)
+                torch.mm(G, V, out=gU[r0:r1])
+                if b == 0:
+                    torch.mm(G.t(), U[r0:r1], out=gV)
+                else:
+                    gV.addmm_(G.t(), U[r0:r1])
+            _lib.check(L.mfcd_adam_dense(*ptrs, binding.step + 1, n, m, d, lr, b1, b2, eps, wd, stream))
+            binding.advance(1, defer=True)
+    finally:
+        binding.flush()         # an interrupt must not leave the moments ahead of the optimizer's `step` tensors
+    if k <= 0:
+        return [], []
+    for r0, r1 in blocks:
+        risk_into(log[len(at) - 1], src.scores(r0, r1), src.truth(r0, r1))
+    return at, (log[:len(at)] * inv).cpu().tolist()       # the one device->host transfer of the run

@@ -169,6 +169,49 @@ def compute_pairwise_metrics(model, X, s=1.0, users=None, row_block=2048):
     return _pairs.pairwise_metrics(model.U.data, model.V.data, X, s, users, row_block)
 
 
+def population_risk(model, X, s=1.0, users=None, row_block=2048):
+    """Extension (not in the reference): the quantity the sampled experiments estimate, as a differentiable scalar — the
+    mean over `users` (None: every user; a user named twice counts twice) and over ALL item pairs of the BCE of
+    p = sigmoid(a_i - a_j), a = U[u] V^T, under the label law q = sigmoid(s (x_i - x_j)); minus
+    `compute_pairwise_metrics`' expected_log_likelihood.  Returns a 0-dim fp32 tensor on the model's device;
+    `population_risk(...).backward()` fills `model.U.grad` / `model.V.grad` (include/mfcd.h mfcd_pair_grad_rows and two
+    library GEMMs per block of `row_block` users), so any torch optimiser can descend it.  fp32 models only.
+    X: a dense GPU tensor or a `FactoredMatrix`.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _pairs.population_risk(model.U, model.V, X, s, users, row_block)
+
+
+def train_model_population(model, X, s, optimizer, device, num_steps=1000, log_every=100, row_block=2048):
+    """Extension (not in the reference): `train_model` with unlimited comparisons — `num_steps` full-batch optimiser steps
+    on `population_risk(model, X, s)` over every user: what the model and its weight decay converge to when sampling
+    error is gone.  Returns (steps, risks) as Python lists: the risk after steps[k] = 0, log_every, 2 log_every, ...
+    optimiser steps and after the last one (two empty lists for log_every = 0), read from the device once at the end.
+    torch.optim.Adam takes the fused loop (mfcd.pairs.fit_population: risk gradient, GEMMs and one dense Adam kernel
+    per step, the optimizer's state updated in place); any other optimiser runs zero_grad / population_risk / backward /
+    step.  Not part of the result dict / .pkl layout."""
+    _need_gpu(device)
+    model.train()
+    if _engine.fused_step_applies(model, optimizer):
+        out = _pairs.fit_population(_engine.AdamBinding(model, optimizer), X, s, num_steps, log_every, row_block)
+    else:
+        at, seen = [], []
+        for t in range(int(num_steps)):
+            optimizer.zero_grad()
+            loss = population_risk(model, X, s, None, row_block)
+            loss.backward()
+            optimizer.step()
+            if log_every > 0 and t % log_every == 0:
+                at.append(t)
+                seen.append(loss.detach())
+        if log_every > 0:
+            with torch.no_grad():
+                at.append(int(num_steps))
+                seen.append(population_risk(model, X, s, None, row_block))
+        out = (at, torch.stack(seen).double().cpu().tolist() if seen else [])
+    model.eval()
+    return out
+
+
 def compute_ground_truth_metrics(test_loader, X, device):
     """ref:1085-1127: MSE between sigmoid(X[u,i]-X[u,j]) (no scale) and the labels, per batch, and
     the accuracy of (diff > 0).  Two-element gather per sample, once per experiment: torch ops on
