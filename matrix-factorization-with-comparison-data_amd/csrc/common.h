@@ -46,12 +46,31 @@ __device__ __forceinline__ float wave_sum64(float x)
     return (r0 + r1) + (r2 + r3);
 }
 
-__device__ __forceinline__ int wave_sum64_i(int x)
+// Sum over the 64 lanes by an xor butterfly, offsets 32 -> 1, the same order for any T (not the order of wave_sum64).
+template <typename T>
+__device__ __forceinline__ T wave_sum_xor(T v)
 {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, MFCD_WAVE);
-    return x;
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, MFCD_WAVE);
+    return v;
 }
+
+__device__ __forceinline__ int wave_sum64_i(int x) { return wave_sum_xor(x); }
+
+// Monotone map of a float onto unsigned: a < b  <=>  key(a) < key(b), with -0.0 == +0.0 (NaN is the caller's business).
+__device__ __forceinline__ unsigned sortable_key(float f)
+{
+    if (f == 0.0f) f = 0.0f;                       // -0.0 -> +0.0
+    const unsigned u = __float_as_uint(f);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+
+// inf or NaN: the exponent bits are all set
+__device__ __forceinline__ bool is_nonfinite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+// acc[reg] of a 32x32 fp32 MFMA tile:  row = (reg&3) + 8*(reg>>2) + 4*half,  col = lane&31   (gfx950 C/D map)
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ int tile_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
 // torch.sigmoid in fp32 (structure.py:795): 1/(1+exp(-x)); rounds to exactly 0/1 when saturated.
 __device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }

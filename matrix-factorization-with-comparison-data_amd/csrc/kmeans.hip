@@ -22,8 +22,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kMaxK = 64;                            // centres of one call: two 32-column MFMA tiles
 constexpr int kMaxP = 1 << 22;
 constexpr int kPts = 128, kKC = 32, kLD = kKC + 1;   // assign: points per workgroup, coordinates per LDS stage, padded row
@@ -31,9 +29,6 @@ constexpr int kDeepMinDim = 256, kDeepBelowBlocks = 256;   // assign, few points
 constexpr int kCols = 64;                            // update: coordinates per wave (one LDS column per lane)
 constexpr int kChunkPts = 128, kMaxChunks = 512;     // update: points per chunk at least / chunks at most
 constexpr size_t kSlabBytes = (size_t)64 << 20;      // update: the f64 slab (but at least one chunk)
-
-// acc[reg] of a 32x32 tile:  row = (reg&3) + 8*(reg>>2) + 4*half,  col = lane&31   (gfx950 C/D map)
-__device__ __forceinline__ int tile_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
 // hn[c] = |centre c|^2 / 2: one wave per centre, f64 partial sums per lane in coordinate order, then a butterfly
 __global__ __launch_bounds__(MFCD_WAVE) void kmeans_half_norms_kernel(const float *__restrict__ C, int dim,
@@ -47,7 +42,7 @@ __global__ __launch_bounds__(MFCD_WAVE) void kmeans_half_norms_kernel(const floa
         s += v * v;
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, MFCD_WAVE);
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, MFCD_WAVE);   // inline: wave_sum_xor changes this kernel's ISA
     if (lane == 0) hn[blockIdx.x] = (float)(0.5 * s);
 }
 

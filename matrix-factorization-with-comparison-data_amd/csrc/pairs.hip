@@ -120,14 +120,6 @@ __device__ __forceinline__ void pair_run(const float2 *tile, int j0, int j1, con
     }
 }
 
-template <typename V>
-__device__ __forceinline__ V pair_wave_sum(V v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, MFCD_WAVE);
-    return v;
-}
-
 template <int WHAT>
 __global__ __launch_bounds__(kPairThreads) void pair_tiles_kernel(const float *__restrict__ A, int64_t lda,
                                                                   const float *__restrict__ X, int64_t ldx, int m, int T,
@@ -152,8 +144,7 @@ __global__ __launch_bounds__(kPairThreads) void pair_tiles_kernel(const float *_
             ai[k] = a[p];
             xi[k] = x[p];
             n_nan += (unsigned)(ai[k] != ai[k] || xi[k] != xi[k]);
-            n_inf += (unsigned)((__float_as_uint(ai[k]) & 0x7f800000u) == 0x7f800000u ||
-                                (__float_as_uint(xi[k]) & 0x7f800000u) == 0x7f800000u);
+            n_inf += (unsigned)(is_nonfinite_bits(ai[k]) || is_nonfinite_bits(xi[k]));
         }
     }
 
@@ -186,9 +177,9 @@ __global__ __launch_bounds__(kPairThreads) void pair_tiles_kernel(const float *_
     long long c6[6] = {(long long)cnt[0], (long long)cnt[1], (long long)cnt[2], (long long)cnt[3], (long long)n_nan,
                        (long long)n_inf};
 #pragma unroll
-    for (int q = 0; q < 6; ++q) c6[q] = pair_wave_sum(c6[q]);
+    for (int q = 0; q < 6; ++q) c6[q] = wave_sum_xor(c6[q]);
 #pragma unroll
-    for (int q = 0; q < 6; ++q) acc[q] = pair_wave_sum(acc[q]);
+    for (int q = 0; q < 6; ++q) acc[q] = wave_sum_xor(acc[q]);
     if ((tid & 63) == 0) {
         for (int q = 0; q < 6; ++q) red_c[tid >> 6][q] = c6[q];
         for (int q = 0; q < 6; ++q) red_s[tid >> 6][q] = acc[q];
@@ -230,9 +221,9 @@ __global__ __launch_bounds__(64) void pair_finish_kernel(const PairPartial *__re
         for (int q = 0; q < 4; ++q) s[q] += p.s[q];
     }
 #pragma unroll
-    for (int q = 0; q < 6; ++q) c6[q] = pair_wave_sum(c6[q]);
+    for (int q = 0; q < 6; ++q) c6[q] = wave_sum_xor(c6[q]);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) s[q] = pair_wave_sum(s[q]);
+    for (int q = 0; q < 4; ++q) s[q] = wave_sum_xor(s[q]);
     if (threadIdx.x == 0) {
         if (what & 1)
             for (int q = 0; q < 4; ++q) counts[r * 4 + q] = c6[4] ? -1 : q < 2 ? c6[q] : n0 - c6[q];
@@ -266,8 +257,6 @@ __device__ __forceinline__ float pair_sigmoid(float v)
     return v >= 0.0f ? hi : e * hi;
 }
 
-__device__ __forceinline__ bool pair_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-
 __global__ __launch_bounds__(kPairThreads) void pair_grad_kernel(const float *__restrict__ A, int64_t lda,
                                                                  const float *__restrict__ X, int64_t ldx, int m, int T,
                                                                  float scale, float *__restrict__ G, int64_t ldg)
@@ -294,7 +283,7 @@ __global__ __launch_bounds__(kPairThreads) void pair_grad_kernel(const float *__
         for (int k = 0; k < kPairIpt; ++k) {
             const int e = k * kPairThreads + tid, p = J * kPairTile + e;
             const float2 v = p < m ? make_float2(a[p], x[p]) : make_float2(0.0f, 0.0f);
-            bad |= (int)(pair_nonfinite(v.x) || pair_nonfinite(v.y));
+            bad |= (int)(is_nonfinite_bits(v.x) || is_nonfinite_bits(v.y));
             tile[e] = v;
         }
         __syncthreads();

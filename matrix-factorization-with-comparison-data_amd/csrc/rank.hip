@@ -37,17 +37,9 @@ namespace {
 constexpr int kRankThreads = 1024;
 constexpr int kRankMaxCols = 20448;   // 8 bytes of LDS per column (+ the reduction scratch) within 160 KiB
 
-__device__ __forceinline__ unsigned sortable_key(float f)
-{
-    if (f == 0.0f) f = 0.0f;                       // -0.0 -> +0.0
-    const unsigned u = __float_as_uint(f);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-
 __device__ __forceinline__ long long block_sum_i64(long long v, long long *red)
 {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, MFCD_WAVE);
+    v = wave_sum_xor(v);
     __syncthreads();                               // red[] may still be read from the previous use
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();

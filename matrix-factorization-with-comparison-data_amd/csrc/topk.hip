@@ -19,13 +19,11 @@
 //                 first level whose bin is wanted whole, every composite at or below that bin is appended to the
 //                 candidate list (exactly k, any order), and a bitonic sort of the <= 8192 composites in LDS puts
 //                 them in final order.  The result does not depend on the order of the appends.
-// Ordered key: best = ~sortable(x), worst = sortable(x) with rank.hip's sortable key (-0.0 == +0.0), NaN -> the
+// Ordered key: best = ~sortable(x), worst = sortable(x) with common.h's sortable_key (-0.0 == +0.0), NaN -> the
 // smallest key for best (torch.topk's convention), the largest for worst; equal keys are ordered by column.
 #include "common.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kTopkThreads = 1024;
 constexpr int kTopkWaves = kTopkThreads / MFCD_WAVE;
@@ -35,13 +33,6 @@ constexpr int kBins = 2048;                     // histogram of the widest radix
 constexpr size_t kSlabBytes = (size_t)128 << 20;   // score slab of the factor mode (at least one block of 128 rows)
 constexpr int kBlk = 128, kKC = 32, kLD = kKC + 1;  // score kernel: output block, factor columns per LDS stage, padded row
 
-__device__ __forceinline__ unsigned sortable_key(float f)   // as rank.hip
-{
-    if (f == 0.0f) f = 0.0f;                       // -0.0 -> +0.0
-    const unsigned u = __float_as_uint(f);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-
 // ascending ordered key = output order of the end
 __device__ __forceinline__ unsigned ordered_key(float f, bool worst)
 {
@@ -49,9 +40,6 @@ __device__ __forceinline__ unsigned ordered_key(float f, bool worst)
     const unsigned s = sortable_key(f);
     return worst ? s : ~s;
 }
-
-// acc[reg] of a 32x32 tile:  row = (reg&3) + 8*(reg>>2) + 4*half,  col = lane&31   (gfx950 C/D map)
-__device__ __forceinline__ int tile_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
 // the id of requested row r, or -1 when it is not a row of the table
 __device__ __forceinline__ int row_id_of(const int32_t *row_ids, int row_base, int r, int n)

@@ -22,8 +22,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kSlices = 256;  // row slices for the deterministic column-sum of U and V
 constexpr int kTiledRowSums = 6;   // doubles the tiled kernel leaves per (split, row) for the final kernel
 
@@ -250,9 +248,6 @@ __global__ __launch_bounds__(256) void x_rows_kernel(const float *__restrict__ X
         sxx[r] = s2;
     }
 }
-
-// acc[reg] of a 32x32 tile:  row = (reg&3) + 8*(reg>>2) + 4*half,  col = lane&31   (gfx950 C/D map)
-__device__ __forceinline__ int tile_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
 // MFMA tile: D is the compile-time factor width (multiple of 8).  a[] holds this lane's A fragment.
 template <int D>

@@ -185,3 +185,31 @@ def stream_ptr(device=None):
     if _raw_stream is not None and isinstance(device, torch.device) and device.index is not None:
         return _raw_stream(device.index)
     return torch.cuda.current_stream(device).cuda_stream
+
+
+_workspaces = {}    # (device index, stream handle) -> the scratch buffer of the row kernels
+
+
+def workspace(nbytes, device):
+    """Scratch for one kernel call: a uint8 buffer of at least `nbytes` (256 at the least), grow-only, one per (device,
+    current stream): work on two streams of a device is not ordered, so it may not share scratch.  No kernel expects
+    anything of its contents.  Fetch it per call: a later request on the same stream may replace it by a larger one.
+    An entry is never dropped: a process keeps the high-water mark of every stream it ran a row kernel on."""
+    index = torch.device(device).index             # "cuda" and "cuda:0" are one device
+    key = (torch.cuda.current_device() if index is None else index, stream_ptr(device))
+    buf = _workspaces.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = _workspaces[key] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+    return buf
+
+
+def row_pair(A, X, who):
+    """Two [rows, m] matrices of a row kernel, checked → (A, X, rows, m, lda, ldx): float32, on a GPU, of one shape, unit
+    column stride (copies otherwise), leading dimensions in elements (m for a single row: its stride says nothing)."""
+    if not torch.is_tensor(A) or not torch.is_tensor(X) or A.dim() != 2 or X.shape != A.shape \
+            or A.dtype != torch.float32 or X.dtype != torch.float32 or not A.is_cuda or not X.is_cuda:
+        raise MfcdError(f"{who} needs two float32 GPU matrices of the same shape (no CPU fallback)")
+    rows, m = A.shape
+    if A.stride(1) != 1 or X.stride(1) != 1:
+        A, X = A.contiguous(), X.contiguous()
+    return A, X, rows, m, (A.stride(0) if rows > 1 else m), (X.stride(0) if rows > 1 else m)

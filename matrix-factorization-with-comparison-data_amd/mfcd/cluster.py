@@ -9,8 +9,7 @@ module's own, as for every device law of mfcd/sampling.py.  There is no CPU form
 import torch
 
 from . import _lib
-
-_ws = {}
+from .rows import resolve
 
 
 def max_k():
@@ -21,7 +20,8 @@ def item_points(X, device):
     """One fp32 point per item, row-major [m, dim] on `device`: the item columns of a dense X [n, m] (dim = n), or, for
     a FactoredMatrix X = A B^T (A [n, dx], B [m, dx]), the rows of B R^T with A^T A = R^T R (dim = dx) — an isometry:
     |R (b_i - b_j)| = |A (b_i - b_j)|, so the distances between these rows are those between the columns of X."""
-    if _lib.is_factored(X):
+    X = resolve(X)
+    if X.factored:                                      # d x d algebra in f64, on the factors' own device
         A, B = X.A.double(), X.B.double()
         G = A.t() @ A
         R, info = torch.linalg.cholesky_ex(G, upper=True)
@@ -29,15 +29,7 @@ def item_points(X, device):
             w, Q = torch.linalg.eigh(G)
             R = torch.sqrt(w.clamp_min(0.0))[:, None] * Q.t()
         return (B @ R.t()).float().to(device).contiguous()
-    return X.detach().to(device=device, dtype=torch.float32).t().contiguous()
-
-
-def _workspace(nbytes, device):
-    buf = _ws.get(device)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-        _ws[device] = buf
-    return buf
+    return X.dense.to(device=device, dtype=torch.float32).t().contiguous()
 
 
 def _checked(points, centres):
@@ -54,7 +46,7 @@ def _checked(points, centres):
     nbytes = _lib.load().mfcd_kmeans_workspace_bytes(P, dim, k)
     if nbytes == 0:
         raise ValueError(f"k-means sizes out of range: {P} points, dim {dim}, k = {k} (1 <= k <= {max_k()})")
-    return P, dim, k, _workspace(nbytes, points.device)
+    return P, dim, k, _lib.workspace(nbytes, points.device)
 
 
 def assign(points, centres, labels=None, dist2=False, changed=None):

@@ -399,13 +399,12 @@ def broadcast_state(binding, src=0, group=None):
 def hip_slab_pass(U, V, X_rows, row0, s, what):
     """Rows [row0, row0 + k) of the UV^T metric pass on this GPU (include/mfcd.h: mfcd_uvt_stats_slab): per-row sums
     for those rows and this slab's share of the two global sums."""
-    from . import metrics
     L = _lib.load()
     U, V, X_rows = U.contiguous(), V.contiguous(), X_rows.contiguous()
     (n, d), m, k = U.shape, V.shape[0], X_rows.shape[0]
     rs = torch.empty((k, 8), dtype=torch.float64, device=U.device) if what & 1 else None
     share = torch.empty(4, dtype=torch.float64, device=U.device) if what & 2 else None
-    ws = metrics._workspace(L.mfcd_uvt_slab_workspace_bytes(n, m, d, k), U.device)
+    ws = _lib.workspace(L.mfcd_uvt_slab_workspace_bytes(n, m, d, k), U.device)
     _lib.check(L.mfcd_uvt_stats_slab(_lib.ptr(U), _lib.ptr(V), _lib.ptr(X_rows), n, m, d, float(s), int(what), int(row0),
                                      k, _lib.ptr(rs), _lib.ptr(share), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(U.device)))
     return rs, share

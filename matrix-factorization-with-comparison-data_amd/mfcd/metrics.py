@@ -15,16 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-
-_ws = {}
-
-
-def _workspace(nbytes, device):
-    buf = _ws.get(device)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-        _ws[device] = buf
-    return buf
+from .rows import blocks, resolve
 
 
 def uvt_stats(U, V, X, s=1.0, what=3):
@@ -42,7 +33,7 @@ def uvt_stats(U, V, X, s=1.0, what=3):
         raise ValueError(f"X must be [{n},{m}], got {tuple(X.shape)}")
     row_stats = torch.empty((n, 8), dtype=torch.float64, device=U.device) if what & 1 else None
     scal = torch.empty(4, dtype=torch.float64, device=U.device) if what & 2 else None
-    ws = _workspace(L.mfcd_uvt_workspace_bytes(n, m, d), U.device)
+    ws = _lib.workspace(L.mfcd_uvt_workspace_bytes(n, m, d), U.device)
     _lib.check(L.mfcd_uvt_stats_select(_lib.ptr(U), _lib.ptr(V), _lib.ptr(X), n, m, d, float(s), int(what),
                                        _lib.ptr(row_stats), _lib.ptr(scal), _lib.ptr(ws), ws.numel(),
                                        _lib.stream_ptr(U.device)))
@@ -61,15 +52,14 @@ def uvt_stats_factored(U, V, FX, s=1.0, what=3, slab_rows=4096):
     (n, d), m = U.shape, V.shape[0]
     if tuple(FX.shape) != (n, m):
         raise ValueError(f"X must be [{n},{m}], got {tuple(FX.shape)}")
-    A, B = FX.A.to(dev), FX.B.to(dev)
+    FX = resolve(FX, dev)
     slab_rows = max(1, min(int(slab_rows), n))
     row_stats = torch.empty((n, 8), dtype=torch.float64, device=dev) if what & 1 else None
     scal = torch.zeros(4, dtype=torch.float64, device=dev) if what & 2 else None
     share = torch.empty(4, dtype=torch.float64, device=dev) if what & 2 else None
-    ws = _workspace(L.mfcd_uvt_slab_workspace_bytes(n, m, d, slab_rows), dev)
-    for r0 in range(0, n, slab_rows):
-        r1 = min(n, r0 + slab_rows)
-        Xs = (A[r0:r1] @ B.t()).contiguous()
+    ws = _lib.workspace(L.mfcd_uvt_slab_workspace_bytes(n, m, d, slab_rows), dev)    # held over GEMMs only
+    for r0, r1 in blocks(n, slab_rows):
+        Xs = FX.rows(r0, r1).contiguous()
         _lib.check(L.mfcd_uvt_stats_slab(_lib.ptr(U), _lib.ptr(V), _lib.ptr(Xs), n, m, d, float(s), int(what), r0,
                                          r1 - r0, _lib.ptr(row_stats[r0:r1]) if what & 1 else None, _lib.ptr(share),
                                          _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
@@ -142,38 +132,27 @@ def spearman_rows_any(A, X):
 
 def spearman_rows_long(A, X):
     """include/mfcd.h mfcd_spearman_rows_long: rows of any length (BASELINE configs[3]: 65536 items), f64 [rows]."""
+    A, X, rows, m, lda, ldx = _lib.row_pair(A, X, "spearman_rows_long")
     L = _lib.load()
-    rows, m = A.shape
-    if X.shape != A.shape or A.dtype != torch.float32 or X.dtype != torch.float32 or not A.is_cuda or not X.is_cuda:
-        raise _lib.MfcdError("spearman_rows_long needs two float32 GPU matrices of the same shape")
-    if A.stride(1) != 1 or X.stride(1) != 1:
-        A, X = A.contiguous(), X.contiguous()
     rho = torch.empty(rows, dtype=torch.float64, device=A.device)
     if rows == 0:
         return rho
     need = L.mfcd_spearman_long_workspace_bytes(rows, m)
     if need == 0:
         raise _lib.MfcdError(f"rows of {m} columns are beyond the rank kernels")
-    ws = _workspace(need, A.device)
-    _lib.check(L.mfcd_spearman_rows_long(A.data_ptr(), A.stride(0) if rows > 1 else m, X.data_ptr(),
-                                         X.stride(0) if rows > 1 else m, rows, m, _lib.ptr(rho), _lib.ptr(ws), ws.numel(),
-                                         _lib.stream_ptr(A.device)))
+    ws = _lib.workspace(need, A.device)
+    _lib.check(L.mfcd_spearman_rows_long(A.data_ptr(), lda, X.data_ptr(), ldx, rows, m, _lib.ptr(rho), _lib.ptr(ws),
+                                         ws.numel(), _lib.stream_ptr(A.device)))
     return rho
 
 
 def spearman_rows(A, X):
     """Per-row Spearman rho of two [rows, m] fp32 GPU matrices (rows may be strided views) → f64 [rows] on device.
     HIP kernel (include/mfcd.h: mfcd_spearman_rows), m <= mfcd_spearman_max_columns() = 20448."""
-    L = _lib.load()
-    rows, m = A.shape
-    if X.shape != A.shape or A.dtype != torch.float32 or X.dtype != torch.float32 or not A.is_cuda or not X.is_cuda:
-        raise _lib.MfcdError("spearman_rows needs two float32 GPU matrices of the same shape")
-    if A.stride(1) != 1 or X.stride(1) != 1:
-        A, X = A.contiguous(), X.contiguous()
+    A, X, rows, m, lda, ldx = _lib.row_pair(A, X, "spearman_rows")
     rho = torch.empty(rows, dtype=torch.float64, device=A.device)
-    _lib.check(L.mfcd_spearman_rows(A.data_ptr(), A.stride(0) if rows > 1 else m, X.data_ptr(),
-                                    X.stride(0) if rows > 1 else m, rows, m, _lib.ptr(rho),
-                                    _lib.stream_ptr(A.device)))
+    _lib.check(_lib.load().mfcd_spearman_rows(A.data_ptr(), lda, X.data_ptr(), ldx, rows, m, _lib.ptr(rho),
+                                              _lib.stream_ptr(A.device)))
     return rho
 
 
@@ -273,8 +252,7 @@ def spearman_and_svd(U, V, X_centred_rows_mean, X, alpha, ok_rows, row_block=204
     vbar = V.mean(dim=0, keepdim=True)
     Vc = V - vbar
     in_kernel = m <= _lib.load().mfcd_spearman_max_columns()
-    for r0 in range(0, n, row_block):
-        r1 = min(n, r0 + row_block)
+    for r0, r1 in blocks(n, row_block):
         A = U[r0:r1] @ Vc.t()                              # row-centred UV^T block (ranks ignore the shift)
         rho[r0:r1] = spearman_rows(A, X[r0:r1]) if in_kernel else spearman_rows_any(A, X[r0:r1])
     rho = rho.cpu().numpy()

@@ -14,18 +14,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from .rows import RowBlocks
 
 TILE = 1024          # columns per workgroup tile of the kernel (csrc/pairs.hip: kPairTile)
 _WHAT = {"counts": 1, "sums": 2, "both": 3}
-_ws = {}
-
-
-def _workspace(nbytes, device):
-    buf = _ws.get(device)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-        _ws[device] = buf
-    return buf
 
 
 def pair_stats_rows(A, X, scale=1.0, what="both"):
@@ -36,13 +28,8 @@ def pair_stats_rows(A, X, scale=1.0, what="both"):
     if what not in _WHAT:
         raise ValueError(f"what must be one of {sorted(_WHAT)}, got {what!r}")
     w = _WHAT[what]
-    if not torch.is_tensor(A) or not torch.is_tensor(X) or A.dim() != 2 or X.shape != A.shape \
-            or A.dtype != torch.float32 or X.dtype != torch.float32 or not A.is_cuda or not X.is_cuda:
-        raise _lib.MfcdError("pair_stats_rows needs two float32 GPU matrices of the same shape (no CPU fallback)")
+    A, X, rows, m, lda, ldx = _lib.row_pair(A, X, "pair_stats_rows")
     L = _lib.load()
-    rows, m = A.shape
-    if A.stride(1) != 1 or X.stride(1) != 1:
-        A, X = A.contiguous(), X.contiguous()
     counts = torch.empty((rows, 4), dtype=torch.int64, device=A.device) if w & 1 else None
     sums = torch.empty((rows, 4), dtype=torch.float64, device=A.device) if w & 2 else None
     if rows == 0:
@@ -50,9 +37,8 @@ def pair_stats_rows(A, X, scale=1.0, what="both"):
     need = L.mfcd_pair_stats_workspace_bytes(rows, m)
     if need == 0:
         raise _lib.MfcdError(f"rows of {m} columns are outside the pair kernel's range [1, 1048576]")
-    ws = _workspace(need, A.device)
-    _lib.check(L.mfcd_pair_stats_rows(A.data_ptr(), A.stride(0) if rows > 1 else m, X.data_ptr(),
-                                      X.stride(0) if rows > 1 else m, rows, m, float(scale), w, _lib.ptr(counts),
+    ws = _lib.workspace(need, A.device)
+    _lib.check(L.mfcd_pair_stats_rows(A.data_ptr(), lda, X.data_ptr(), ldx, rows, m, float(scale), w, _lib.ptr(counts),
                                       _lib.ptr(sums), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(A.device)))
     return counts, sums
 
@@ -61,20 +47,14 @@ def pair_grad_rows(A, X, scale=1.0):
     """Two [rows, m] fp32 GPU matrices (rows may be strided views): scores A, ground truth X → G fp32 [rows, m] on the
     device, g_i = sum over j != i of sigmoid(a_i - a_j) - sigmoid(scale (x_i - x_j)): the gradient of the `risk` sum of
     `pair_stats_rows` with respect to the scores.  A row with a non-finite entry is all NaN.  Deterministic."""
-    if not torch.is_tensor(A) or not torch.is_tensor(X) or A.dim() != 2 or X.shape != A.shape \
-            or A.dtype != torch.float32 or X.dtype != torch.float32 or not A.is_cuda or not X.is_cuda:
-        raise _lib.MfcdError("pair_grad_rows needs two float32 GPU matrices of the same shape (no CPU fallback)")
+    A, X, rows, m, lda, ldx = _lib.row_pair(A, X, "pair_grad_rows")
     L = _lib.load()
-    rows, m = A.shape
-    if A.stride(1) != 1 or X.stride(1) != 1:
-        A, X = A.contiguous(), X.contiguous()
     G = torch.empty((rows, m), dtype=torch.float32, device=A.device)
     if rows == 0:
         return G
     if not 1 <= m <= 1 << 20:
         raise _lib.MfcdError(f"rows of {m} columns are outside the pair kernel's range [1, 1048576]")
-    _lib.check(L.mfcd_pair_grad_rows(A.data_ptr(), A.stride(0) if rows > 1 else m, X.data_ptr(),
-                                     X.stride(0) if rows > 1 else m, rows, m, float(scale), G.data_ptr(), m,
+    _lib.check(L.mfcd_pair_grad_rows(A.data_ptr(), lda, X.data_ptr(), ldx, rows, m, float(scale), G.data_ptr(), m,
                                      _lib.stream_ptr(A.device)))
     return G
 
@@ -112,53 +92,10 @@ _KEYS = ("kendall_tau", "pairwise_accuracy", "expected_log_likelihood", "bayes_l
          "bayes_accuracy")
 
 
-class _RowSource:
-    """The chosen users' score rows U[u] V^T and ground-truth rows X[u] (A[u] B^T for a factored X), formed `row_block`
-    users at a time by plain library GEMMs; nothing n x m is formed for a factored X."""
-
-    def __init__(self, U, V, X, users, row_block, what):
-        if not torch.is_tensor(U) or not U.is_cuda:
-            raise _lib.MfcdError(f"{what} need the model on a GPU (there is no CPU fallback)")
-        self.dev = dev = U.device
-        self.U, self.V = U.float(), V.float()
-        n, m = U.shape[0], V.shape[0]
-        if tuple(X.shape) != (n, m):
-            raise ValueError(f"X must be [{n},{m}], got {tuple(X.shape)}")
-        self.factored = _lib.is_factored(X)
-        if self.factored:
-            self.XA, self.XBt = X.A.to(dev), X.B.to(dev).t()
-        else:
-            if not torch.is_tensor(X):
-                raise TypeError("X must be a dense GPU tensor or a FactoredMatrix")
-            self.X = X.to(dev).float()
-        self.whole = users is None
-        if self.whole:
-            self.ids = torch.arange(n, device=dev)
-        else:
-            self.ids = torch.as_tensor(users).reshape(-1).to(device=dev, dtype=torch.int64)
-            if self.ids.numel() and (int(self.ids.min()) < 0 or int(self.ids.max()) >= n):
-                raise IndexError(f"user number out of range for a model of {n} users")
-        self.n, self.m, self.k = n, m, self.ids.numel()
-        self.row_block = max(1, int(row_block))
-        self.Vt = self.V.t()
-
-    def blocks(self):
-        return [(r0, min(r0 + self.row_block, self.k)) for r0 in range(0, self.k, self.row_block)]
-
-    def rows_of(self, table, r0, r1):
-        return table[r0:r1] if self.whole else table[self.ids[r0:r1]]
-
-    def scores(self, r0, r1):
-        return self.rows_of(self.U, r0, r1) @ self.Vt
-
-    def truth(self, r0, r1):
-        return self.rows_of(self.XA, r0, r1) @ self.XBt if self.factored else self.rows_of(self.X, r0, r1)
-
-
 def pairwise_metrics(U, V, X, s=1.0, users=None, row_block=2048):
     """structure.compute_pairwise_metrics on factor tables: score rows U[r0:r1] @ V^T (and A[r0:r1] @ B^T for a
     factored X) are formed `row_block` at a time by a plain library GEMM and go through `pair_stats_rows`."""
-    src = _RowSource(U.detach(), V.detach(), X, users, row_block, "pairwise metrics")
+    src = RowBlocks(U.detach(), V.detach(), X, users, row_block, "pairwise metrics")
     m = src.m
     counts = torch.empty((src.k, 4), dtype=torch.int64, device=src.dev)
     sums = torch.empty((src.k, 4), dtype=torch.float64, device=src.dev)
@@ -177,7 +114,7 @@ def pairwise_metrics(U, V, X, s=1.0, users=None, row_block=2048):
 
 
 class _PopulationRisk(torch.autograd.Function):
-    """mean over the users of a _RowSource and over the n0 pairs of the BTL risk, as a function of the factor tables.
+    """mean over the users of a RowBlocks and over the n0 pairs of the BTL risk, as a function of the factor tables.
     Backward recomputes a block's scores instead of keeping n x m of them, takes dRisk/dscores from `pair_grad_rows`
     and carries it to the tables with two library GEMMs per block, accumulating in block order."""
 
@@ -213,7 +150,7 @@ def population_risk(U, V, X, s=1.0, users=None, row_block=2048):
     to fp32 `U` and `V`.  X: a dense GPU tensor or a FactoredMatrix.  Rows are formed `row_block` users at a time."""
     if torch.is_tensor(U) and U.is_cuda and (U.dtype != torch.float32 or V.dtype != torch.float32):
         raise _lib.MfcdError("the population risk takes float32 factor tables")
-    src = _RowSource(U.detach(), V.detach(), X, users, row_block, "the population risk")
+    src = RowBlocks(U.detach(), V.detach(), X, users, row_block, "the population risk")
     if src.m < 2:
         raise ValueError("the population risk needs at least two items (m >= 2)")
     if src.k == 0:
@@ -236,7 +173,7 @@ def fit_population(binding, X, s, steps, log_every=0, row_block=2048):
         engine._require_cuda_param(t, name)                    # fp32 only: bf16 tables are refused here
     L = _lib.load()
     U, V, mU, vU, mV, vV = binding.tensors()
-    src = _RowSource(U, V, X, None, row_block, "the population fit")
+    src = RowBlocks(U, V, X, None, row_block, "the population fit")
     n, m, d, dev = src.n, src.m, U.shape[1], src.dev
     if m < 2:
         raise ValueError("the population risk needs at least two items (m >= 2)")

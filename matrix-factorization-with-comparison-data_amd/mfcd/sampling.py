@@ -16,13 +16,16 @@ import torch
 from . import _lib
 from . import cluster as _cluster
 from . import topk as _topk
+from .rows import resolve
 
 LAW_UNIFORM, LAW_ITEM_CDF, LAW_LISTS, LAW_GROUPS = 0, 1, 2, 3
 DEVICE_STRATEGIES = ("random", "margin", "popularity", "variance", "proximity", "top_k", "svd", "cluster")
 
 
-def _dense_on(X, device):
-    return X.detach().to(device=device, dtype=torch.float32).contiguous()
+def _on(X, device):
+    """X on the device in the form the kernels read: contiguous, a dense X in fp32, factors as they are kept."""
+    X = resolve(X, device)
+    return X.map(torch.Tensor.contiguous) if X.factored else X.map(lambda t: t.float().contiguous())
 
 
 class _Law:
@@ -72,11 +75,11 @@ def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha
     if strategy == "margin":
         c.use_margin = 1
         c.margin = float(_gd._margin_threshold(X, num_triplets))
-        if _lib.is_factored(X):
-            A, B = X.A.to(device).contiguous(), X.B.to(device).contiguous()
-            c.A, c.B, c.dx = law.hold(A), law.hold(B), A.shape[1]
+        Xd = _on(X, device)
+        if Xd.factored:
+            c.A, c.B, c.dx = law.hold(Xd.A), law.hold(Xd.B), Xd.d
         else:
-            c.X = law.hold(_dense_on(X, device))
+            c.X = law.hold(Xd.dense)
         law.budget, law.block_multiple = int(max_attempts), 500
         law.report = lambda got, attempts: _gd._report_short_margin(X, got, num_triplets, c.margin, attempts)
         return law
@@ -86,7 +89,7 @@ def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha
             c.pair_rule = 0
         else:                                                            # generation_data.py:90-91
             var = _gd._factored_column_variances(X).numpy() if _lib.is_factored(X) else \
-                torch.var(_dense_on(X, device), dim=0).double().cpu().numpy()
+                torch.var(_on(X, device).dense, dim=0).double().cpu().numpy()
             probs = var / var.sum()
             c.pair_rule = 1
             if not np.isfinite(probs).all() or (probs < 0).any():      # e.g. one user: the unbiased variance is NaN
@@ -98,8 +101,8 @@ def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha
         return law
     if strategy in ("proximity", "top_k"):
         # a factored X never becomes dense: its lists come from mfcd_topk_rows over the factors (one call, all n rows)
-        fac = (X.A.to(device).contiguous(), X.B.to(device).contiguous()) if _lib.is_factored(X) else None
-        Xd = None if fac else _dense_on(X, device)
+        Xd = _on(X, device)
+        fac, Xd = ((Xd.A, Xd.B), None) if Xd.factored else (None, Xd.dense)
         if strategy == "proximity":
             kk = int(_gd._proximity_k(m, k))
             if fac:
@@ -172,13 +175,13 @@ def run_law(law, num_triplets, exclude=None, seed=0):
         ws_bytes = L.mfcd_sample_workspace_bytes(A, barred.numel())
         if ws_bytes == 0:
             raise _lib.MfcdError("triplet request too large for one sampling block")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        ws = _lib.workspace(ws_bytes, device)
         keys = torch.empty(need, dtype=torch.int64, device=device)
         counts = torch.zeros(2, dtype=torch.int64, device=device)
         part = out[have:]
         _lib.check(L.mfcd_sample_triplets(ctypes.byref(law.c), _lib.ptr(barred) if barred.numel() else None,
                                           barred.numel(), attempts, A, int(seed) & 0xFFFFFFFFFFFFFFFF, need,
-                                          _lib.ptr(part), _lib.ptr(keys), _lib.ptr(counts), _lib.ptr(ws), ws_bytes,
+                                          _lib.ptr(part), _lib.ptr(keys), _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
                                           stream))
         got, used = (int(v) for v in counts.tolist())
         used = -(-used // law.block_multiple) * law.block_multiple

@@ -9,51 +9,26 @@ import numpy as np
 import torch
 
 from . import _lib
+from .rows import resolve
 
 _ENDS = {"best": 1, "worst": 2, "both": 3}
-_ws = {}
 
 
 def max_k():
     return int(_lib.load().mfcd_topk_max_k())
 
 
-def _workspace(nbytes, device):
-    buf = _ws.get(device)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-        _ws[device] = buf
-    return buf
-
-
-def _gpu_f32(t, name):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise _lib.MfcdError(f"{name} must be a GPU tensor (got {'a CPU tensor' if torch.is_tensor(t) else type(t).__name__}; "
-                             "there is no CPU fallback)")
-    if t.dim() != 2:
-        raise ValueError(f"{name} must have two dimensions, got {tuple(t.shape)}")
-    return t.detach().float()
-
-
 def _resolve(X, device):
-    """→ (dense or None, A or None, B or None, n, m, d, device)."""
-    if torch.is_tensor(X):
-        Xd = _gpu_f32(X, "X")
-        if Xd.stride(1) != 1 or Xd.stride(0) < Xd.shape[1]:
-            Xd = Xd.contiguous()
-        return Xd, None, None, Xd.shape[0], Xd.shape[1], 0, Xd.device
-    if isinstance(X, (tuple, list)) and len(X) == 2:
-        A, B = _gpu_f32(X[0], "A").contiguous(), _gpu_f32(X[1], "B").contiguous()
-    elif _lib.is_factored(X):                      # a host object, its factors move per call
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if dev.type != "cuda":
-            raise _lib.MfcdError("topk_rows needs a GPU device (there is no CPU fallback)")
-        A, B = X.A.to(dev).float().contiguous(), X.B.to(dev).float().contiguous()
+    """→ (dense or None, A or None, B or None, n, m, d, device): fp32, factors contiguous, a dense X with unit column
+    stride and rows that do not overlap (its row stride may exceed m)."""
+    X = resolve(X, device, gpu_only=True)
+    if X.factored:
+        X = X.map(lambda t: t.float().contiguous())
     else:
-        raise TypeError("X must be a dense GPU tensor, a FactoredMatrix or a pair (A, B) of GPU tensors")
-    if A.shape[1] != B.shape[1] or A.device != B.device:
-        raise ValueError(f"factors do not match: A {tuple(A.shape)} on {A.device}, B {tuple(B.shape)} on {B.device}")
-    return None, A, B, A.shape[0], B.shape[0], A.shape[1], A.device
+        X = X.map(torch.Tensor.float)
+        if X.dense.stride(1) != 1 or X.dense.stride(0) < X.m:
+            X = X.map(torch.Tensor.contiguous)
+    return X.dense, X.A, X.B, X.n, X.m, X.d, X.device
 
 
 def exclude_csr(pairs, row_ids, n, m, device):
@@ -125,7 +100,7 @@ def topk_rows(X, k, rows=None, ends="best", exclude=None, values=False, device=N
         nbytes = L.mfcd_topk_rows_workspace_bytes(nrows, m, d, k, e)
         if nbytes == 0:
             raise _lib.MfcdError(f"topk_rows: sizes out of range (rows {nrows}, m {m}, d {d}, k {k})")
-        ws = _workspace(nbytes, dev)
+        ws = _lib.workspace(nbytes, dev)
         _lib.check(L.mfcd_topk_rows(Xd.data_ptr() if Xd is not None else None, Xd.stride(0) if Xd is not None else 0,
                                     _lib.ptr(A), _lib.ptr(B), d,
                                     _lib.ptr(ids), nrows, n, m, k, e, _lib.ptr(off), _lib.ptr(items), _lib.ptr(bi),

@@ -457,3 +457,54 @@ def test_dataset_rows_and_lazy_data_list():
     assert dataset_records(ds)[0].tolist() == [1.0, 1.0, 1.0, 0.5] and ds[0] == (1, 1, 1, 0.5)
     ds.data = [(2, 2, 3, 1.0)]
     assert len(ds) == 1 and dataset_records(ds).tolist() == [[2.0, 2.0, 3.0, 1.0]]
+
+
+class _OnGpu(torch.Tensor):
+    """A CPU tensor that answers `is_cuda`: `row_pair` reads shapes, dtypes and strides and touches no memory."""
+    is_cuda = property(lambda self: True)
+
+
+def test_row_pair_checks_and_leading_dimensions():
+    from mfcd import _lib
+    m = 5
+    A, X = torch.zeros(3, m), torch.ones(3, m)
+    for a, x in ((A, X),                                                    # CPU tensors
+                 (A.as_subclass(_OnGpu), X),
+                 (A.as_subclass(_OnGpu), X.double().as_subclass(_OnGpu)),   # dtype mismatch
+                 (A.as_subclass(_OnGpu), X[:, :-1].as_subclass(_OnGpu)),    # shape mismatch
+                 (A.as_subclass(_OnGpu), None)):
+        with pytest.raises(_lib.MfcdError, match=r"somebody needs two float32 GPU matrices of the same shape \(no CPU fallback\)"):
+            _lib.row_pair(a, x, "somebody")
+    wide = torch.arange(3 * 2 * m, dtype=torch.float32).reshape(3, 2 * m).as_subclass(_OnGpu)
+    a, x, rows, cols, lda, ldx = _lib.row_pair(wide[:, :m], X.as_subclass(_OnGpu), "somebody")
+    assert (rows, cols, lda, ldx) == (3, m, 2 * m, m) and a.data_ptr() == wide.data_ptr()       # a view: no copy
+    a, x, rows, cols, lda, ldx = _lib.row_pair(wide[1:2, :m], X[1:2].as_subclass(_OnGpu), "somebody")
+    assert (rows, cols, lda, ldx) == (1, m, m, m)                          # one row: its stride says nothing
+    a, x, rows, cols, lda, ldx = _lib.row_pair(wide[:, 0:2 * m:2], X.as_subclass(_OnGpu), "somebody")
+    assert (lda, ldx) == (m, m) and a.is_contiguous() and torch.equal(a, wide[:, 0:2 * m:2])   # column stride 2: copied
+
+
+def test_score_matrix_resolver_on_host_objects():
+    from mfcd import rows, topk
+    for bad in (None, 3.5, "X", [1, 2, 3], object()):
+        with pytest.raises(TypeError, match="X must be a dense GPU tensor, a FactoredMatrix or a pair"):
+            rows.resolve(bad)
+        with pytest.raises(TypeError, match="X must be a dense GPU tensor, a FactoredMatrix or a pair"):
+            topk.topk_rows(bad, 1)
+
+    class Duck:
+        A, B, shape = torch.zeros(7, 3, dtype=torch.float64), torch.ones(4, 3, dtype=torch.float64), (7, 4)
+
+    X = rows.resolve(Duck())
+    assert (X.n, X.m, X.d, X.factored, X.dense) == (7, 4, 3, True, None) and X.device.type == "cpu"
+    assert X.A.dtype == torch.float64                                       # moved and checked, never converted
+    assert torch.equal(X.rows(2, 5), Duck.A[2:5] @ Duck.B.t()) and X.rows(torch.tensor([6, 0, 6])).shape == (3, 4)
+    D = rows.resolve(torch.arange(12.0).reshape(3, 4))
+    assert (D.n, D.m, D.d, D.factored) == (3, 4, 0, False) and torch.equal(D.rows(1, 3), D.dense[1:3])
+    P = rows.resolve((Duck.A, Duck.B))
+    assert (P.n, P.m, P.d) == (7, 4, 3)
+    with pytest.raises(ValueError):
+        rows.resolve((Duck.A, torch.ones(4, 2)))                            # inner dimensions differ
+    with pytest.raises(ValueError):
+        rows.resolve(torch.zeros(5))
+    assert rows.blocks(70, 32) == [(0, 32), (32, 64), (64, 70)] and rows.blocks(0, 32) == []

@@ -361,3 +361,28 @@ def test_fit_population_refuses_bf16_tables(dev):
         pairs.fit_population((model, opt), X, 1.0, 2)
     with pytest.raises(_lib.MfcdError):
         S.population_risk(model, X)
+
+
+def test_population_risk_block_loop_at_a_ragged_last_block_and_a_repeated_user(dev):
+    """n = 70, m = 130, d = 8 with row_block = 32 (blocks of 32, 32 and 6 or 8 rows) and = 70, every user and users with a
+    repeat, dense and factored X: value and table gradients against the f64 model, under the bounds of the test above;
+    the values at the two row blocks against each other under the same RTOL / ATOL (the score GEMMs may round
+    differently, so not bits)."""
+    n, m, d, s = 70, 130, 8, 0.7
+    S, model, F, Xd = _problem(n, m, d, 23, dev)
+    Xh = Xd.cpu().numpy().astype(np.float64)
+    U, V = model.U.detach().cpu().numpy(), model.V.detach().cpu().numpy()
+    users = list(range(n - 1, -1, -1)) + [3, 3]
+    for sel in (None, users):
+        want = GM.population_risk(U, V, Xh, s, sel)
+        for X, kind in ((Xd, "dense"), (F, "factored")):
+            risks = {}
+            for rb in (32, 70):
+                what = f"{kind} X, row_block={rb}, {'every user' if sel is None else 'users with a repeat'}"
+                model.zero_grad()
+                risk = S.population_risk(model, X, s, users=sel, row_block=rb)
+                risks[rb] = float(risk.detach())
+                np.testing.assert_allclose(risks[rb], want, rtol=RTOL, atol=ATOL, err_msg=what)
+                risk.backward()
+                check_tables(model, Xh, s, sel, what)
+            np.testing.assert_allclose(risks[32], risks[70], rtol=RTOL, atol=ATOL, err_msg=kind)

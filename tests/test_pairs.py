@@ -298,3 +298,45 @@ def test_metrics_of_the_true_and_the_negated_model(setup, dev):
     assert (neg["kendall_tau_per_user"] == -1.0).all() and neg["kendall_tau"] == -1.0
     assert neg["pairwise_accuracy"] == 0.0
     assert neg["expected_log_likelihood"] < res["expected_log_likelihood"] <= 0.0
+
+
+def test_block_loop_at_a_ragged_last_block_and_a_repeated_user(dev):
+    """n = 70, m = 130, d = 8, row_block = 32 (blocks of 32, 32 and 6 rows), users with a repeat.  Exact: every block
+    is what `pair_stats_rows` gives for the products formed here as the function forms them, in the order of `users`.
+    Across row_block in {32, 70} the score GEMMs may round differently, so that comparison carries the tolerances of
+    the tests above: 1e-3 on the two values made of counts (a pair whose order flips moves tau by 2 / n0 = 2.4e-4), the
+    module's RTOL / ATOL on the sums.  Dense against factored X: bits where the products are bit-equal, else 1e-6."""
+    import generation_data as gd
+    import structure as S
+    from mfcd import pairs
+    n, m, d, rb = 70, 130, 8, 32
+    g = torch.Generator().manual_seed(12)
+    F = gd.FactoredMatrix(torch.randn(n, d, generator=g) / 2, torch.randn(m, d, generator=g) / 2)
+    Xd = F.dense(dev)
+    torch.manual_seed(12)
+    model = S.MatrixFactorization(n, m, d).to(dev)
+    U, V = model.U.data, model.V.data
+    users = list(range(n - 1, -1, -1)) + [3, 3]                              # 72 rows: blocks of 32, 32 and 8
+    for sel in (None, users):
+        ids = torch.arange(n, device=dev) if sel is None else torch.tensor(sel, device=dev)
+        for X, truth in ((Xd, lambda i: Xd[i]), (F, lambda i: F.A.to(dev)[i] @ F.B.to(dev).t())):
+            res = {b: S.compute_pairwise_metrics(model, X, s=0.5, users=sel, row_block=b) for b in (rb, n)}
+            parts = [pairs.pair_stats_rows(U[ids[r0:r0 + rb]] @ V.t(), truth(ids[r0:r0 + rb]), 0.5, "both")
+                     for r0 in range(0, len(ids), rb)]
+            want = pairs.pairwise_from_counts(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), m)
+            want["expected_log_likelihood"], want["bayes_log_likelihood"] = -want.pop("risk"), -want.pop("bayes_risk")
+            for k in KEYS:
+                assert res[rb][k + "_per_user"].tobytes() == want[k].tobytes(), k
+                counted = k in ("kendall_tau", "pairwise_accuracy")
+                np.testing.assert_allclose(res[rb][k + "_per_user"], res[n][k + "_per_user"], err_msg=k,
+                                           rtol=0 if counted else RTOL, atol=1e-3 if counted else ATOL)
+            if sel is not None:
+                assert all(res[rb][k + "_per_user"][-1] == res[rb][k + "_per_user"][-2] for k in KEYS)
+    dense, fact = (S.compute_pairwise_metrics(model, X, s=0.5, row_block=rb) for X in (Xd, F))
+    same_bits = all(torch.equal(F.A.to(dev)[r0:r0 + rb] @ F.B.to(dev).t(), Xd[r0:r0 + rb]) for r0 in range(0, n, rb))
+    for k in KEYS:
+        a, b = dense[k + "_per_user"], fact[k + "_per_user"]
+        if same_bits:
+            assert a.tobytes() == b.tobytes(), k
+        else:
+            np.testing.assert_allclose(a, b, rtol=0, atol=1e-6, err_msg=k)
