@@ -334,13 +334,14 @@ extern "C" int mfcd_train_steps_big(float *U, float *V, float *mU, float *vU, fl
     float *terms = (float *)((char *)sc_dev + align_up(sizeof(StepScalars) * (size_t)K));
     u64 *mailbox = (u64 *)((char *)terms + align_up(sizeof(float) * (size_t)N));
     std::vector<StepScalars> sc((size_t)K);
-    for (int k = 0; k < K; ++k) sc[(size_t)k] = step_scalars(lr, beta1, beta2, step0 + k + 1);
+    const AdamHyper h{lr, beta1, beta2, eps, weight_decay};
+    for (int k = 0; k < K; ++k) sc[(size_t)k] = step_scalars(h, step0 + k + 1);
     MFCD_HIP_TRY(hipMemcpyAsync(sc_dev, sc.data(), sizeof(StepScalars) * (size_t)K, hipMemcpyHostToDevice, st));
     MFCD_HIP_TRY(hipStreamSynchronize(st));          // (the table is on this call's stack)
     MFCD_HIP_TRY(hipMemsetAsync(status, 0, 256, st));
     MFCD_HIP_TRY(hipMemsetAsync(mailbox, 0, sizeof(u64) * (size_t)N * 3 * kD, st));
     BigArgs a{U, V, mU, vU, mV, vV, samples, (long long)N, B, K, n, m, sc_dev,
-              adam_static(beta1, beta2, eps, weight_decay), mailbox, terms, status};
+              adam_static(h), mailbox, terms, status};
     hipLaunchKernelGGL(kernel, dim3(kWaves / 4), dim3(256), kLds, st, a);
     MFCD_HIP_TRY(hipGetLastError());
     if (loss_per_step) return mfcd_detail::launch_batch_means(terms, nullptr, N, B, loss_per_step, st);

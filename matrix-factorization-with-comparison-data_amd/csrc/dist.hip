@@ -18,6 +18,22 @@ using mfcd_detail::make_plan;
 // for the "allgather" exchange; same protocol, same results).
 namespace {
 
+// One multi-GPU training call as its extern "C" entry (mfcd_dp_train_steps*, mfcd_shard_train_steps*) received it;
+// MFCD_DIST_CALL packs the arguments of those four entries, which share their parameter names
+struct DistCall {
+    AdamTables t;
+    const mfcd_sample *samples;
+    int64_t N, step0;
+    int B, rank, world, n, m, d;
+    AdamHyper h;
+    float *loss_per_step;
+    void *workspace, *comm, *stream;
+    size_t workspace_bytes;
+};
+#define MFCD_DIST_CALL                                                                                      \
+    DistCall{{U, V, mU, vU, mV, vV}, samples, N, step0, B, rank, world, n, m, d, {lr, beta1, beta2, eps, weight_decay}, \
+             loss_per_step, workspace, comm, stream, workspace_bytes}
+
 // Data-parallel exchange slot of one rank for one step: B interleaved pairs {g_t, BCE term_t}; one wave per slot entry.
 // Entries past the rank's (possibly short or empty) shard are written as {0, 0} so that the gathered buffer of a
 // step is fully defined.
@@ -95,25 +111,27 @@ extern "C" size_t mfcd_dp_workspace_bytes(int64_t N, int B, int world, int n, in
 }
 
 namespace {
-// fp32 or bf16 factor tables (BASELINE configs[2]); the moments, the coefficients on the wire and the arithmetic are fp32
-template <typename TP>
-int run_dp_train_steps(TP *U, TP *V, float *mU, float *vU, float *mV, float *vV, const mfcd_sample *samples, int64_t N,
-                       int B, int rank, int world, int64_t step0, int n, int m, int d, double lr, double beta1,
-                       double beta2, double eps, double weight_decay, float *loss_per_step, void *workspace,
-                       size_t workspace_bytes, void *comm, void *stream)
+template <typename TP>   // fp32 or bf16 factor tables; the moments, the coefficients on the wire and the arithmetic are fp32
+int run_dp_train_steps(const DistCall &c)
 {
+    TP *U = (TP *)c.t.U, *V = (TP *)c.t.V;
+    float *mU = c.t.mU, *vU = c.t.vU, *mV = c.t.mV, *vV = c.t.vV, *loss_per_step = c.loss_per_step;
+    const mfcd_sample *samples = c.samples;
+    const int64_t N = c.N, step0 = c.step0;
+    const int B = c.B, rank = c.rank, world = c.world, n = c.n, m = c.m, d = c.d;
+    void *workspace = c.workspace, *comm = c.comm;
     if (int rc = check_common(U, V, n, m, d)) return rc;
     if (!mU || !vU || !mV || !vV || N < 0 || B <= 0 || world < 1 || rank < 0 || rank >= world || step0 < 0)
         return MFCD_EINVAL;
     if (N == 0) return 0;
     if (!samples || !workspace) return MFCD_EINVAL;
-    if (workspace_bytes < mfcd_dp_workspace_bytes(N, B, world, n, m, d)) return MFCD_EWORKSPACE;
+    if (c.workspace_bytes < mfcd_dp_workspace_bytes(N, B, world, n, m, d)) return MFCD_EWORKSPACE;
     const mfcd_detail::RcclApi *R = nullptr;
     if (comm) {
         R = &mfcd_detail::rccl();
         if (!R->ok) return MFCD_ERCCL;
     }
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)c.stream;
     const int64_t Bg = (int64_t)B * world, nsteps = (N + Bg - 1) / Bg;
     char *ws = (char *)workspace + kStatusBytes;
     TP *Ualt = (TP *)ws;
@@ -142,7 +160,7 @@ int run_dp_train_steps(TP *U, TP *V, float *mU, float *vU, float *mV, float *vV,
             if (R->AllGather(xk + (size_t)rank * B, xk, (size_t)B * 2, ncclFloat, (ncclComm_t)comm, st) != ncclSuccess)
                 return MFCD_ERCCL;
         }
-        const AdamConst ac = adam_const(lr, beta1, beta2, eps, weight_decay, step0 + k + 1);
+        const AdamConst ac = adam_const(c.h, step0 + k + 1);
         launch_streaming_step<0, TP>(pl, st, Uc, Vc, even ? Ualt : U, even ? Valt : V, mU, vU, mV, vV, samples + lo,
                                      (const float *)xk, nglob, 0.0f, n, m, d, ac, nullptr, nullptr, nullptr, 2);
     }
@@ -165,8 +183,7 @@ extern "C" int mfcd_dp_train_steps(float *U, float *V, float *mU, float *vU, flo
                                    double weight_decay, float *loss_per_step, void *workspace, size_t workspace_bytes,
                                    void *comm, void *stream)
 {
-    return run_dp_train_steps<float>(U, V, mU, vU, mV, vV, samples, N, B, rank, world, step0, n, m, d, lr, beta1, beta2,
-                                     eps, weight_decay, loss_per_step, workspace, workspace_bytes, comm, stream);
+    return run_dp_train_steps<float>(MFCD_DIST_CALL);
 }
 
 extern "C" int mfcd_dp_train_steps_bf16(uint16_t *U, uint16_t *V, float *mU, float *vU, float *mV, float *vV,
@@ -175,9 +192,7 @@ extern "C" int mfcd_dp_train_steps_bf16(uint16_t *U, uint16_t *V, float *mU, flo
                                         double weight_decay, float *loss_per_step, void *workspace,
                                         size_t workspace_bytes, void *comm, void *stream)
 {
-    return run_dp_train_steps<mfcd_bf16>((mfcd_bf16 *)U, (mfcd_bf16 *)V, mU, vU, mV, vV, samples, N, B, rank, world, step0,
-                                         n, m, d, lr, beta1, beta2, eps, weight_decay, loss_per_step, workspace,
-                                         workspace_bytes, comm, stream);
+    return run_dp_train_steps<mfcd_bf16>(MFCD_DIST_CALL);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -280,6 +295,8 @@ void shard_range(int rows, int rank, int world, int *lo, int *hi)
     *hi = (int)((int64_t)rows * (rank + 1) / world);
 }
 
+struct ShardRows { int u_lo, u_hi, v_lo, v_hi; };   // one rank holds rows [u_lo, u_hi) of U and [v_lo, v_hi) of V
+
 size_t shard_xbuf_bytes(int B, int d) { return align_up(sizeof(float) * 3 * (size_t)B * d); }
 
 // BCE terms of a batch from the exchange buffer alone: what workgroup 0 of the MODE 3 step records, for a rank whose
@@ -334,7 +351,7 @@ extern "C" int mfcd_shard_pack_ahead(const float *U_shard, const float *V_shard,
         step < 1)
         return MFCD_EINVAL;
     if ((u_hi > u_lo && (!U_shard || !mU || !vU)) || (v_hi > v_lo && (!V_shard || !mV || !vV))) return MFCD_EINVAL;
-    const AdamConst ac = adam_const(lr, beta1, beta2, eps, weight_decay, step);
+    const AdamConst ac = adam_const({lr, beta1, beta2, eps, weight_decay}, step);
     hipLaunchKernelGGL(shard_pack_ahead_kernel<float>, dim3((3 * B + 3) / 4), dim3(256), 0, (hipStream_t)stream, U_shard, V_shard,
                        mU, vU, mV, vV, next_batch, Bk, B, d, u_lo, u_hi - u_lo, v_lo, v_hi - v_lo, ac, xbuf, 0);
     MFCD_HIP_TRY(hipGetLastError());
@@ -355,12 +372,13 @@ extern "C" int mfcd_shard_pack(const float *U_shard, const float *V_shard, const
 
 namespace {
 template <typename TP>
-int shard_apply_t(TP *U_shard, TP *V_shard, float *mU, float *vU, float *mV, float *vV, const mfcd_sample *batch, int Bk,
-                  int B, const float *xbuf, int64_t step, int d, int u_lo, int u_hi, int v_lo, int v_hi, double lr,
-                  double beta1, double beta2, double eps, double weight_decay, float *loss_terms, void *stream)
+int shard_apply_t(const AdamTables &t, const mfcd_sample *batch, int Bk, int B, const float *xbuf, int64_t step, int d,
+                  const ShardRows &rows, const AdamHyper &h, float *loss_terms, void *stream)
 {
+    TP *U_shard = (TP *)t.U, *V_shard = (TP *)t.V;
+    float *mU = t.mU, *vU = t.vU, *mV = t.mV, *vV = t.vV;
     if (!batch || !xbuf || Bk <= 0 || B <= 0 || Bk > B || d <= 0 || d > MFCD_MAX_D || step < 1) return MFCD_EINVAL;
-    const int nu = u_hi - u_lo, nv = v_hi - v_lo;
+    const int nu = rows.u_hi - rows.u_lo, nv = rows.v_hi - rows.v_lo;
     if (nu < 0 || nv < 0) return MFCD_EINVAL;
     if (nu + nv == 0) {   // this rank owns no row (world > rows): nothing to update, only the step's loss terms
         if (loss_terms) {
@@ -374,9 +392,9 @@ int shard_apply_t(TP *U_shard, TP *V_shard, float *mU, float *vU, float *mV, flo
     const void *ptrs[] = {U_shard, V_shard, mU, vU, mV, vV, xbuf};
     // an empty table side is legal (a rank may own rows of one table only when world > rows): one dummy row count
     const Plan pl = make_plan(ptrs, 7, nu > 0 ? nu : 0, nv > 0 ? nv : 0, d);
-    const AdamConst ac = adam_const(lr, beta1, beta2, eps, weight_decay, step);
+    const AdamConst ac = adam_const(h, step);
     launch_streaming_step<3, TP>(pl, (hipStream_t)stream, U_shard, V_shard, U_shard, V_shard, mU, vU, mV, vV, batch, xbuf,
-                                 Bk, 1.0f / (float)Bk, nu, nv, d, ac, loss_terms, nullptr, nullptr, B, u_lo, v_lo);
+                                 Bk, 1.0f / (float)Bk, nu, nv, d, ac, loss_terms, nullptr, nullptr, B, rows.u_lo, rows.v_lo);
     MFCD_HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -387,24 +405,25 @@ extern "C" int mfcd_shard_apply(float *U_shard, float *V_shard, float *mU, float
                                 int u_lo, int u_hi, int v_lo, int v_hi, double lr, double beta1, double beta2,
                                 double eps, double weight_decay, float *loss_terms, void *stream)
 {
-    return shard_apply_t<float>(U_shard, V_shard, mU, vU, mV, vV, batch, Bk, B, xbuf, step, d, u_lo, u_hi, v_lo, v_hi, lr,
-                                beta1, beta2, eps, weight_decay, loss_terms, stream);
+    return shard_apply_t<float>({U_shard, V_shard, mU, vU, mV, vV}, batch, Bk, B, xbuf, step, d, {u_lo, u_hi, v_lo, v_hi},
+                                {lr, beta1, beta2, eps, weight_decay}, loss_terms, stream);
 }
 
 namespace {
-// fp32 or bf16 factor shards (BASELINE configs[2]'s storage); the exchange buffer, the moments and the arithmetic are fp32
-template <typename TP>
-int run_shard_train_steps(TP *U, TP *V, float *mU, float *vU, float *mV, float *vV, const mfcd_sample *samples, int64_t N,
-                          int B, int rank, int world, int64_t step0, int n, int m, int d, double lr, double beta1,
-                          double beta2, double eps, double weight_decay, float *loss_per_step, void *workspace,
-                          size_t workspace_bytes, void *comm, void *stream)
+template <typename TP>   // fp32 or bf16 factor shards; the exchange buffer, the moments and the arithmetic are fp32
+int run_shard_train_steps(const DistCall &c)
 {
+    const AdamTables &t = c.t;
+    const mfcd_sample *samples = c.samples;
+    const int64_t N = c.N, step0 = c.step0;
+    const int B = c.B, rank = c.rank, world = c.world, n = c.n, m = c.m, d = c.d;
+    void *workspace = c.workspace, *comm = c.comm, *stream = c.stream;
     if (n <= 0 || m <= 0 || d <= 0 || d > MFCD_MAX_D || N < 0 || B <= 0 || world < 1 || rank < 0 || rank >= world ||
         step0 < 0)
         return MFCD_EINVAL;
     if (N == 0) return 0;
-    if (!samples || !workspace || !U || !V || !mU || !vU || !mV || !vV) return MFCD_EINVAL;
-    if (workspace_bytes < mfcd_shard_workspace_bytes(N, B, d)) return MFCD_EWORKSPACE;
+    if (!samples || !workspace || !t.U || !t.V || !t.mU || !t.vU || !t.mV || !t.vV) return MFCD_EINVAL;
+    if (c.workspace_bytes < mfcd_shard_workspace_bytes(N, B, d)) return MFCD_EWORKSPACE;
     const mfcd_detail::RcclApi *R = nullptr;
     if (comm) {
         R = &mfcd_detail::rccl();
@@ -419,22 +438,23 @@ int run_shard_train_steps(TP *U, TP *V, float *mU, float *vU, float *mV, float *
     // with a communicator the table pointers are this rank's SHARDS; without one they are the FULL tables and this
     // process plays every rank in turn (single-process rehearsal of any world size; exact, the protocol is the same)
     const int r0 = comm ? rank : 0, r1 = comm ? rank + 1 : world;
-    auto range = [&](int r, int &ul, int &uh, int &vl, int &vh, int64_t &uo, int64_t &vo) {
-        shard_range(n, r, world, &ul, &uh);
-        shard_range(m, r, world, &vl, &vh);
-        uo = comm ? 0 : (int64_t)ul * d;
-        vo = comm ? 0 : (int64_t)vl * d;
+    struct RankShard : ShardRows { AdamTables t; };   // a rank's rows and where they start
+    auto shard_of = [&](int r) {
+        RankShard s{{}, t};
+        shard_range(n, r, world, &s.u_lo, &s.u_hi);
+        shard_range(m, r, world, &s.v_lo, &s.v_hi);
+        if (!comm) s.t = t.from<TP>((int64_t)s.u_lo * d, (int64_t)s.v_lo * d);
+        return s;
     };
     // rows of batch k as they are NOW into xbuf (after step k-1 has run)
     auto pack_now = [&](int64_t k, float *xbuf) -> int {
         const int64_t off = k * B;
         const int Bk = (int)((N - off) < B ? (N - off) : B);
         for (int r = r0; r < r1; ++r) {
-            int ul, uh, vl, vh;
-            int64_t uo, vo;
-            range(r, ul, uh, vl, vh, uo, vo);
-            hipLaunchKernelGGL(shard_pack_kernel<TP>, dim3((3 * B + 3) / 4), dim3(256), 0, st, U + uo, V + vo, samples + off, Bk,
-                               B, d, ul, uh - ul, vl, vh - vl, xbuf, (comm || r == r0) ? 0 : 1);
+            const RankShard s = shard_of(r);
+            hipLaunchKernelGGL(shard_pack_kernel<TP>, dim3((3 * B + 3) / 4), dim3(256), 0, st, (const TP *)s.t.U,
+                               (const TP *)s.t.V, samples + off, Bk, B, d, s.u_lo, s.u_hi - s.u_lo, s.v_lo, s.v_hi - s.v_lo,
+                               xbuf, (comm || r == r0) ? 0 : 1);
         }
         MFCD_HIP_TRY(hipGetLastError());
         return 0;
@@ -443,14 +463,13 @@ int run_shard_train_steps(TP *U, TP *V, float *mU, float *vU, float *mV, float *
     auto pack_ahead = [&](int64_t k, float *xbuf) -> int {
         const int64_t off = (k + 1) * B;
         const int Bk = (int)((N - off) < B ? (N - off) : B);
-        const AdamConst ac = adam_const(lr, beta1, beta2, eps, weight_decay, step0 + k + 1);
+        const AdamConst ac = adam_const(c.h, step0 + k + 1);
         for (int r = r0; r < r1; ++r) {
-            int ul, uh, vl, vh;
-            int64_t uo, vo;
-            range(r, ul, uh, vl, vh, uo, vo);
-            hipLaunchKernelGGL(shard_pack_ahead_kernel<TP>, dim3((3 * B + 3) / 4), dim3(256), 0, st, U + uo, V + vo, mU + uo,
-                               vU + uo, mV + vo, vV + vo, samples + off, Bk, B, d, ul, uh - ul, vl, vh - vl, ac, xbuf,
-                               (comm || r == r0) ? 0 : 1);
+            const RankShard s = shard_of(r);
+            hipLaunchKernelGGL(shard_pack_ahead_kernel<TP>, dim3((3 * B + 3) / 4), dim3(256), 0, st, (const TP *)s.t.U,
+                               (const TP *)s.t.V, (const float *)s.t.mU, (const float *)s.t.vU, (const float *)s.t.mV,
+                               (const float *)s.t.vV, samples + off, Bk, B, d, s.u_lo, s.u_hi - s.u_lo, s.v_lo,
+                               s.v_hi - s.v_lo, ac, xbuf, (comm || r == r0) ? 0 : 1);
         }
         MFCD_HIP_TRY(hipGetLastError());
         return 0;
@@ -459,11 +478,8 @@ int run_shard_train_steps(TP *U, TP *V, float *mU, float *vU, float *mV, float *
         const int64_t off = k * B;
         const int Bk = (int)((N - off) < B ? (N - off) : B);
         for (int r = r0; r < r1; ++r) {
-            int ul, uh, vl, vh;
-            int64_t uo, vo;
-            range(r, ul, uh, vl, vh, uo, vo);
-            if (int rc = shard_apply_t<TP>(U + uo, V + vo, mU + uo, vU + uo, mV + vo, vV + vo, samples + off, Bk, B, xbuf,
-                                           step0 + k + 1, d, ul, uh, vl, vh, lr, beta1, beta2, eps, weight_decay,
+            const RankShard s = shard_of(r);
+            if (int rc = shard_apply_t<TP>(s.t, samples + off, Bk, B, xbuf, step0 + k + 1, d, s, c.h,
                                            r == r0 ? terms + off : nullptr, stream))
                 return rc;
         }
@@ -554,7 +570,7 @@ int run_shard_train_steps(TP *U, TP *V, float *mU, float *vU, float *mV, float *
         }
         if (rc) return rc;
     }
-    if (loss_per_step) return mfcd_detail::launch_batch_means(terms, nullptr, N, B, loss_per_step, st);
+    if (c.loss_per_step) return mfcd_detail::launch_batch_means(terms, nullptr, N, B, c.loss_per_step, st);
     return 0;
 }
 }  // namespace
@@ -565,8 +581,7 @@ extern "C" int mfcd_shard_train_steps(float *U, float *V, float *mU, float *vU, 
                                       double weight_decay, float *loss_per_step, void *workspace, size_t workspace_bytes,
                                       void *comm, void *stream)
 {
-    return run_shard_train_steps<float>(U, V, mU, vU, mV, vV, samples, N, B, rank, world, step0, n, m, d, lr, beta1, beta2,
-                                        eps, weight_decay, loss_per_step, workspace, workspace_bytes, comm, stream);
+    return run_shard_train_steps<float>(MFCD_DIST_CALL);
 }
 
 extern "C" int mfcd_shard_train_steps_bf16(uint16_t *U, uint16_t *V, float *mU, float *vU, float *mV, float *vV,
@@ -575,7 +590,5 @@ extern "C" int mfcd_shard_train_steps_bf16(uint16_t *U, uint16_t *V, float *mU, 
                                            double eps, double weight_decay, float *loss_per_step, void *workspace,
                                            size_t workspace_bytes, void *comm, void *stream)
 {
-    return run_shard_train_steps<mfcd_bf16>((mfcd_bf16 *)U, (mfcd_bf16 *)V, mU, vU, mV, vV, samples, N, B, rank, world,
-                                            step0, n, m, d, lr, beta1, beta2, eps, weight_decay, loss_per_step, workspace,
-                                            workspace_bytes, comm, stream);
+    return run_shard_train_steps<mfcd_bf16>(MFCD_DIST_CALL);
 }

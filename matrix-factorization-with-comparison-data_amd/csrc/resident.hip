@@ -107,33 +107,27 @@ static int resident_blocks_per_cu(int d, int Q, int look, int fast, int bf16)
     return occ;
 }
 
-// Resident-path plan: Q registers per array, NW owner waves, or ok=false when the path does not apply.
-// Every wave of the grid must be resident at once (waves wait on each other).  The wave count per CU the design wants
-// is 16 for Q <= 2 (4 workgroups of 4 waves hide each other's hand-off latency: +7 % at C2 over 2 per CU) and 8 above;
-// whether the code object really admits that many is asked of the runtime (resident_blocks_per_cu) and the plan is
-// refused otherwise, so that a compiler that allocates more registers ends in the streaming form, not in a spin.
-// smallest slice (registers per array) whose wave count the chip can hold: geometry only (no tuning knob, no occupancy
-// query), the same rule the plan applies first
-static int resident_default_q(int n, int m, int d, int num_cus)
+ResidentSlices resident_slices(int n, int m, int d, int num_cus)
 {
-    if (d < 2 || d > 256 || (d & (d - 1)) != 0 || num_cus <= 0) return 0;
+    ResidentSlices sl{};
+    if (d < 2 || d > 256 || (d & (d - 1)) != 0 || num_cus <= 0) return sl;
     const int64_t T = (int64_t)(n + m) * d;
     static const int kQ[5] = {1, 2, 4, 16, 32};
     for (int Q : kQ) {
         if ((64 * Q) % d != 0) continue;
         const int64_t nw = (T + 64 * (int64_t)Q - 1) / (64 * Q);
-        if (nw <= (int64_t)num_cus * (Q <= 2 ? 16 : 8) && nw <= kResidentMaxWaves) return Q;
+        if (nw <= (int64_t)num_cus * (Q <= 2 ? 16 : 8) && nw <= kResidentMaxWaves) sl.at[sl.count++] = {Q, (int)nw};
     }
-    return 0;
+    return sl;
 }
 
 ResidentEvents resident_events(int B, int n, int m, int d, int num_cus)
 {
     ResidentEvents ev{0, 0, 0};
-    const int Q = resident_default_q(n, m, d, num_cus);
-    if (!Q || B > 64) return ev;
-    ev.rows_per_wave = 64 * Q / d;
-    ev.waves = (int)(((int64_t)(n + m) * d + 64 * (int64_t)Q - 1) / (64 * Q));
+    const ResidentSlices sl = resident_slices(n, m, d, num_cus);
+    if (!sl.count || B > 64) return ev;
+    ev.rows_per_wave = 64 * sl.at[0].Q / d;   // the smallest slice that fits
+    ev.waves = sl.at[0].waves;
     // expected list entries per wave and step for uniformly drawn rows; a chunk of T steps (plus the boundary copies of
     // the deepest window) should average <= 20 of the 64 slots, so that an overflow is a property of the data (a row
     // most batches name), not of chance: P[Poisson(20) > 64] ~ 1e-14
@@ -148,37 +142,26 @@ ResidentEvents resident_events(int B, int n, int m, int d, int num_cus)
     return ev;
 }
 
+// Resident-path plan: Q registers per array, NW owner waves, or ok=false when the path does not apply.
+// Every wave of the grid must be resident at once (waves wait on each other).  The wave count per CU the design wants
+// is 16 for Q <= 2 (4 workgroups of 4 waves hide each other's hand-off latency: +7 % at C2 over 2 per CU) and 8 above;
+// whether the code object really admits that many is asked of the runtime (resident_blocks_per_cu) and the plan is
+// refused otherwise, so that a compiler that allocates more registers ends in the streaming form, not in a spin.
 ResidentPlan plan_resident(int64_t N, int B, int n, int m, int d, int num_cus, bool bf16, int ev_tshift)
 {
-    ResidentPlan pl{};
-    pl.ok = false;
-    if (d < 2 || d > 256 || (d & (d - 1)) != 0 || num_cus <= 0 || !launcher_for(d)) return pl;
-    const int64_t T = (int64_t)(n + m) * d;
+    const ResidentSlices sl = resident_slices(n, m, d, num_cus);
+    if (!sl.count || !launcher_for(d)) return ResidentPlan{};
     int look = resident_lookahead(N, B, n, m);
     const bool fast = g_resident_math != 0;
     if (ev_tshift < 0) ev_tshift = resident_events(B, n, m, d, num_cus).tshift;
     if (ev_tshift == 0) look = 0;          // no event lists for this shape: publish right before use
-    static const int kQ[5] = {1, 2, 4, 16, 32};
-    for (int qi = 0; qi < 5; ++qi) {
-        const int Q = kQ[qi];
-        if ((64 * Q) % d != 0) continue;
-        const int64_t nw = (T + 64 * (int64_t)Q - 1) / (64 * Q);
-        if (nw <= (int64_t)num_cus * (Q <= 2 ? 16 : 8) && nw <= kResidentMaxWaves) {
-            const int occ = resident_blocks_per_cu(d, Q, look, fast, bf16);
-            const int blocks = (int)((nw + 3) / 4);
-            if (occ > 0 && (int64_t)blocks > (int64_t)occ * num_cus) continue;   // would not be resident: next Q or none
-            pl.ok = true;
-            pl.Q = Q;
-            pl.NW = (int)nw;
-            pl.blocks = blocks;
-            pl.lookahead = look;
-            pl.fast_math = fast;
-            pl.bf16 = bf16;
-            pl.tshift = ev_tshift;
-            return pl;
-        }
+    for (int s = 0; s < sl.count; ++s) {
+        const int Q = sl.at[s].Q, waves = sl.at[s].waves, blocks = (waves + 3) / 4;
+        const int occ = resident_blocks_per_cu(d, Q, look, fast, bf16);
+        if (occ > 0 && (int64_t)blocks > (int64_t)occ * num_cus) continue;   // would not be resident: next Q or none
+        return ResidentPlan{true, Q, waves, blocks, look, fast, bf16, ev_tshift};
     }
-    return pl;
+    return ResidentPlan{};
 }
 
 // ---- prologue of a resident / local call: ONE kernel ----
@@ -267,27 +250,27 @@ __global__ __launch_bounds__(256) void train_prologue_kernel(InlineStage inl, co
     }
 }
 
-int launch_train_prologue(const void *stage_host, const void *stage_host_devview, void *stage_dev, size_t stage_bytes,
-                          const mfcd_sample *samples, int64_t N, int B, int n, int m, int rows_per_wave, int tshift,
-                          int look, int64_t nch_cap, mfcd_sample *xs, unsigned *ev_cnt, void *ev_ent, hipStream_t st)
+int launch_train_prologue(const StageCopy &sc, const SampleTranslation *tr, hipStream_t st)
 {
-    const int units = (int)((stage_bytes + 15) / 16);
-    const int64_t items = xs ? (N > units ? N : units) : units;
+    static const SampleTranslation none{nullptr, 0, 1, 0, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr};
+    const SampleTranslation &t = tr ? *tr : none;
+    const int units = (int)((sc.bytes + 15) / 16);
+    const int64_t items = t.xs ? (t.N > units ? t.N : units) : units;
     // 64-thread workgroups: the kernel is a chain of dependent round trips per thread (record load, returning atomics,
     // entry stores), so it wants many workgroups per CU in flight, not few wide ones
     constexpr int kPT = 64;
     const dim3 grid((unsigned)((items + kPT - 1) / kPT));
     if (units <= kInlineStageUnits) {
         InlineStage inl;
-        std::memcpy(inl.v, stage_host, (size_t)units * 16);
+        std::memcpy(inl.v, sc.host, (size_t)units * 16);
         hipLaunchKernelGGL(train_prologue_kernel<true>, grid, dim3(kPT), 0, st, inl, (const uint4 *)nullptr,
-                           (uint4 *)stage_dev, units, samples, N, B, n, m, rows_per_wave, tshift, look, nch_cap, xs,
-                           ev_cnt, (uint4 *)ev_ent);
+                           (uint4 *)sc.dev, units, t.samples, t.N, t.B, t.n, t.m, t.rows_per_wave, t.tshift, t.look,
+                           t.nch_cap, t.xs, t.ev_cnt, (uint4 *)t.ev_ent);
     } else {
-        static const InlineStage none{};
-        hipLaunchKernelGGL(train_prologue_kernel<false>, grid, dim3(kPT), 0, st, none, (const uint4 *)stage_host_devview,
-                           (uint4 *)stage_dev, units, samples, N, B, n, m, rows_per_wave, tshift, look, nch_cap, xs,
-                           ev_cnt, (uint4 *)ev_ent);
+        static const InlineStage no_inline{};
+        hipLaunchKernelGGL(train_prologue_kernel<false>, grid, dim3(kPT), 0, st, no_inline, (const uint4 *)sc.devview,
+                           (uint4 *)sc.dev, units, t.samples, t.N, t.B, t.n, t.m, t.rows_per_wave, t.tshift, t.look,
+                           t.nch_cap, t.xs, t.ev_cnt, (uint4 *)t.ev_ent);
     }
     MFCD_HIP_TRY(hipGetLastError());
     return 0;

@@ -110,25 +110,8 @@ constexpr int kEventCap = 64;          // slots per list; a list that is USED ho
 constexpr unsigned kEventNone = 0xFFFFFFF8u;   // sorts last, step 0x7FFFFF, no own role
 constexpr int kEventMaxLocalRows = 1024;
 
-// Pointers needed only at a few points of a launch.  They live in device memory (workspace) and are (re)read with
-// scalar loads there, so they do not occupy SGPRs during the step loop (with them passed by value the kernel needed
-// > 102 SGPRs and spilled scalars into VGPR lanes on every step).
-struct ResidentCold {
-    float *U, *V, *mU, *vU, *mV, *vV;
-    int *status;                     // 0 = ok, 1 = a bounded spin expired (sticky: never cleared by a launch)
-    unsigned long long spin_limit;   // polls before a wave gives up
-    unsigned *ev_cnt;                // [waves][nch_cap] entries appended to list (wave, chunk); all-zero between launches
-                                     // (every wave clears its own counters at the end of a launch)
-    uint4 *ev_ent;                   // [waves][nch_cap][kEventCap] entries
-    long long nch_cap;               // chunks per wave the two arrays are laid out for
-    long long tshift;                // log2(steps per chunk)
-    float *loss_out;                 // [K] batch-mean BCE per step, formed inside the launch (look-ahead form); may be null
-    unsigned long long pad[3];       // 128 bytes
-};
-static_assert(sizeof(ResidentCold) == 128, "train.hip fills this block as sixteen 8-byte words (kColdBytes)");
-
 struct ResidentArgs {
-    const ResidentCold *cold;
+    const ResidentCold *cold;     // train_common.h
     const mfcd_sample *samples;   // the call's samples with u, i, j already translated to VIRTUAL row ids
     const StepScalars *sc;   // [K + 1]
     u64 *mailbox;            // [N][3][D] granules; a granule is valid when its tag == tag_base + step + 1

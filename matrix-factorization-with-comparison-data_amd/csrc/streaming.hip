@@ -416,7 +416,7 @@ extern "C" int mfcd_apply_step(float *U, float *V, float *mU, float *vU, float *
     float *Valt = (float *)ws;
     const void *ptrs[] = {U, V, mU, vU, mV, vV, Ualt, Valt};
     const Plan pl = make_plan(ptrs, 8, n, m, d);
-    const AdamConst ac = adam_const(lr, beta1, beta2, eps, weight_decay, step);
+    const AdamConst ac = adam_const({lr, beta1, beta2, eps, weight_decay}, step);
     launch_streaming_step<0, float>(pl, st, U, V, Ualt, Valt, mU, vU, mV, vV, samples, g, B, 0.0f, n, m, d, ac,
                                     nullptr);
     MFCD_HIP_TRY(hipGetLastError());
@@ -465,7 +465,7 @@ extern "C" int mfcd_adam_dense(float *U, float *V, float *mU, float *vU, float *
     if (!mU || !vU || !mV || !vV || !gradU || !gradV || step < 1) return MFCD_EINVAL;
     const void *ptrs[] = {U, V, mU, vU, mV, vV, gradU, gradV};
     const Plan pl = make_plan(ptrs, 8, n, m, d);
-    const AdamConst ac = adam_const(lr, beta1, beta2, eps, weight_decay, step);
+    const AdamConst ac = adam_const({lr, beta1, beta2, eps, weight_decay}, step);
     // element-wise: reading and writing the same element in place is safe (no gather in this mode)
     launch_streaming_step<2, float>(pl, (hipStream_t)stream, U, V, U, V, mU, vU, mV, vV, nullptr, nullptr, 0, 0.0f, n,
                                     m, d, ac, nullptr, const_cast<float *>(gradU), const_cast<float *>(gradV));

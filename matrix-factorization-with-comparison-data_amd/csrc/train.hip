@@ -31,7 +31,7 @@ int device_cus()
     return cached;
 }
 
-constexpr size_t kColdBytes = 128;  // ResidentCold (resident_kernel.h), directly in front of the scalar table
+constexpr size_t kColdBytes = sizeof(mfcd_detail::ResidentCold);  // directly in front of the scalar table
 constexpr size_t kDbgBytes = 256 + 2 * 16 * 256 * 8 * 8;  // [8] who gave up first + 2 banks of [<=4096 waves][8] u64 of the diagnostic builds (tools/)
 constexpr size_t kMaxMailboxBytes = (size_t)24 << 30;  // beyond this the resident form is not planned
 constexpr int kTagStepBits = 21;    // granule tag = launch id << 21 | (step + 1)
@@ -42,33 +42,22 @@ constexpr unsigned kMaxLaunchId = (1u << (32 - kTagStepBits)) - 1;
 //   counters (resident; kept all-zero between launches) | event-list entries |
 //   { U_alt, V_alt (streaming) } overlapping { translated samples, mailbox (resident) }
 // Every call with N <= N_cap and ceil(N/B) <= K_cap uses these offsets, so nothing has to be re-initialised per call.
+// the regions the prologue kernel writes: stage table, list counters, list entries, translated samples
+struct PrologueRegions { size_t stage_off, evcnt_off, event_off, xs_off; };
+
 struct TrainLayout {
-    size_t dbg_off, stage_off, stage_bytes, terms_off, evcnt_off, evcnt_bytes, event_off, event_bytes;
-    size_t ualt_off, valt_off, xs_off, mailbox_off, mailbox_bytes, total;
+    size_t dbg_off, stage_bytes, terms_off, evcnt_bytes, event_bytes;
+    size_t ualt_off, valt_off, mailbox_off, mailbox_bytes, total;
     size_t alt_end;  // end of the streaming members of the union (U_alt, V_alt)
-    // second set of the regions the prologue kernel writes (stage table, list counters, list entries, translated samples):
-    // a call's prologue may be STAGED on a side stream under the previous call's step kernel (mfcd_train_call_stage)
-    size_t stage2_off, evcnt2_off, event2_off, xs2_off;
+    // set[0] sits in the carve-up above; set[1] (two_sets only, behind everything else) lets a call's prologue be STAGED
+    // on a side stream under the previous call's step kernel (mfcd_train_call_stage)
+    PrologueRegions set[2];
     bool two_sets;
     int64_t K_cap;
     int64_t nch_cap;                    // chunks per wave of the event lists
     mfcd_detail::ResidentEvents ev;     // geometry of the event lists (tshift 0: none)
     bool resident;   // the resident regions exist
 };
-
-// geometric feasibility of the resident form (tuning knobs ignored: the layout must not depend on them)
-bool resident_feasible(int n, int m, int d, int cus)
-{
-    if (d < 2 || d > 256 || (d & (d - 1)) != 0) return false;
-    const int64_t T = (int64_t)(n + m) * d;
-    static const int kQ[5] = {1, 2, 4, 16, 32};
-    for (int Q : kQ) {
-        if ((64 * Q) % d != 0) continue;
-        const int64_t nw = (T + 64 * (int64_t)Q - 1) / (64 * Q);
-        if (nw <= (int64_t)cus * (Q <= 2 ? 16 : 8) && nw <= mfcd_detail::kResidentMaxWaves) return true;
-    }
-    return false;
-}
 
 TrainLayout train_layout(int64_t N_cap, int B, int n, int m, int d)
 {
@@ -78,20 +67,21 @@ TrainLayout train_layout(int64_t N_cap, int B, int n, int m, int d)
     size_t off = kStatusBytes;
     L.dbg_off = off;
     off += kDbgBytes;
-    L.stage_off = off;
+    L.set[0].stage_off = off;
     L.stage_bytes = kColdBytes + sizeof(StepScalars) * (size_t)(L.K_cap + 1);   // one pad entry: the kernel reads step k+1
     off += align_up(L.stage_bytes);
     L.terms_off = off;
     off += align_up(sizeof(unsigned long long) * (size_t)Nc);
     L.mailbox_bytes = sizeof(unsigned long long) * (size_t)Nc * 3 * (size_t)d;
-    L.resident = resident_feasible(n, m, d, device_cus()) && L.mailbox_bytes <= kMaxMailboxBytes &&
+    // any slice at all (geometry only: the layout must not depend on a tuning knob)
+    L.resident = mfcd_detail::resident_slices(n, m, d, device_cus()).count > 0 && L.mailbox_bytes <= kMaxMailboxBytes &&
                  L.K_cap < ((int64_t)1 << 31) - 64;
     L.ev = L.resident ? mfcd_detail::resident_events(B, n, m, d, device_cus()) : mfcd_detail::ResidentEvents{0, 0, 0};
     L.nch_cap = L.ev.tshift ? mfcd_detail::resident_event_chunks(L.K_cap, L.ev.tshift) : 0;
-    L.evcnt_off = off;
+    L.set[0].evcnt_off = off;
     L.evcnt_bytes = sizeof(unsigned) * (size_t)L.ev.waves * (size_t)L.nch_cap;
     off += align_up(L.evcnt_bytes);
-    L.event_off = off;
+    L.set[0].event_off = off;
     L.event_bytes = (size_t)16 * mfcd_detail::kResidentEventCap * (size_t)L.ev.waves * (size_t)L.nch_cap;
     off += align_up(L.event_bytes);
     // streaming members of the union
@@ -102,7 +92,7 @@ TrainLayout train_layout(int64_t N_cap, int B, int n, int m, int d)
     a_off += align_up(sizeof(float) * (size_t)m * d);
     // resident members of the union
     size_t b_off = off;
-    L.xs_off = b_off;
+    L.set[0].xs_off = b_off;
     L.mailbox_off = b_off;
     if (L.resident) {
         b_off += align_up(sizeof(mfcd_sample) * (size_t)Nc);
@@ -112,13 +102,12 @@ TrainLayout train_layout(int64_t N_cap, int B, int n, int m, int d)
     L.alt_end = a_off;
     L.total = a_off > b_off ? a_off : b_off;
     L.two_sets = L.resident && L.ev.tshift != 0;
-    L.stage2_off = L.evcnt2_off = L.event2_off = L.xs2_off = 0;
     if (L.two_sets) {
         size_t c = align_up(L.total);
-        L.stage2_off = c; c += align_up(L.stage_bytes);
-        L.evcnt2_off = c; c += align_up(L.evcnt_bytes);
-        L.event2_off = c; c += align_up(L.event_bytes);
-        L.xs2_off = c; c += align_up(sizeof(mfcd_sample) * (size_t)Nc);
+        L.set[1].stage_off = c; c += align_up(L.stage_bytes);
+        L.set[1].evcnt_off = c; c += align_up(L.evcnt_bytes);
+        L.set[1].event_off = c; c += align_up(L.event_bytes);
+        L.set[1].xs_off = c; c += align_up(sizeof(mfcd_sample) * (size_t)Nc);
         L.total = c;
     }
     return L;
@@ -135,6 +124,13 @@ struct StageSlot {
     size_t cap = 0;
     hipEvent_t ev = nullptr;
     bool pending = false;
+    // whoever reads the slot is on `st` by now: it is free again once the stream has passed this point
+    int release(hipStream_t st)
+    {
+        MFCD_HIP_TRY(hipEventRecord(ev, st));
+        pending = true;
+        return 0;
+    }
 };
 
 struct WsState {
@@ -187,7 +183,7 @@ struct WsState {
     int clear_lists(int set, char *base, hipStream_t st)
     {
         if (lists_dirty[set]) {
-            MFCD_HIP_TRY(hipMemsetAsync(base + (set ? L.evcnt2_off : L.evcnt_off), 0, L.evcnt_bytes, st));
+            MFCD_HIP_TRY(hipMemsetAsync(base + L.set[set].evcnt_off, 0, L.evcnt_bytes, st));
             lists_dirty[set] = false;
         }
         return 0;
@@ -401,10 +397,9 @@ FormChoice choose_form(bool f32, bool resident_planned, int ev_tshift, int64_t N
 
 // what mfcd_train_call_prepare binds: everything of a call but its samples, step and loss buffer
 struct TrainCall {
-    void *U, *V;
-    float *mU, *vU, *mV, *vV;
+    AdamTables t;
     int bf16, B, n, m, d;
-    double lr, beta1, beta2, eps, wd;
+    AdamHyper h;
     void *workspace;
     size_t workspace_bytes;
 };
@@ -413,77 +408,72 @@ struct TrainCall {
 int run_persistent(WsState &S, const TrainCall &c, const FormChoice &fc, const mfcd_sample *samples, int64_t N,
                    int64_t step0, float *loss_per_step, hipStream_t st, float *timing_us, bool stage_only)
 {
+    using mfcd_detail::ResidentCold;
     const TrainLayout &L = S.L;
     const int B = c.B, n = c.n, m = c.m, d = c.d;
     const int64_t nsteps = (N + B - 1) / B;
     char *base = (char *)c.workspace;
-    int *status = (int *)base;
     const bool resident = fc.form == 2;
     // look-ahead form (B <= 64): the batch means are formed inside the launch; otherwise by batch_mean_kernel
     const bool means_inside = resident && fc.rp.lookahead > 0;
-    const WsState::Staged call{true, samples, c.U, N, step0, loss_per_step, c.lr, c.beta1, c.beta2, 0};
+    // the set of prologue regions this call uses; staged_hit: its prologue already ran into them, on the side stream
+    const WsState::Staged call{true, samples, c.t.U, N, step0, loss_per_step, c.h.lr, c.h.beta1, c.h.beta2, 0};
     bool staged_hit = false;
     const int set = S.claim_set(call, means_inside && !timing_us, stage_only, &staged_hit);
-    const size_t stage_off = set ? L.stage2_off : L.stage_off, evcnt_off = set ? L.evcnt2_off : L.evcnt_off;
-    const size_t event_off = set ? L.event2_off : L.event_off, xs_off = set ? L.xs2_off : L.xs_off;
-    StepScalars *sc_dev = (StepScalars *)(base + stage_off + kColdBytes);
-    void *terms = base + L.terms_off;
-    StageSlot *slot = nullptr;
+    const PrologueRegions &R = L.set[set];
+    ResidentCold *cold_dev = (ResidentCold *)(base + R.stage_off);
+    const StepScalars *sc_dev = (const StepScalars *)(cold_dev + 1);
+    const mfcd_detail::SampleTranslation tr{samples, N, B, n, m, resident ? 64 * fc.rp.Q / d : 0, fc.rp.tshift,
+                                            means_inside ? fc.rp.lookahead : 0, L.nch_cap,
+                                            resident ? (mfcd_sample *)(base + R.xs_off) : nullptr,
+                                            (unsigned *)(base + R.evcnt_off), base + R.event_off};
+    // the stage table (ResidentCold, step scalars): short calls build it on this thread's stack and it travels in the
+    // prologue's kernel arguments; longer ones build it in a pinned slot that the prologue reads over the host link
     const size_t need = kColdBytes + sizeof(StepScalars) * (size_t)(nsteps + 1);
-    // short calls: the table is built on this thread's stack and copied into the prologue's kernel arguments at launch
     alignas(16) unsigned char inline_stage[4096];
     const bool stage_inline = need <= mfcd_detail::train_inline_stage_bytes() && need <= sizeof(inline_stage);
-    if (!stage_inline && !staged_hit)
+    StageSlot *slot = nullptr;
+    if (!staged_hit && !stage_inline)
         if (int rc = stage_acquire(S, need, &slot)) return rc;
-    void *const stage_host = (stage_inline || staged_hit) ? (void *)inline_stage : slot->host;
-    void **cold = (void **)stage_host;   // ResidentCold (resident_kernel.h)
+    char *const stage_host = slot ? (char *)slot->host : (char *)inline_stage;
     if (!staged_hit) {
-        cold[0] = c.U; cold[1] = c.V; cold[2] = c.mU; cold[3] = c.vU; cold[4] = c.mV; cold[5] = c.vV; cold[6] = status;
-        cold[7] = (void *)(uintptr_t)mfcd_detail::g_tune.spin_limit;
-        cold[8] = base + evcnt_off;
-        cold[9] = base + event_off;
-        cold[10] = (void *)(uintptr_t)L.nch_cap;
-        cold[11] = (void *)(uintptr_t)fc.rp.tshift;
-        cold[12] = means_inside ? (void *)loss_per_step : nullptr;
-        for (int k = 13; k < 16; ++k) cold[k] = nullptr;
-        StepScalars *sc_host = (StepScalars *)((char *)stage_host + kColdBytes);
-        for (int64_t k = 0; k <= nsteps; ++k) sc_host[k] = step_scalars(c.lr, c.beta1, c.beta2, step0 + k + 1);
+        ResidentCold cold{};
+        cold.U = (float *)c.t.U; cold.V = (float *)c.t.V;
+        cold.mU = c.t.mU; cold.vU = c.t.vU; cold.mV = c.t.mV; cold.vV = c.t.vV;
+        cold.status = (int *)base; cold.spin_limit = mfcd_detail::g_tune.spin_limit;
+        cold.ev_cnt = tr.ev_cnt; cold.ev_ent = (uint4 *)tr.ev_ent;
+        cold.nch_cap = L.nch_cap; cold.tshift = fc.rp.tshift;
+        cold.loss_out = means_inside ? loss_per_step : nullptr;
+        std::memcpy(stage_host, &cold, sizeof(cold));
+        StepScalars *sc_host = (StepScalars *)(stage_host + sizeof(cold));
+        for (int64_t k = 0; k <= nsteps; ++k) sc_host[k] = step_scalars(c.h, step0 + k + 1);
+        if (means_inside)
+            if (int rc = S.clear_lists(set, base, st)) return rc;
     }
-
-    mfcd_sample *xs = resident ? (mfcd_sample *)(base + xs_off) : nullptr;
-    const int rpw = resident ? 64 * fc.rp.Q / d : 0;
-    const int look = means_inside ? fc.rp.lookahead : 0;
-    if (!staged_hit && means_inside)
-        if (int rc = S.clear_lists(set, base, st)) return rc;
-    if (stage_only) {
-        // the prologue of a LATER call, on the caller's side stream: stage table, translated samples, event lists
-        S.lists_dirty[set] = true;
-        if (int rc = mfcd_detail::launch_train_prologue(stage_host, stage_inline ? nullptr : slot->devview, base + stage_off,
-                                                        need, samples, N, B, n, m, rpw, fc.rp.tshift, look, L.nch_cap, xs,
-                                                        (unsigned *)(base + evcnt_off), base + event_off, st))
-            return rc;
-        if (slot) {
-            MFCD_HIP_TRY(hipEventRecord(slot->ev, st));
-            slot->pending = true;
+    // a call that launches: its tag base and the clears of what other forms left (ahead of the prologue, as before)
+    unsigned tag_base = 0;
+    if (!stage_only) {
+        if (resident) {
+            if (int rc = S.next_tag_base(base, st, &tag_base)) return rc;
+            if (int rc = S.clear_dirty(base, st)) return rc;
         }
+        if (!means_inside) S.terms_dirty = true;
+    }
+    if (!staged_hit) {
+        if (stage_only) S.lists_dirty[set] = true;   // until the staged call's launch has read the lists
+        if (int rc = mfcd_detail::launch_train_prologue({stage_host, slot ? slot->devview : nullptr, cold_dev, need},
+                                                        &tr, st))
+            return rc;
+    }
+    if (stage_only) {
+        // the prologue of a LATER call, on the caller's side stream: that call finds it by what it was built from
+        if (slot)
+            if (int rc = slot->release(st)) return rc;
         S.staged = call;
         S.staged.set = set;
         return 0;
     }
-    unsigned long long *mailbox = (unsigned long long *)(base + L.mailbox_off);
-    unsigned tag_base = 0;
-    if (resident) {
-        if (int rc = S.next_tag_base(base, st, &tag_base)) return rc;
-        if (int rc = S.clear_dirty(base, st)) return rc;
-    }
-    if (!means_inside) S.terms_dirty = true;
-    if (staged_hit) {
-        S.staged.valid = false;          // consumed: its prologue ran on the side stream (the caller ordered the streams)
-    } else if (int rc = mfcd_detail::launch_train_prologue(stage_host, stage_inline ? nullptr : slot->devview,
-                                                           base + stage_off, need, samples, N, B, n, m, rpw,
-                                                           fc.rp.tshift, look, L.nch_cap, xs,
-                                                           (unsigned *)(base + evcnt_off), base + event_off, st))
-        return rc;
+    if (staged_hit) S.staged.valid = false;   // consumed (the caller ordered the streams)
     if (resident) {
         S.last_set = set;
         S.lists_dirty[set] = false;      // the launch below reads the lists and leaves their counters at zero
@@ -495,25 +485,25 @@ int run_persistent(WsState &S, const TrainCall &c, const FormChoice &fc, const m
         MFCD_HIP_TRY(hipEventCreate(&e1));
         MFCD_HIP_TRY(hipEventRecord(e0, st));
     }
-    const AdamStatic as = adam_static(c.beta1, c.beta2, c.eps, c.wd);
+    const AdamStatic as = adam_static(c.h);
+    void *terms = base + L.terms_off;
     int rc = 0;
     if (resident)
-        rc = mfcd_detail::launch_resident_steps(fc.rp, base + stage_off, xs, N, B, n, m, d, sc_dev, as, mailbox,
-                                                tag_base, terms, (unsigned long long *)(base + L.dbg_off), (int)nsteps, st);
+        rc = mfcd_detail::launch_resident_steps(fc.rp, cold_dev, tr.xs, N, B, n, m, d, sc_dev, as,
+                                                (unsigned long long *)(base + L.mailbox_off), tag_base, terms,
+                                                (unsigned long long *)(base + L.dbg_off), (int)nsteps, st);
     else
-        rc = mfcd_detail::launch_local_steps((float *)c.U, (float *)c.V, c.mU, c.vU, c.mV, c.vV, samples, N, B, n, m, d,
-                                             sc_dev, as, (float *)terms, (int)nsteps, st);
+        rc = mfcd_detail::launch_local_steps((float *)c.t.U, (float *)c.t.V, c.t.mU, c.t.vU, c.t.mV, c.t.vV, samples, N, B,
+                                             n, m, d, sc_dev, as, (float *)terms, (int)nsteps, st);
     if (rc) return rc;
     if (timing_us) MFCD_HIP_TRY(hipEventRecord(e1, st));
     if (loss_per_step && !means_inside)
         rc = mfcd_detail::launch_batch_means((const float *)terms, samples, N, B, loss_per_step, st);
     if (rc) return rc;
-    // the slot is free again once the prologue has read it; recorded behind the call's last launch so that the
-    // record does not sit between two launches (any later point of the stream implies the prologue is done)
-    if (slot) {
-        MFCD_HIP_TRY(hipEventRecord(slot->ev, st));
-        slot->pending = true;
-    }
+    // recorded behind the call's last launch so that the record does not sit between two launches (any later point of
+    // the stream implies the prologue is done)
+    if (slot)
+        if (int rc = slot->release(st)) return rc;
     if (timing_us) {
         MFCD_HIP_TRY(hipEventSynchronize(e1));
         float ms = 0.0f;
@@ -534,13 +524,13 @@ int run_streaming(WsState &S, const TrainCall &c, const mfcd_sample *samples, in
     const int B = c.B, n = c.n, m = c.m, d = c.d;
     const int64_t nsteps = (N + B - 1) / B;
     char *base = (char *)c.workspace;
-    TP *U = (TP *)c.U, *V = (TP *)c.V;
+    TP *U = (TP *)c.t.U, *V = (TP *)c.t.V;
     if (L.resident) S.mailbox_dirty = S.terms_dirty = true;
     TP *Ualt = (TP *)(base + L.ualt_off);
     TP *Valt = (TP *)(base + L.valt_off);
     float *terms = (float *)(base + L.terms_off);
 
-    const void *ptrs[] = {U, V, c.mU, c.vU, c.mV, c.vV, Ualt, Valt};
+    const void *ptrs[] = {U, V, c.t.mU, c.t.vU, c.t.mV, c.t.vV, Ualt, Valt};
     const mfcd_detail::Plan pl = mfcd_detail::make_plan(ptrs, 8, n, m, d);
     std::vector<hipEvent_t> ev;
     if (timing_us) {
@@ -550,12 +540,12 @@ int run_streaming(WsState &S, const TrainCall &c, const mfcd_sample *samples, in
     for (int64_t k = 0; k < nsteps; ++k) {
         const int64_t off = k * B;
         const int Bk = (int)((N - off) < B ? (N - off) : B);
-        const AdamConst ac = adam_const(c.lr, c.beta1, c.beta2, c.eps, c.wd, step0 + k + 1);
+        const AdamConst ac = adam_const(c.h, step0 + k + 1);
         const bool even = (k & 1) == 0;
         if (timing_us) MFCD_HIP_TRY(hipEventRecord(ev[2 * k], st));
         mfcd_detail::launch_streaming_step<0, TP>(pl, st, even ? U : Ualt, even ? V : Valt, even ? Ualt : U,
-                                                  even ? Valt : V, c.mU, c.vU, c.mV, c.vV, samples + off, nullptr, Bk,
-                                                  1.0f / (float)Bk, n, m, d, ac, terms + off);
+                                                  even ? Valt : V, c.t.mU, c.t.vU, c.t.mV, c.t.vV, samples + off,
+                                                  nullptr, Bk, 1.0f / (float)Bk, n, m, d, ac, terms + off);
         if (timing_us) MFCD_HIP_TRY(hipEventRecord(ev[2 * k + 1], st));
     }
     MFCD_HIP_TRY(hipGetLastError());
@@ -590,8 +580,8 @@ int run_streaming(WsState &S, const TrainCall &c, const mfcd_sample *samples, in
 int run_call(const TrainCall &c, const mfcd_sample *samples, int64_t N, int64_t step0, float *loss_per_step,
              void *stream, float *timing_us, bool stage_only = false)
 {
-    if (int rc = check_common(c.U, c.V, c.n, c.m, c.d)) return rc;
-    if (!c.mU || !c.vU || !c.mV || !c.vV || N < 0 || c.B <= 0 || step0 < 0) return MFCD_EINVAL;
+    if (int rc = check_common(c.t.U, c.t.V, c.n, c.m, c.d)) return rc;
+    if (!c.t.mU || !c.t.vU || !c.t.mV || !c.t.vV || N < 0 || c.B <= 0 || step0 < 0) return MFCD_EINVAL;
     if (N == 0) return 0;
     if (!samples || !c.workspace) return MFCD_EINVAL;
     WsState *S = find_ws(c.workspace);
@@ -648,7 +638,7 @@ extern "C" int mfcd_train_steps(float *U, float *V, float *mU, float *vU, float 
                                 double lr, double beta1, double beta2, double eps, double weight_decay,
                                 float *loss_per_step, void *workspace, size_t workspace_bytes, void *stream)
 {
-    const TrainCall c{U, V, mU, vU, mV, vV, 0, B, n, m, d, lr, beta1, beta2, eps, weight_decay, workspace, workspace_bytes};
+    const TrainCall c{{U, V, mU, vU, mV, vV}, 0, B, n, m, d, {lr, beta1, beta2, eps, weight_decay}, workspace, workspace_bytes};
     return run_call(c, samples, N, step0, loss_per_step, stream, nullptr);
 }
 
@@ -657,7 +647,7 @@ extern "C" int mfcd_train_steps_bf16(uint16_t *U, uint16_t *V, float *mU, float 
                                      double lr, double beta1, double beta2, double eps, double weight_decay,
                                      float *loss_per_step, void *workspace, size_t workspace_bytes, void *stream)
 {
-    const TrainCall c{U, V, mU, vU, mV, vV, 1, B, n, m, d, lr, beta1, beta2, eps, weight_decay, workspace, workspace_bytes};
+    const TrainCall c{{U, V, mU, vU, mV, vV}, 1, B, n, m, d, {lr, beta1, beta2, eps, weight_decay}, workspace, workspace_bytes};
     return run_call(c, samples, N, step0, loss_per_step, stream, nullptr);
 }
 
@@ -668,7 +658,7 @@ extern "C" int mfcd_train_steps_timed(float *U, float *V, float *mU, float *vU, 
                                       float *kernel_us_host)
 {
     if (!kernel_us_host) return MFCD_EINVAL;
-    const TrainCall c{U, V, mU, vU, mV, vV, 0, B, n, m, d, lr, beta1, beta2, eps, weight_decay, workspace, workspace_bytes};
+    const TrainCall c{{U, V, mU, vU, mV, vV}, 0, B, n, m, d, {lr, beta1, beta2, eps, weight_decay}, workspace, workspace_bytes};
     return run_call(c, samples, N, step0, loss_per_step, stream, kernel_us_host);
 }
 
@@ -684,8 +674,8 @@ extern "C" int mfcd_train_call_prepare(void *U, void *V, float *mU, float *vU, f
     if (!S) return MFCD_ESTATE;
     if (n != S->n || m != S->m || d != S->d) return MFCD_ESTATE;
     if (workspace_bytes < S->L.total) return MFCD_EWORKSPACE;
-    *handle_out = new TrainCall{U, V, mU, vU, mV, vV, bf16_factors ? 1 : 0, B, n, m, d, lr, beta1, beta2, eps,
-                                weight_decay, workspace, workspace_bytes};
+    *handle_out = new TrainCall{{U, V, mU, vU, mV, vV}, bf16_factors ? 1 : 0, B, n, m, d,
+                                {lr, beta1, beta2, eps, weight_decay}, workspace, workspace_bytes};
     return 0;
 }
 
@@ -830,14 +820,15 @@ extern "C" int mfcd_train_steps_local_multi(const mfcd_local_model *models, int 
     for (int r = 0; r < R; ++r) {
         const mfcd_local_model &md = models[r];
         const int64_t K = (md.N + md.B - 1) / md.B;
-        for (int64_t k = 0; k <= K; ++k) sc[k0 + k] = step_scalars(md.lr, md.beta1, md.beta2, md.step0 + k + 1);
+        const AdamHyper h{md.lr, md.beta1, md.beta2, md.eps, md.weight_decay};
+        for (int64_t k = 0; k <= K; ++k) sc[k0 + k] = step_scalars(h, md.step0 + k + 1);
         LocalArgs a{};
         a.U = md.U; a.V = md.V; a.mU = md.mU; a.vU = md.vU; a.mV = md.mV; a.vV = md.vV;
         a.samples = md.samples;
         a.sc = (const StepScalars *)(base + L.sc_off) + k0;
         a.loss_terms = (float *)(base + L.terms_off) + t0;
         a.N = md.N; a.B = md.B; a.n = md.n; a.m = md.m; a.d = md.d; a.K = (int)K;
-        a.ac = adam_static(md.beta1, md.beta2, md.eps, md.weight_decay);
+        a.ac = adam_static(h);
         const size_t need = mfcd_detail::local_multi_fill(a, ql);
         lds = need > lds ? need : lds;
         tab[r] = a;
@@ -852,16 +843,12 @@ extern "C" int mfcd_train_steps_local_multi(const mfcd_local_model *models, int 
     if (lds > mfcd_detail::kLocalMaxLds) return MFCD_EINVAL;   // (not reached: every model fits at QL = 8)
 
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = mfcd_detail::launch_train_prologue(host, slot->devview, base, L.stage_bytes, nullptr, 0, 1, 0, 0, 0, 0,
-                                                    0, 0, nullptr, nullptr, nullptr, st))
-        return rc;
+    if (int rc = mfcd_detail::launch_train_prologue({host, slot->devview, base, L.stage_bytes}, nullptr, st)) return rc;
     if (int rc = mfcd_detail::launch_local_multi((const LocalArgs *)base, R, ql, max_B <= mfcd_detail::kLocalSmallBatch,
                                                  lds, st))
         return rc;
     if (int rc = mfcd_detail::launch_batch_means_multi((const MeanSeg *)(base + L.seg_off), R, L.steps, st)) return rc;
-    MFCD_HIP_TRY(hipEventRecord(slot->ev, st));   // the slot is free again once the prologue has read it
-    slot->pending = true;
-    return 0;
+    return slot->release(st);
 }
 
 extern "C" int mfcd_eval_batches_multi(const mfcd_eval_model *models, int R, void *workspace, size_t workspace_bytes,
@@ -894,11 +881,7 @@ extern "C" int mfcd_eval_batches_multi(const mfcd_eval_model *models, int R, voi
     if (blocks == 0) return 0;
     if (blocks > 0x7fffffff) return MFCD_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = mfcd_detail::launch_train_prologue(segs, slot->devview, workspace, stage_bytes, nullptr, 0, 1, 0, 0, 0, 0,
-                                                    0, 0, nullptr, nullptr, nullptr, st))
-        return rc;
+    if (int rc = mfcd_detail::launch_train_prologue({segs, slot->devview, workspace, stage_bytes}, nullptr, st)) return rc;
     if (int rc = mfcd_detail::launch_eval_multi((const EvalSeg *)workspace, nseg, blocks, max_B, st)) return rc;
-    MFCD_HIP_TRY(hipEventRecord(slot->ev, st));
-    slot->pending = true;
-    return 0;
+    return slot->release(st);
 }

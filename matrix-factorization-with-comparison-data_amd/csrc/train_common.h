@@ -25,37 +25,40 @@ struct AdamConst {
     StepScalars sc;
 };
 
+// One training call's hyper-parameters as the caller passed them, and its six tables (U, V: fp32 or bf16 elements)
+struct AdamHyper { double lr, beta1, beta2, eps, wd; };
+struct AdamTables {
+    void *U, *V;
+    float *mU, *vU, *mV, *vV;
+    template <typename TP>   // from element uo of the U side and vo of the V side on (shard rehearsal on full tables)
+    AdamTables from(int64_t uo, int64_t vo) const { return {(TP *)U + uo, (TP *)V + vo, mU + uo, vU + uo, mV + vo, vV + vo}; }
+};
+
 // host-side Adam constants (f64 as Python computes them, rounded where ATen rounds)
-inline AdamStatic adam_static(double beta1, double beta2, double eps, double wd)
+inline AdamStatic adam_static(const AdamHyper &h)
 {
     AdamStatic a;
-    a.w1 = (float)(1.0 - beta1);
-    a.b2 = (float)beta2;
-    a.w2 = (float)(1.0 - beta2);
-    a.eps = (float)eps;
-    a.wd = (float)wd;
+    a.w1 = (float)(1.0 - h.beta1);
+    a.b2 = (float)h.beta2;
+    a.w2 = (float)(1.0 - h.beta2);
+    a.eps = (float)h.eps;
+    a.wd = (float)h.wd;
     return a;
 }
 
-inline StepScalars step_scalars(double lr, double beta1, double beta2, int64_t step)
+inline StepScalars step_scalars(const AdamHyper &h, int64_t step)
 {
     // bias corrections in f64 as Python does (adam.py: 1 - beta**step, lr / bc1, bc2 ** 0.5)
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const double bc1 = 1.0 - pow(h.beta1, (double)step), bc2 = 1.0 - pow(h.beta2, (double)step);
     StepScalars s;
-    s.neg_step_size = (float)(-(lr / bc1));
+    s.neg_step_size = (float)(-(h.lr / bc1));
     s.bc2_sqrt = (float)sqrt(bc2);
     s.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
     s.pad = 0.0f;
     return s;
 }
 
-inline AdamConst adam_const(double lr, double beta1, double beta2, double eps, double wd, int64_t step)
-{
-    AdamConst ac;
-    ac.st = adam_static(beta1, beta2, eps, wd);
-    ac.sc = step_scalars(lr, beta1, beta2, step);
-    return ac;
-}
+inline AdamConst adam_const(const AdamHyper &h, int64_t step) { return {adam_static(h), step_scalars(h, step)}; }
 
 constexpr size_t kStatusBytes = 256;  // workspace[0..3] = int32 status word (sticky: set by an aborting resident launch)
 
@@ -287,6 +290,16 @@ int set_uvt_split(int v);    // uvt.hip
 int set_uvt_target_wgs(int v);   // uvt.hip
 int set_uvt_min_stages(int v);   // uvt.hip
 
+// The resident slice rule, in one place: the slices of Q registers per array (64*Q elements, whole rows) whose wave
+// count the chip can hold at the design's waves per CU (16 for Q <= 2, 8 above) and kResidentMaxWaves, in ascending Q.
+// Geometry only: no tuning knob, no occupancy query.  The workspace layout asks "any?", the event lists are laid out
+// for the first, the plan walks them with the occupancy of the actual code object.
+struct ResidentSlices {
+    int count;
+    struct { int Q, waves; } at[5];
+};
+ResidentSlices resident_slices(int n, int m, int d, int num_cus);
+
 // ev_tshift: chunk length of the event lists the WORKSPACE was laid out for (ResidentEvents::tshift; 0 = no lists, the
 // look-ahead form is then not planned)
 ResidentPlan plan_resident(int64_t N, int B, int n, int m, int d, int num_cus, bool bf16 = false, int ev_tshift = -1);
@@ -309,14 +322,43 @@ inline int64_t resident_event_chunks(int64_t K, int tshift) { return (K >> tshif
 // built in is read at launch time only (no pinned slot, no event)
 size_t train_inline_stage_bytes();
 
-// One kernel in front of a resident / local launch: pinned staging slot -> workspace, and (xs != nullptr) the
-// translated samples + (look > 0) the per-wave event lists of the resident form.
-int launch_train_prologue(const void *stage_host, const void *stage_host_devview, void *stage_dev, size_t stage_bytes,
-                          const mfcd_sample *samples, int64_t N, int B, int n, int m, int rows_per_wave, int tshift,
-                          int look, int64_t nch_cap, mfcd_sample *xs, unsigned *ev_cnt, void *ev_ent, hipStream_t st);
+// Pointers needed only at a few points of a resident launch.  They live in device memory (workspace, directly in front
+// of the call's step scalars) and are (re)read with scalar loads there, so they do not occupy SGPRs during the step loop
+// (with them passed by value the kernel needed > 102 SGPRs and spilled scalars into VGPR lanes on every step).
+struct ResidentCold {
+    float *U, *V, *mU, *vU, *mV, *vV;
+    int *status;                     // 0 = ok, 1 = a bounded spin expired (sticky: never cleared by a launch)
+    unsigned long long spin_limit;   // polls before a wave gives up
+    unsigned *ev_cnt;                // [waves][nch_cap] entries appended to list (wave, chunk); all-zero between launches
+                                     // (every wave clears its own counters at the end of a launch)
+    uint4 *ev_ent;                   // [waves][nch_cap][kEventCap] entries
+    long long nch_cap;               // chunks per wave the two arrays are laid out for
+    long long tshift;                // log2(steps per chunk)
+    float *loss_out;                 // [K] batch-mean BCE per step, formed inside the launch (look-ahead form); may be null
+    unsigned long long pad[3];       // 128 bytes
+};
+static_assert(sizeof(ResidentCold) == 128, "eight 16-byte units of the stage table (resident.hip: kInlineStageUnits)");
 
-// cold_dev: device copy of ResidentCold (resident_kernel.h: table pointers, status word, spin limit, touch strings);
-// xs: the call's samples translated to virtual row ids
+// One kernel in front of a resident / local / multi-model launch: the host-built stage table -> workspace, and (tr
+// given, tr->xs set) the translated samples + (tr->look > 0) the per-wave event lists of the resident form.
+struct StageCopy {
+    const void *host;      // the table as the host built it (read at launch time when it travels in the kernel arguments)
+    const void *devview;   // the pinned slot `host` is, as the device addresses it; null: it fits the kernel arguments
+    void *dev;
+    size_t bytes;
+};
+struct SampleTranslation {
+    const mfcd_sample *samples;
+    int64_t N;
+    int B, n, m, rows_per_wave, tshift, look;
+    int64_t nch_cap;
+    mfcd_sample *xs;
+    unsigned *ev_cnt;
+    void *ev_ent;
+};
+int launch_train_prologue(const StageCopy &sc, const SampleTranslation *tr, hipStream_t st);
+
+// cold_dev: device copy of the call's ResidentCold; xs: the call's samples translated to virtual row ids
 int launch_resident_steps(const ResidentPlan &pl, const void *cold_dev, const mfcd_sample *xs, int64_t N, int B, int n,
                           int m, int d, const StepScalars *sc_dev, const AdamStatic &ac, unsigned long long *mailbox,
                           unsigned tag_base, void *loss_terms, unsigned long long *dbg, int K, hipStream_t st);

@@ -4,6 +4,9 @@ object stays valid after a fused run).
 
 All compute goes through the C-ABI in libmfcd_hip.so; there is no eager/torch fallback.
 """
+import ctypes
+import weakref
+
 import numpy as np
 import torch
 
@@ -27,6 +30,9 @@ class AdamBinding:
     """View of a caller-owned torch.optim.Adam over exactly (model.U, model.V)."""
 
     def __init__(self, model, optimizer):
+        self._ctx, self._prep = None, None             # call_context(); prepared(): (key, handle, workspace buffer)
+        self._big = None                               # the big resident form: None undecided, False no, or a BigResident
+        self._fast, self._fast_stream = None, None     # train_steps' per-binding fast path (engine._FastCall)
         if type(optimizer) is not torch.optim.Adam:
             raise NotImplementedError("the fused step implements torch.optim.Adam only "
                                       f"(got {type(optimizer).__name__})")
@@ -59,7 +65,6 @@ class AdamBinding:
         if float(su) != float(sv):
             raise NotImplementedError("U and V must have taken the same number of Adam steps")
         self._pending, self._base = 0, None
-        self._fast, self._fast_stream = None, None     # train_steps' per-binding fast path (engine._FastCall)
 
     @property
     def step(self):
@@ -93,18 +98,15 @@ class AdamBinding:
     def call_context(self):
         """(six raw table pointers, n, m, d, device, dtype) for the C-ABI, computed once per binding: the binding is
         a view of tensors that stay where they are for its lifetime (`refresh()` after replacing any of them)."""
-        ctx = getattr(self, "_ctx", None)
-        if ctx is None:
+        if self._ctx is None:
             t = self.tensors()
             U, V = t[0], t[1]
-            ctx = self._ctx = (tuple(_lib.ptr(x) for x in t), U.shape[0], V.shape[0], U.shape[1], U.device, U.dtype)
-        return ctx
+            self._ctx = (tuple(_lib.ptr(x) for x in t), U.shape[0], V.shape[0], U.shape[1], U.device, U.dtype)
+        return self._ctx
 
     def refresh(self):
-        self._ctx = None
-        self._fast = None
-        self._big = None
-        self.drop_prepared()
+        self._ctx = self._big = None
+        self.drop_prepared()                   # (and the fast path built on it)
 
     # ---- prepared calls (include/mfcd.h: mfcd_train_call_*) ----
     def prepared(self, ws, batch_size):
@@ -113,10 +115,8 @@ class AdamBinding:
         (learning-rate schedules write param_groups between calls) or the tables (refresh())."""
         g = self.group
         key = (ws.buf.data_ptr(), batch_size, g["lr"], g["betas"], g["eps"], g["weight_decay"])
-        hit = getattr(self, "_prep", None)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        import ctypes
+        if self._prep is not None and self._prep[0] == key:
+            return self._prep[1]
         self.drop_prepared()
         L = _lib.load()
         ptrs, n, m, d, dev, dtype = self.call_context()
@@ -128,10 +128,8 @@ class AdamBinding:
         return h
 
     def drop_prepared(self):
-        hit = getattr(self, "_prep", None)
-        self._fast = None
+        hit, self._prep, self._fast = self._prep, None, None
         if hit is not None:
-            self._prep = None
             _lib.load().mfcd_train_call_release(hit[1])
 
     def __del__(self):
@@ -140,8 +138,6 @@ class AdamBinding:
         except Exception:
             pass
 
-
-import weakref
 
 _big_forms = weakref.WeakSet()          # live BigResident objects: check_status() reads their status words too
 _BIG_MODE = "auto"                      # "auto": train_steps takes the big resident form where it applies; "off"; "force"
@@ -159,14 +155,20 @@ def set_big_resident(mode):
     _BIG_MODE = mode
 
 
+def _big_shape_ok(binding):
+    """The shape the big resident form takes: fp32 tables with d == 64 and n + m <= 131072."""
+    U, V = binding.model.U.data, binding.model.V.data
+    return U.dtype == torch.float32 and U.shape[1] == 64 and U.shape[0] + V.shape[0] <= 131072
+
+
 def _big_for(binding, N, batch_size, samples_dev):
     """The binding's BigResident if this call should take it, else None."""
     if _BIG_MODE == "off" or batch_size > 64:
         return None
-    big = getattr(binding, "_big", None)
+    big = binding._big
     if big is None:
         U, V = binding.model.U.data, binding.model.V.data
-        ok = U.dtype == torch.float32 and U.shape[1] == 64 and U.shape[0] + V.shape[0] <= 131072
+        ok = _big_shape_ok(binding)
         if ok and _BIG_MODE == "auto":      # only where the library itself would stream (state beyond the resident form)
             ok = train_plan(max(N, BIG_MIN_STEPS * batch_size), batch_size, U.shape[0], V.shape[0], 64)["form_name"] == "streaming"
         big = binding._big = BigResident(binding) if ok else False
@@ -185,10 +187,9 @@ class BigResident:
 
     def __init__(self, binding):
         self.b, self.L = binding, _lib.load()
-        U, V = binding.model.U.data, binding.model.V.data
-        if U.dtype != torch.float32 or U.shape[1] != 64 or U.shape[0] + V.shape[0] > 131072:
+        if not _big_shape_ok(binding):
             raise NotImplementedError("the big resident form takes fp32 tables with d == 64 and n + m <= 131072")
-        self.dev, self.ws = U.device, None
+        self.dev, self.ws = binding.model.U.device, None
         _big_forms.add(self)
 
     def train_steps(self, stream, B, loss_out=None, defer_step=False):
@@ -223,7 +224,6 @@ class BigResident:
         return int(worst.item()) <= self.L.mfcd_train_big_slots()
 
     def status(self):
-        import ctypes
         if self.ws is None:
             return
         out = ctypes.c_int(0)
@@ -481,7 +481,6 @@ def set_tuning(**knobs):
 
 def train_plan(n_samples, batch_size, n, m, d, bf16=False):
     """What the library would do for a call of these sizes under the current settings → dict (mfcd_train_plan)."""
-    import ctypes
     out = _lib.TrainPlan()
     _lib.check(_lib.load().mfcd_train_plan_query(n_samples, batch_size, n, m, d, int(bool(bf16)), ctypes.byref(out)))
     plan = {k: int(getattr(out, k)) for k, _ in _lib.TrainPlan._fields_ if k != "reserved"}
@@ -558,9 +557,9 @@ def train_steps(binding, samples_dev, batch_size, loss_out=None, kernel_us=None,
     nsteps = (N + batch_size - 1) // batch_size
     if N == 0:
         return torch.empty(0, dtype=torch.float32, device=dev) if loss_out is None else loss_out[:0]
-    if getattr(binding, "_big", None) is None and d != 64:
+    if binding._big is None and d != 64:
         binding._big = False                                      # decided once per binding (refresh() clears it)
-    if kernel_us is None and getattr(binding, "_big", None) is not False:
+    if kernel_us is None and binding._big is not False:
         big = _big_for(binding, N, batch_size, samples_dev)      # C4-sized states: the big resident form (csrc/big.hip)
         if big is not None:
             return big.train_steps(samples_dev, batch_size, loss_out, defer_step)
@@ -585,7 +584,6 @@ def train_steps(binding, samples_dev, batch_size, loss_out=None, kernel_us=None,
                    loss_out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
     if dtype == torch.bfloat16:
         raise NotImplementedError("the timed diagnostic twin exists for fp32 factors only")
-    import ctypes
     out = (ctypes.c_float * 3)()
     _lib.check(L.mfcd_train_steps_timed(*args, ctypes.cast(out, ctypes.c_void_p)))
     kernel_us[:] = [float(out[0]), float(out[1]), float(out[2])]
@@ -781,7 +779,6 @@ def fit(model, train_loader, val_loader, optimizer, num_epochs, progress=None, o
 def _numpy_mirror(struct):
     """numpy structured dtype with the layout of a ctypes Structure (pointers as uint64): lets the host update one
     field of every descriptor of a table with one vectorised assignment."""
-    import ctypes
     names, formats, offsets = [], [], []
     for name, ct in struct._fields_:
         names.append(name)
@@ -900,7 +897,6 @@ def _fit_local_multi(models, train_loaders, val_loaders, optimizers, epochs, ord
     loss_v = losses.data_ptr() + 4 * (int(K.sum()) + kv_off).astype(np.uint64)
     tv["step0"], tv["loss_per_step"], ev["loss_per_batch"] = step0, loss_t, loss_v
 
-    import ctypes
     stage = ctypes.c_size_t(0)
     tws = _multi_workspace(L, L.mfcd_train_local_multi_workspace_bytes(tv.ctypes.data, R, ctypes.byref(stage)),
                            stage.value, dev)

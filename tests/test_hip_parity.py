@@ -27,22 +27,16 @@ def dev():
     return torch.device("cuda:0")
 
 
-def resident_applies(n, m, d):
-    """Mirror of plan_resident (csrc/resident.hip): d a power of two <= 256 and the state fits the register files."""
-    return 2 <= d <= 256 and (d & (d - 1)) == 0 and (n + m) * d <= 256 * 8 * 64 * 32
-
-
-def local_applies(n, m, d, B=64):
-    """Mirror of local_applies (csrc/local.hip): the whole problem fits one workgroup's LDS and vector ALU."""
-    pad = lambda v: (v + 3) & ~3  # noqa: E731
-    T = (n + m) * d
-    ql = -(-T // 1024)
-    ql = 1 if ql <= 1 else 2 if ql <= 2 else 4 if ql <= 4 else 8
-    lds = 4 * (2 * ql * 1024 + 3 * pad(n + m) + pad(B)) + 16 * B + 16
-    lps = 1
-    while lps < d and lps < 8:
-        lps *= 2
-    return T <= 8192 and 1 <= B <= 4096 and 3 * B <= 2 * (1024 // lps) and lds <= 160 * 1024
+def form_applies(N, B, n, m, d):
+    """Whether the form the `path` fixture has forced takes a call of these sizes: the library's own answer
+    (engine.train_plan = mfcd_train_plan_query under the forced path; MFCD_EINVAL means "does not apply")."""
+    from mfcd import _lib, engine
+    try:
+        engine.train_plan(N, B, n, m, d)
+    except _lib.MfcdError as e:
+        assert str(e) == _lib.load().mfcd_error_string(-1).decode(), e      # MFCD_EINVAL, nothing else
+        return False
+    return True
 
 
 @pytest.fixture(params=["streaming", "resident", "resident-ieee", "local"])
@@ -95,10 +89,11 @@ class ListDataset(torch.utils.data.Dataset):
 def test_kat_steps_match_reference(dev, path, name):
     from mfcd import engine
     g = load_golden(name)
-    if path == "resident" and not resident_applies(g["U0"].shape[0], g["V0"].shape[0], g["U0"].shape[1]):
-        pytest.skip("resident form needs d to be a power of two")
-    if path == "local" and not local_applies(g["U0"].shape[0], g["V0"].shape[0], g["U0"].shape[1]):
-        pytest.skip("local form needs (n+m)*d <= 8192")
+    (n, d), m = g["U0"].shape, g["V0"].shape[0]
+    if not all(form_applies(len(g[f"u{k}"]), len(g[f"u{k}"]), n, m, d) for k in range(int(g["n_steps"]))):
+        assert path in ("resident", "local"), "the streaming form takes every shape"
+        pytest.skip({"resident": "resident form needs d to be a power of two",
+                     "local": "local form needs (n+m)*d <= 8192"}[path])
     lr, wd = float(g["lr"]), float(g["wd"])
     model, opt = _model_from(g["U0"], g["V0"], dev, lr, wd)
     bind = engine.AdamBinding(model, opt)
@@ -222,10 +217,9 @@ def _synthetic(n, m, d, N, seed, soft=False):
 def test_train_epoch_matches_oracle(dev, orc, path, n, m, d, N, B, soft):
     from mfcd import engine
     from oracle import oracle as O
-    if path == "resident" and not resident_applies(n, m, d):
-        pytest.skip("resident form does not apply to this shape")
-    if path == "local" and not local_applies(n, m, d, B):
-        pytest.skip("local form does not apply to this shape")
+    if not form_applies(N, B, n, m, d):
+        assert path in ("resident", "local"), "the streaming form takes every shape"
+        pytest.skip(f"{path} form does not apply to this shape")
     U0, V0, u, i, j, z = _synthetic(n, m, d, N, seed=n + d + N, soft=soft)
     lr, wd = 1e-3, 1e-5
     model, opt = _model_from(U0, V0, dev, lr, wd)
@@ -2083,19 +2077,33 @@ def test_row_block_sharded_uvt_pass_rehearsal_at_c5_shape(dev, orc):
     np.testing.assert_allclose(got[:, 2], ref_rows[:, 2], rtol=2e-5)
 
 
+# Shapes of the staged-prologue tests: (n, m, d, samples per call).  The first is the one each test was written at; the
+# other two are resident look-ahead calls, whose prologue IS staged (second set of prologue regions, claim_set,
+# lists_dirty): 40 steps, whose step table travels in the prologue's kernel arguments, and 300 steps (> 223), whose
+# table goes through a pinned slot.
+STAGED_LOOKAHEAD = [(4096, 4096, 8, 64 * 40 + 17), (4096, 4096, 8, 64 * 300 + 5)]
+
+
+def _assert_prologue_is_staged(n, m, d, N):
+    from mfcd import engine
+    assert engine.train_plan(N, 64, n, m, d)["resident_lookahead"] > 0   # the form whose prologue is staged
+
+
 @pytest.mark.gpu
-def test_staged_prologue_gives_the_same_run(dev, monkeypatch):
+@pytest.mark.parametrize("n,m,d,N", [(640, 512, 64, 64 * 150 + 17)] + STAGED_LOOKAHEAD)
+def test_staged_prologue_gives_the_same_run(dev, monkeypatch, n, m, d, N):
     """engine.fit stages every epoch's prologue (sample translation, per-wave event lists) on a side stream under the
     previous epoch's step kernel (mfcd_train_call_stage, second set of prologue regions).  Same inputs to the same step
     kernel: the run must be BIT-identical to one whose prologues all run in-stream, epoch losses included, and the
     staged descriptor must not leak into a call on other samples."""
     from mfcd import engine
-    n, m, d, N = 640, 512, 64, 64 * 150 + 17
     U0, V0, u, i, j, z = _synthetic(n, m, d, N, seed=31)
     rows = np.stack([u, i, j, z], 1)
     mk = lambda r, sh: torch.utils.data.DataLoader(ListDataset(r), batch_size=64, shuffle=sh)   # noqa: E731
     engine.set_train_path("resident")
     try:
+        if (n, m, d, N) in STAGED_LOOKAHEAD:
+            _assert_prologue_is_staged(n, m, d, N)
         outs = []
         for staged in (True, False):
             if not staged:
@@ -2117,19 +2125,21 @@ def test_staged_prologue_gives_the_same_run(dev, monkeypatch):
 
 
 @pytest.mark.gpu
-def test_abandoned_staged_prologue_leaves_no_trace(dev):
+@pytest.mark.parametrize("n,m,d,N", [(640, 512, 64, 64 * 150 + 17)] + STAGED_LOOKAHEAD)
+def test_abandoned_staged_prologue_leaves_no_trace(dev, n, m, d, N):
     """A staged prologue whose call never comes (the caller went on with other samples, or with another step count)
     leaves its set's per-wave event lists filled: the next prologue into that set must start from empty lists, not
     append to them (train.hip: WsState::lists_dirty).  Stage A, abandon it, run B in-stream, stage C over A's set, run
     C: BIT-identical to the same two calls with nothing staged."""
     from mfcd import engine
-    n, m, d, N = 640, 512, 64, 64 * 150 + 17
     U0, V0, u, i, j, z = _synthetic(n, m, d, 3 * N, seed=33)
     recs = [_records(u[k * N:(k + 1) * N], i[k * N:(k + 1) * N], j[k * N:(k + 1) * N], z[k * N:(k + 1) * N], n, m, dev).dev
             for k in range(3)]
     side = torch.cuda.Stream(device=dev)
     engine.set_train_path("resident")
     try:
+        if (n, m, d, N) in STAGED_LOOKAHEAD:
+            _assert_prologue_is_staged(n, m, d, N)
         outs = []
         for staged in (True, False):
             model, opt = _model_from(U0, V0, dev, 1e-3, 1e-5)
@@ -2157,20 +2167,20 @@ def test_abandoned_staged_prologue_leaves_no_trace(dev):
 
 
 @pytest.mark.gpu
-def test_staged_prologue_follows_a_changed_learning_rate(dev):
+@pytest.mark.parametrize("n,m,d,N", [(4096, 4096, 64, 64 * 150 + 17)] + STAGED_LOOKAHEAD)
+def test_staged_prologue_follows_a_changed_learning_rate(dev, n, m, d, N):
     """A staged prologue's step table holds the step scalars of the lr / betas current when it was staged.  A caller
     that changes the learning rate between staging and the call (a schedule writing param_groups) gets a new prepared
     call; that call must build its own prologue, not take the staged table: stage at lr = a, switch to lr = b, run:
     BIT-identical to the same call run unstaged at lr = b, losses and both moments included."""
     from mfcd import engine
-    n, m, d, N = 4096, 4096, 64, 64 * 150 + 17
     U0, V0, u, i, j, z = _synthetic(n, m, d, 2 * N, seed=35)
     recs = [_records(u[k * N:(k + 1) * N], i[k * N:(k + 1) * N], j[k * N:(k + 1) * N], z[k * N:(k + 1) * N], n, m, dev).dev
             for k in range(2)]
     side = torch.cuda.Stream(device=dev)
     engine.set_train_path("resident")
     try:
-        assert engine.train_plan(N, 64, n, m, d)["resident_lookahead"] > 0   # the form whose prologue is staged
+        _assert_prologue_is_staged(n, m, d, N)
         outs = []
         for staged in (True, False):
             model, opt = _model_from(U0, V0, dev, 1e-3, 1e-5)

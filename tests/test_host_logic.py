@@ -43,6 +43,47 @@ def test_library_exports_every_declared_symbol():
     assert L.mfcd_uvt_workspace_bytes(100, 100, 8) > 0
 
 
+def test_resident_plans_follow_the_slice_rule_and_layouts_ignore_the_knobs():
+    """Over the grid of tools/plan_table.py, with the resident form forced: wherever the library plans it, the plan is a
+    slice of the one rule (csrc/resident.hip: resident_slices) - whole rows per wave, the wave count of that slice, at
+    most 4096 waves, four waves per workgroup.  And the workspace size, which the same rule decides, is a function of the
+    sizes alone: the same under every train path and every look-ahead setting."""
+    import ctypes
+    import importlib.util
+    from mfcd import _lib
+    spec = importlib.util.spec_from_file_location("plan_table", os.path.join(ROOT, "tools", "plan_table.py"))
+    grid = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(grid)
+    L = _lib.load()
+    cases = [(N, B, n, m, d) for n, m, d in grid.SHAPES for B in grid.BATCHES
+             for N in (B, 3 * B, 40 * B, 300 * B + 5)]
+    planned = 0
+    try:
+        assert L.mfcd_set_train_path(2) == 0
+        plan = _lib.TrainPlan()
+        for N, B, n, m, d in cases:
+            for bf16 in (0, 1):
+                rc = L.mfcd_train_plan_query(N, B, n, m, d, bf16, ctypes.byref(plan))
+                assert rc in (0, -1), (rc, N, B, n, m, d)
+                if rc == 0:
+                    planned += 1
+                    q, waves = plan.resident_q, plan.resident_waves
+                    assert plan.form == 2 and (64 * q) % d == 0, (q, N, B, n, m, d)
+                    assert waves == -(-(n + m) * d // (64 * q)) and waves <= 4096, (q, waves, N, B, n, m, d)
+                    assert plan.resident_blocks == -(-waves // 4), (waves, plan.resident_blocks)
+        assert planned > len(cases)          # (more than half of the grid: the check is not vacuous)
+        sizes = {c: L.mfcd_train_workspace_bytes(*c) for c in cases}
+        for path in range(4):
+            assert L.mfcd_set_train_path(path) == 0
+            for look in (-1, 0, 4, 8):
+                assert L.mfcd_set_tuning(_lib.TUNE_KEYS["resident_lookahead"], look) == 0
+                for c in cases:
+                    assert L.mfcd_train_workspace_bytes(*c) == sizes[c] > 0, (path, look, c)
+    finally:
+        L.mfcd_set_train_path(0)
+        L.mfcd_set_tuning(_lib.TUNE_KEYS["resident_lookahead"], -1)
+
+
 def test_missing_library_is_loud(monkeypatch):
     from mfcd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
