@@ -703,6 +703,53 @@ int mfcd_pair_stats_rows(const float *A, int64_t lda, const float *X, int64_t ld
 int mfcd_pair_grad_rows(const float *A, int64_t lda, const float *X, int64_t ldx, int rows, int m, double scale, float *G,
                         int64_t ldg, void *stream);
 
+/*
+ * The two entries above under a pair law (no reference counterpart: per sampling strategy, the risk that the strategy's
+ * own test split estimates, and the gradient of that risk).  The unordered pair {i, j} of a row carries the weight
+ *     w_ij = (alpha_i beta_j + alpha_j beta_i, or 1 without alpha / beta)
+ *            * [ |x_i - x_j| <= margin ]     if use_margin: the fp32 difference of the raw x (not scaled) against the
+ *                                            margin, as mfcd_sample_triplets decides it; the entry rounds the margin down
+ *                                            to the largest fp32 <= it once, which decides every pair identically
+ *            * [ label_i != label_j ]        if labels
+ * An ordered attempt law P(i, j) enters a symmetric loss only through P(i, j) + P(j, i), which is this family for every
+ * device strategy of mfcd_sample_triplets.
+ *   alpha, beta   fp32 [m] device vectors shared by all rows, both or neither; every entry finite and >= 0.  The caller
+ *                 keeps every entry either 0 or within 1e-6 of the largest (mfcd/pairs.py: PairLaw scales the largest to
+ *                 1 and zeroes smaller ones), so that every product is a normal fp32 number.
+ *   labels        int32 device labels: label_stride = 0, one vector [m] for all rows; label_stride >= m, row r reads
+ *                 labels + r * label_stride.  NULL: no label factor.
+ *   support       [rows] int64: the exact number of pairs i < j with w > 0
+ *   sums          [rows][5] f64: W = sum of w, then risk, bayes_risk, exp_acc, bayes_acc of mfcd_pair_stats_rows, each the
+ *                 sum of w * term.  Without alpha / beta W equals the support exactly.  A row with W = 0 has sums of
+ *                 exactly +0; a row with a non-finite entry in A or X has five NaN (its support is still counted).
+ *   G             [rows][ldg] fp32: g_i = sum over j != i of w_ij (sigmoid(a_i - a_j) - sigmoid(scale (x_i - x_j))), the
+ *                 derivative of sums[r][1] with respect to a_i; exactly +0 where no pair of i has weight; all NaN for a
+ *                 row with a non-finite entry; columns >= m are not written.
+ * Kernels, arithmetic and determinism are those of the two entries above: one 256-thread workgroup per (row, tile of
+ * 1024 columns), the weight folded into every term by one fma, at most 64 terms in an fp32 run, f64 beyond, a finishing
+ * kernel with a fixed order for the sums, no floating-point atomics, two calls bit-equal, a row independent of its
+ * neighbours and of the leading dimensions.  The kernels are compiled per combination of the three factors: an absent
+ * factor costs nothing.
+ * Limits: those of the two entries above, and a law that is not NULL; MFCD_EINVAL also when exactly one of alpha / beta
+ * is given, when use_margin is set with a negative or NaN margin, or when labels are given with a label_stride that is
+ * neither 0 nor >= m; all before anything touches the device.  workspace: as the workspace_bytes entry says (56 bytes
+ * per (row, tile), longer inputs go through in blocks of rows; 0 = sizes out of range), 256-byte aligned.  No allocation
+ * and no host wait.
+ */
+typedef struct mfcd_pair_law {
+    const float *alpha, *beta;
+    const int32_t *labels;
+    int64_t label_stride;
+    int32_t use_margin, reserved;
+    double margin;
+} mfcd_pair_law;
+size_t mfcd_pair_law_stats_workspace_bytes(int rows, int m);
+int mfcd_pair_law_stats_rows(const float *A, int64_t lda, const float *X, int64_t ldx, int rows, int m, double scale,
+                             const mfcd_pair_law *law, int64_t *support, double *sums, void *workspace,
+                             size_t workspace_bytes, void *stream);
+int mfcd_pair_law_grad_rows(const float *A, int64_t lda, const float *X, int64_t ldx, int rows, int m, double scale,
+                            const mfcd_pair_law *law, float *G, int64_t ldg, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -315,6 +315,365 @@ __global__ __launch_bounds__(kPairThreads) void pair_grad_kernel(const float *__
     }
 }
 
+// ---- the same two kernels under a pair law (second follow-on) ----
+// Every unordered pair {i, j} of a row carries a weight
+//   w = (alpha_i beta_j + alpha_j beta_i   or 1)  *  [|x_i - x_j| <= margin]  *  [label_i != label_j],
+// each factor present or not (template flags HW, HM, HL: an absent factor costs no load and no instruction).  The sums
+// become sums of w * term, W = sum of w rides along, and `support` counts the pairs with w > 0.  The decomposition is
+// the unweighted kernels'; the LDS element grows to (a, x, alpha, beta) — still one broadcast read — plus the label:
+// 20 KiB per workgroup.  Masks fold into w (0 where masked) and every accumulation is fma(w, term, f); all terms of the
+// sums are non-negative, so w = 0 adds exactly +0.  The margin arrives rounded down to fp32: fabsf(dx) <= floor32(margin)
+// decides as (double)fabsf(dx) <= margin does.
+struct LawPartial {
+    long long support, bad;   // pairs with w > 0; non-finite entries among tile I's elements
+    double s[5];              // W, risk, bayes_risk, exp_acc, bayes_acc
+};
+static_assert(sizeof(LawPartial) == 56, "workspace layout");
+
+template <bool HW> struct LawElem { typedef float2 type; };
+template <> struct LawElem<true> { typedef float4 type; };
+
+struct LawArgs {
+    const float *alpha, *beta;     // [m], both or neither
+    const int32_t *labels;         // row r reads labels + r * label_stride
+    int64_t label_stride;
+    float margin;                  // floor32 of the caller's
+};
+
+template <bool HW, bool HM, bool HL>
+__device__ __forceinline__ float law_weight(float dx, float ali, float bei, int li, float alj, float bej, int lj, float mg)
+{
+    float w = HW ? fmaf(ali, bej, __fmul_rn(alj, bei)) : 1.0f;   // a product of its own: never contracted
+    if (HM) w = fabsf(dx) <= mg ? w : 0.0f;
+    if (HL) w = li != lj ? w : 0.0f;
+    return w;
+}
+
+// One element of this thread against one column: f = log2 parts and linear parts of the two risks, exp_acc, bayes_acc, W.
+template <bool HW, bool HM, bool HL, bool MASKED>
+__device__ __forceinline__ void law_term(float ai, float xi, float ali, float bei, int li, float aj, float xj, float alj,
+                                         float bej, int lj, bool valid, float scale, float mg, unsigned &support,
+                                         float (&f)[7])
+{
+    const float da = ai - aj, dx = xi - xj, t = scale * dx;
+    float w = law_weight<HW, HM, HL>(dx, ali, bei, li, alj, bej, lj, mg);
+    if (MASKED) w = valid ? w : 0.0f;
+    support += (unsigned)(w > 0.0f);
+    const float ada = fabsf(da), at = fabsf(t);
+    const float ea = __builtin_amdgcn_exp2f(-1.4426950408889634f * ada);
+    const float et = __builtin_amdgcn_exp2f(-1.4426950408889634f * at);
+    const float l2a = __builtin_amdgcn_logf(1.0f + ea), l2t = __builtin_amdgcn_logf(1.0f + et);
+    const float qhi = __builtin_amdgcn_rcpf(1.0f + et), qlo = et * qhi;
+    const bool ga = ai > aj, la = ai < aj;
+    const bool against = ga != (t >= 0.0f);
+    const float miss = against ? qhi : qlo, hit = against ? qlo : qhi;
+    const float eacc = (ga || la) ? hit : 0.5f;
+    f[0] = fmaf(w, l2a, f[0]);
+    f[1] = fmaf(w, __fmul_rn(ada, miss), f[1]);      // rounded apart, so that w = 1 adds the same bits as a constant 1
+    f[2] = fmaf(w, l2t, f[2]);
+    f[3] = fmaf(w, __fmul_rn(at, qlo), f[3]);
+    f[4] = fmaf(w, eacc, f[4]);
+    f[5] = fmaf(w, qhi, f[5]);
+    if (HW) f[6] += w;                                 // without alpha/beta W is the support itself
+}
+
+template <bool HW, bool HM, bool HL, int KFULL, int KMASK>
+__device__ __forceinline__ void law_run(const typename LawElem<HW>::type *tile, const int *lab, int j0, int j1,
+                                        const float (&ai)[kPairIpt], const float (&xi)[kPairIpt],
+                                        const float (&ali)[kPairIpt], const float (&bei)[kPairIpt],
+                                        const int (&li)[kPairIpt], int tid, float scale, float mg, unsigned &support,
+                                        double (&acc)[7])
+{
+    for (int jb = j0; jb < j1; jb += kPairFlush) {
+        const int je = jb + kPairFlush < j1 ? jb + kPairFlush : j1;
+        float f[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // at most kPairFlush columns x 4 elements = 64 terms each
+#pragma unroll 4
+        for (int j = jb; j < je; ++j) {
+            const typename LawElem<HW>::type v = tile[j];
+            float alj = 0.0f, bej = 0.0f;
+            if constexpr (HW) {
+                alj = v.z;
+                bej = v.w;
+            }
+            const int lj = HL ? lab[j] : 0;
+#pragma unroll
+            for (int k = 0; k < kPairIpt; ++k) {
+                if (k < KFULL)
+                    law_term<HW, HM, HL, false>(ai[k], xi[k], ali[k], bei[k], li[k], v.x, v.y, alj, bej, lj, true, scale, mg,
+                                                support, f);
+                else if (k == KMASK)
+                    law_term<HW, HM, HL, true>(ai[k], xi[k], ali[k], bei[k], li[k], v.x, v.y, alj, bej, lj, tid < j - j0,
+                                               scale, mg, support, f);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 7; ++q) acc[q] += (double)f[q];
+    }
+}
+
+template <bool HW> __device__ __forceinline__ typename LawElem<HW>::type law_elem(float a, float x, float al, float be);
+template <> __device__ __forceinline__ float2 law_elem<false>(float a, float x, float, float) { return make_float2(a, x); }
+template <> __device__ __forceinline__ float4 law_elem<true>(float a, float x, float al, float be)
+{
+    return make_float4(a, x, al, be);
+}
+
+template <bool HW, bool HM, bool HL>
+__global__ __launch_bounds__(kPairThreads) void pair_law_tiles_kernel(const float *__restrict__ A, int64_t lda,
+                                                                      const float *__restrict__ X, int64_t ldx, LawArgs law,
+                                                                      int m, int T, float scale,
+                                                                      LawPartial *__restrict__ part)
+{
+    __shared__ typename LawElem<HW>::type tile[kPairTile];
+    __shared__ int lab[HL ? kPairTile : 1];
+    __shared__ long long red_c[kPairThreads / 64][2];
+    __shared__ double red_s[kPairThreads / 64][7];
+    const int tid = threadIdx.x;
+    const int64_t r = blockIdx.x / T;
+    const int I = (int)(blockIdx.x - r * T);
+    const float *a = A + r * lda, *x = X + r * ldx;
+    const int32_t *lb = HL ? law.labels + r * law.label_stride : nullptr;
+
+    float ai[kPairIpt], xi[kPairIpt], ali[kPairIpt], bei[kPairIpt];
+    int li[kPairIpt];
+    unsigned n_inf = 0;
+#pragma unroll
+    for (int k = 0; k < kPairIpt; ++k) {
+        const int p = I * kPairTile + k * kPairThreads + tid;
+        ai[k] = xi[k] = ali[k] = bei[k] = 0.0f;
+        li[k] = 0;
+        if (p < m) {
+            ai[k] = a[p];
+            xi[k] = x[p];
+            if (HW) {
+                ali[k] = law.alpha[p];
+                bei[k] = law.beta[p];
+            }
+            if (HL) li[k] = lb[p];
+            n_inf += (unsigned)(is_nonfinite_bits(ai[k]) || is_nonfinite_bits(xi[k]));
+        }
+    }
+
+    unsigned support = 0u;                             // <= 4 m <= 2^22 pairs per thread
+    double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int J = I; J < T; ++J) {
+        __syncthreads();                               // the previous tile's readers are done
+#pragma unroll
+        for (int k = 0; k < kPairIpt; ++k) {
+            const int e = k * kPairThreads + tid, p = J * kPairTile + e;
+            if (J == I) {                              // the tile is this workgroup's own elements
+                tile[e] = law_elem<HW>(ai[k], xi[k], ali[k], bei[k]);
+                if (HL) lab[e] = li[k];
+            } else {                                   // zero-filled pad columns: alpha = beta = 0, and jn bars them
+                const bool in = p < m;
+                tile[e] = law_elem<HW>(in ? a[p] : 0.0f, in ? x[p] : 0.0f, HW && in ? law.alpha[p] : 0.0f,
+                                       HW && in ? law.beta[p] : 0.0f);
+                if (HL) lab[e] = in ? lb[p] : 0;
+            }
+        }
+        __syncthreads();
+        const int jn = m - J * kPairTile < kPairTile ? m - J * kPairTile : kPairTile;   // columns of tile J that exist
+        const auto end = [jn](int j1) { return j1 < jn ? j1 : jn; };
+        if (J != I) {
+            for (int c = 0; c < kPairIpt; ++c)
+                law_run<HW, HM, HL, kPairIpt, kPairIpt>(tile, lab, c * kPairThreads, end((c + 1) * kPairThreads), ai, xi, ali,
+                                                        bei, li, tid, scale, law.margin, support, acc);
+        } else {                                       // an element past m only meets columns past m: j < jn bars both
+            law_run<HW, HM, HL, 0, 0>(tile, lab, 0, end(256), ai, xi, ali, bei, li, tid, scale, law.margin, support, acc);
+            law_run<HW, HM, HL, 1, 1>(tile, lab, 256, end(512), ai, xi, ali, bei, li, tid, scale, law.margin, support, acc);
+            law_run<HW, HM, HL, 2, 2>(tile, lab, 512, end(768), ai, xi, ali, bei, li, tid, scale, law.margin, support, acc);
+            law_run<HW, HM, HL, 3, 3>(tile, lab, 768, end(1024), ai, xi, ali, bei, li, tid, scale, law.margin, support, acc);
+        }
+    }
+
+    long long c2[2] = {(long long)support, (long long)n_inf};
+#pragma unroll
+    for (int q = 0; q < 2; ++q) c2[q] = wave_sum_xor(c2[q]);
+#pragma unroll
+    for (int q = 0; q < 7; ++q) acc[q] = wave_sum_xor(acc[q]);
+    if ((tid & 63) == 0) {
+        for (int q = 0; q < 2; ++q) red_c[tid >> 6][q] = c2[q];
+        for (int q = 0; q < 7; ++q) red_s[tid >> 6][q] = acc[q];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        LawPartial out;
+        out.support = out.bad = 0;
+        for (int w = 0; w < kPairThreads / 64; ++w) {
+            out.support += red_c[w][0];
+            out.bad += red_c[w][1];
+        }
+        double s7[7];
+        for (int q = 0; q < 7; ++q) {
+            s7[q] = 0.0;
+            for (int w = 0; w < kPairThreads / 64; ++w) s7[q] += red_s[w][q];   // fixed order
+        }
+        out.s[0] = HW ? s7[6] : (double)out.support;
+        out.s[1] = 0.6931471805599453 * s7[0] + s7[1];
+        out.s[2] = 0.6931471805599453 * s7[2] + s7[3];
+        out.s[3] = s7[4];
+        out.s[4] = s7[5];
+        part[blockIdx.x] = out;
+    }
+}
+
+// One wave per row, as pair_finish_kernel: a fixed order over the tiles, then a fixed tree over the lanes.
+__global__ __launch_bounds__(64) void pair_law_finish_kernel(const LawPartial *__restrict__ part, int T,
+                                                             int64_t *__restrict__ support, double *__restrict__ sums)
+{
+    const int64_t r = blockIdx.x;
+    long long c2[2] = {0, 0};
+    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int I = threadIdx.x; I < T; I += 64) {
+        const LawPartial &p = part[r * T + I];
+        c2[0] += p.support;
+        c2[1] += p.bad;
+        for (int q = 0; q < 5; ++q) s[q] += p.s[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 2; ++q) c2[q] = wave_sum_xor(c2[q]);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) s[q] = wave_sum_xor(s[q]);
+    if (threadIdx.x == 0) {
+        support[r] = c2[0];
+        for (int q = 0; q < 5; ++q) sums[r * 5 + q] = c2[1] ? __longlong_as_double(0x7ff8000000000000ll) : s[q];
+    }
+}
+
+// g_i = sum over j != i of w_ij (sigmoid(a_i - a_j) - sigmoid(scale (x_i - x_j))): pair_grad_kernel under the law.  The
+// column j == i still needs no mask: its term is exactly +0 whatever its weight.
+template <bool HW, bool HM, bool HL>
+__global__ __launch_bounds__(kPairThreads) void pair_law_grad_kernel(const float *__restrict__ A, int64_t lda,
+                                                                     const float *__restrict__ X, int64_t ldx, LawArgs law,
+                                                                     int m, int T, float scale, float *__restrict__ G,
+                                                                     int64_t ldg)
+{
+    __shared__ typename LawElem<HW>::type tile[kPairTile];
+    __shared__ int lab[HL ? kPairTile : 1];
+    const int tid = threadIdx.x;
+    const int64_t r = blockIdx.x / T;
+    const int I = (int)(blockIdx.x - r * T);
+    const float *a = A + r * lda, *x = X + r * ldx;
+    const int32_t *lb = HL ? law.labels + r * law.label_stride : nullptr;
+    const float mg = law.margin;
+
+    float ai[kPairIpt], xi[kPairIpt], ali[kPairIpt], bei[kPairIpt];
+    int li[kPairIpt];
+#pragma unroll
+    for (int k = 0; k < kPairIpt; ++k) {
+        const int p = I * kPairTile + k * kPairThreads + tid;
+        const bool in = p < m;                         // an element past m is computed and never stored
+        ai[k] = in ? a[p] : 0.0f;
+        xi[k] = in ? x[p] : 0.0f;
+        ali[k] = HW && in ? law.alpha[p] : 0.0f;
+        bei[k] = HW && in ? law.beta[p] : 0.0f;
+        li[k] = HL && in ? lb[p] : 0;
+    }
+
+    int bad = 0;                                       // the workgroup stages the whole row: it sees every entry
+    double acc[kPairIpt] = {0.0, 0.0, 0.0, 0.0};
+    for (int J = 0; J < T; ++J) {
+        __syncthreads();                               // the previous tile's readers are done
+#pragma unroll
+        for (int k = 0; k < kPairIpt; ++k) {
+            const int e = k * kPairThreads + tid, p = J * kPairTile + e;
+            const bool in = p < m;
+            const float va = in ? a[p] : 0.0f, vx = in ? x[p] : 0.0f;
+            bad |= (int)(is_nonfinite_bits(va) || is_nonfinite_bits(vx));
+            tile[e] = law_elem<HW>(va, vx, HW && in ? law.alpha[p] : 0.0f, HW && in ? law.beta[p] : 0.0f);
+            if (HL) lab[e] = in ? lb[p] : 0;
+        }
+        __syncthreads();
+        const int jn = m - J * kPairTile < kPairTile ? m - J * kPairTile : kPairTile;   // pad columns stay out
+        for (int jb = 0; jb < jn; jb += kGradFlush) {
+            const int je = jb + kGradFlush < jn ? jb + kGradFlush : jn;
+            float f[kPairIpt] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 4
+            for (int j = jb; j < je; ++j) {
+                const typename LawElem<HW>::type v = tile[j];
+                float alj = 0.0f, bej = 0.0f;
+                if constexpr (HW) {
+                    alj = v.z;
+                    bej = v.w;
+                }
+                const int lj = HL ? lab[j] : 0;
+#pragma unroll
+                for (int k = 0; k < kPairIpt; ++k) {
+                    const float dx = xi[k] - v.y;
+                    const float w = law_weight<HW, HM, HL>(dx, ali[k], bei[k], li[k], alj, bej, lj, mg);
+                    f[k] = fmaf(w, pair_sigmoid(ai[k] - v.x) - pair_sigmoid(scale * dx), f[k]);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kPairIpt; ++k) acc[k] += (double)f[k];
+        }
+    }
+
+    bad = __syncthreads_or(bad);
+    float *g = G + r * ldg;
+#pragma unroll
+    for (int k = 0; k < kPairIpt; ++k) {
+        const int p = I * kPairTile + k * kPairThreads + tid;
+        if (p < m) g[p] = bad ? __uint_as_float(0x7fc00000u) : (float)acc[k];     // rounded to fp32 once
+    }
+}
+
+// The largest fp32 <= margin (margin >= 0, not NaN).
+inline float floor32(double margin)
+{
+    float f = (float)margin;
+    if ((double)f > margin) f = std::nextafterf(f, -INFINITY);
+    return f;
+}
+
+// The shared part of the two law entries' argument check → 0, or MFCD_EINVAL; fills the kernels' LawArgs.
+inline int law_args(const mfcd_pair_law *law, int m, LawArgs *out)
+{
+    if (!law || (law->alpha == nullptr) != (law->beta == nullptr)) return MFCD_EINVAL;
+    if (law->use_margin && !(law->margin >= 0.0)) return MFCD_EINVAL;          // negative or NaN
+    if (law->labels && law->label_stride != 0 && law->label_stride < m) return MFCD_EINVAL;
+    out->alpha = law->alpha;
+    out->beta = law->beta;
+    out->labels = law->labels;
+    out->label_stride = law->label_stride;
+    out->margin = law->use_margin ? floor32(law->margin) : 0.0f;
+    return 0;
+}
+
+// F: a functor template over the three flags; picks the instantiation the law needs.
+template <template <bool, bool, bool> class F, class... Args>
+void law_dispatch(bool hw, bool hm, bool hl, Args... args)
+{
+    switch ((hw ? 1 : 0) | (hm ? 2 : 0) | (hl ? 4 : 0)) {
+    case 0: F<false, false, false>::go(args...); break;
+    case 1: F<true, false, false>::go(args...); break;
+    case 2: F<false, true, false>::go(args...); break;
+    case 3: F<true, true, false>::go(args...); break;
+    case 4: F<false, false, true>::go(args...); break;
+    case 5: F<true, false, true>::go(args...); break;
+    case 6: F<false, true, true>::go(args...); break;
+    default: F<true, true, true>::go(args...); break;
+    }
+}
+
+template <bool HW, bool HM, bool HL> struct LawTilesLaunch {
+    static void go(const float *A, int64_t lda, const float *X, int64_t ldx, LawArgs law, int nr, int m, int T, float scale,
+                   LawPartial *part, hipStream_t st)
+    {
+        hipLaunchKernelGGL((pair_law_tiles_kernel<HW, HM, HL>), dim3((unsigned)((int64_t)nr * T)), dim3(kPairThreads), 0, st,
+                           A, lda, X, ldx, law, m, T, scale, part);
+    }
+};
+
+template <bool HW, bool HM, bool HL> struct LawGradLaunch {
+    static void go(const float *A, int64_t lda, const float *X, int64_t ldx, LawArgs law, int nr, int m, int T, float scale,
+                   float *G, int64_t ldg, hipStream_t st)
+    {
+        hipLaunchKernelGGL((pair_law_grad_kernel<HW, HM, HL>), dim3((unsigned)((int64_t)nr * T)), dim3(kPairThreads), 0, st,
+                           A, lda, X, ldx, law, m, T, scale, G, ldg);
+    }
+};
+
 }  // namespace
 
 extern "C" size_t mfcd_pair_stats_workspace_bytes(int rows, int m)
@@ -365,6 +724,64 @@ extern "C" int mfcd_pair_grad_rows(const float *A, int64_t lda, const float *X, 
         hipLaunchKernelGGL(pair_grad_kernel, dim3((unsigned)((int64_t)nr * T)), dim3(kPairThreads), 0, (hipStream_t)stream,
                            A + (int64_t)r0 * lda, lda, X + (int64_t)r0 * ldx, ldx, m, T, (float)scale,
                            G + (int64_t)r0 * ldg, ldg);
+        MFCD_HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" size_t mfcd_pair_law_stats_workspace_bytes(int rows, int m)
+{
+    if (rows < 0 || m < 1 || m > kPairMaxCols) return 0;
+    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
+    return align_up((size_t)(R > 0 ? R : 1) * T * sizeof(LawPartial));
+}
+
+extern "C" int mfcd_pair_law_stats_rows(const float *A, int64_t lda, const float *X, int64_t ldx, int rows, int m,
+                                        double scale, const mfcd_pair_law *law, int64_t *support, double *sums,
+                                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!A || !X || rows < 0 || m < 1 || m > kPairMaxCols || lda < m || ldx < m || !support || !sums) return MFCD_EINVAL;
+    if (!std::isfinite(scale) || !std::isfinite((float)scale)) return MFCD_EINVAL;
+    LawArgs la;
+    if (law_args(law, m, &la)) return MFCD_EINVAL;
+    if (rows == 0) return 0;
+    if (!workspace) return MFCD_EINVAL;
+    if (workspace_bytes < mfcd_pair_law_stats_workspace_bytes(rows, m)) return MFCD_EWORKSPACE;
+    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
+    LawPartial *part = (LawPartial *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    for (int r0 = 0; r0 < rows; r0 += R) {             // stream order keeps one chunk's partials apart from the next's
+        const int nr = rows - r0 < R ? rows - r0 : R;
+        LawArgs lr = la;
+        if (lr.labels) lr.labels += (int64_t)r0 * lr.label_stride;
+        law_dispatch<LawTilesLaunch>(la.alpha != nullptr, law->use_margin != 0, la.labels != nullptr,
+                                     A + (int64_t)r0 * lda, lda, X + (int64_t)r0 * ldx, ldx, lr, nr, m, T, (float)scale, part,
+                                     st);
+        MFCD_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(pair_law_finish_kernel, dim3((unsigned)nr), dim3(64), 0, st, part, T, support + r0,
+                           sums + (int64_t)r0 * 5);
+        MFCD_HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int mfcd_pair_law_grad_rows(const float *A, int64_t lda, const float *X, int64_t ldx, int rows, int m,
+                                       double scale, const mfcd_pair_law *law, float *G, int64_t ldg, void *stream)
+{
+    if (!A || !X || !G || rows < 0 || m < 1 || m > kPairMaxCols || lda < m || ldx < m || ldg < m) return MFCD_EINVAL;
+    if (G == A || G == X) return MFCD_EINVAL;
+    if (!std::isfinite(scale) || !std::isfinite((float)scale)) return MFCD_EINVAL;
+    LawArgs la;
+    if (law_args(law, m, &la)) return MFCD_EINVAL;
+    if (rows == 0) return 0;
+    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
+    for (int r0 = 0; r0 < rows; r0 += R) {
+        const int nr = rows - r0 < R ? rows - r0 : R;
+        LawArgs lr = la;
+        if (lr.labels) lr.labels += (int64_t)r0 * lr.label_stride;
+        law_dispatch<LawGradLaunch>(la.alpha != nullptr, law->use_margin != 0, la.labels != nullptr,
+                                    A + (int64_t)r0 * lda, lda, X + (int64_t)r0 * ldx, ldx, lr, nr, m, T, (float)scale,
+                                    G + (int64_t)r0 * ldg, ldg, (hipStream_t)stream);
         MFCD_HIP_TRY(hipGetLastError());
     }
     return 0;

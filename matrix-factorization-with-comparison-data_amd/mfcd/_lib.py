@@ -94,6 +94,9 @@ SIGNATURES = {
     "mfcd_pair_stats_workspace_bytes": (_sz, [_i32, _i32]),
     "mfcd_pair_stats_rows": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _dbl, _i32, _vp, _vp, _vp, _sz, _vp]),
     "mfcd_pair_grad_rows": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _dbl, _vp, _i64, _vp]),
+    "mfcd_pair_law_stats_workspace_bytes": (_sz, [_i32, _i32]),
+    "mfcd_pair_law_stats_rows": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _dbl, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mfcd_pair_law_grad_rows": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _dbl, _vp, _vp, _i64, _vp]),
 }
 
 TUNE_KEYS = {"resident_lookahead": 3, "resident_spin_limit": 5, "uvt_target_wgs": 9, "uvt_min_stages": 10,
@@ -128,6 +131,12 @@ class Sampler(ctypes.Structure):
                 ("list_row_stride", ctypes.c_int32), ("users", _vp), ("n_users", ctypes.c_int32),
                 ("use_margin", ctypes.c_int32), ("margin", _dbl), ("X", _vp), ("A", _vp), ("B", _vp),
                 ("dx", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class PairLawC(ctypes.Structure):
+    """mfcd_pair_law of include/mfcd.h."""
+    _fields_ = [("alpha", _vp), ("beta", _vp), ("labels", _vp), ("label_stride", ctypes.c_int64),
+                ("use_margin", ctypes.c_int32), ("reserved", ctypes.c_int32), ("margin", _dbl)]
 
 
 _lib = None

@@ -9,7 +9,15 @@ returns.
 The risk can also be minimised: `pair_grad_rows` (mfcd_pair_grad_rows) is its gradient with respect to the score rows,
 `population_risk` the mean risk as a differentiable scalar of the factor tables, `fit_population` the fused loop of
 risk gradient and Adam step.  There is no CPU form of any of it.
+
+All of it also exists under a pair law (`PairLaw`; `strategy_law` builds the one a sampling strategy draws its attempts
+from): `pair_law_stats_rows` / `pair_law_grad_rows` are the weighted kernel calls, and `law_risk`, `law_metrics` and
+`fit_law` are `population_risk`, `pairwise_metrics` and `fit_population` under it.  The law's risk is normalised
+globally, by the weight of all users.
 """
+import copy
+import ctypes
+
 import numpy as np
 import torch
 
@@ -59,6 +67,207 @@ def pair_grad_rows(A, X, scale=1.0):
     return G
 
 
+class PairLaw:
+    """A weight on the item pairs of every user: the law a population risk is taken under.  For a user whose truth row,
+    restricted to the law's columns, is x, the unordered pair {i, j} of those columns weighs
+        w_ij = (alpha_i beta_j + alpha_j beta_i, or 1)  *  [|x_i - x_j| <= margin]  *  [label_i != label_j],
+    each factor present only if given (include/mfcd.h: mfcd_pair_law).
+      alpha, beta   [k] non-negative finite weights, both or neither.  Each vector is scaled so that its largest entry is
+                    1 (the risk does not change) and positive entries below 1e-6 of the largest are set to 0, so that
+                    every product is a normal fp32 number.
+      labels        int [k] shared by all users, or [n, k], one row per user of the model
+      margin        a non-negative float, compared with the fp32 difference of the raw (unscaled) x
+      columns       the item numbers the law lives on: [k] shared, or [n, k] per user; None: all m items in order
+      users         the users the law is over (None: every user)
+    Validated once, here (ValueError); the tensors stay on `device` (None: where they are) as long as the law lives."""
+
+    def __init__(self, alpha=None, beta=None, labels=None, margin=None, columns=None, users=None, device=None):
+        if (alpha is None) != (beta is None):
+            raise ValueError("a pair law takes alpha and beta together or neither")
+        k = None
+        if columns is not None:
+            columns = torch.as_tensor(columns)
+            if columns.dim() not in (1, 2) or columns.dtype.is_floating_point or columns.shape[-1] < 1:
+                raise ValueError(f"columns must be item numbers [k] or [n, k], got {tuple(columns.shape)}")
+            if int(columns.min()) < 0:
+                raise ValueError("a column number is negative")
+            columns = columns.to(torch.int64)
+            k = columns.shape[-1]
+            self.max_column = int(columns.max())
+        if alpha is not None:
+            vs = []
+            for name, v in (("alpha", alpha), ("beta", beta)):
+                v = torch.as_tensor(v).detach().double().reshape(-1).cpu()
+                if not bool(torch.isfinite(v).all()) or bool((v < 0).any()):
+                    raise ValueError(f"{name} must be finite and non-negative")
+                if k is not None and v.numel() != k:
+                    raise ValueError(f"{name} has {v.numel()} entries for {k} columns")
+                k = v.numel()
+                top = float(v.max()) if k else 0.0
+                if top > 0:
+                    v = v / top
+                    v = torch.where(v < 1e-6, torch.zeros_like(v), v)
+                vs.append(v.float().contiguous())
+            alpha, beta = vs
+        if labels is not None:
+            labels = torch.as_tensor(labels)
+            if labels.dim() not in (1, 2) or labels.dtype.is_floating_point or (k is not None and labels.shape[-1] != k):
+                raise ValueError(f"labels must be integers [k] or [n, k] with k = {k}, got {tuple(labels.shape)}")
+            if labels.dim() == 2 and columns is not None and columns.dim() == 2 and labels.shape[0] != columns.shape[0]:
+                raise ValueError(f"{labels.shape[0]} label rows for {columns.shape[0]} column rows")
+            labels = labels.to(torch.int32).contiguous()
+        if margin is not None:
+            margin = float(margin)
+            if not margin >= 0.0:
+                raise ValueError(f"the margin must be a non-negative number, got {margin}")
+        if users is not None:
+            users = torch.as_tensor(users).reshape(-1).to(torch.int64)
+        dev = None if device is None else torch.device(device)
+        put = (lambda t: t) if dev is None else (lambda t: t.to(dev))
+        self.alpha, self.beta = (None, None) if alpha is None else (put(alpha), put(beta))
+        self.labels = None if labels is None else put(labels)
+        self.columns = None if columns is None else put(columns)
+        self.users = None if users is None else put(users)
+        self.margin = margin
+        if dev is None and alpha is not None:           # follow the other tensors, if any is on a device
+            for t in (self.labels, self.columns, self.users):
+                if t is not None and t.is_cuda:
+                    self.alpha, self.beta = self.alpha.to(t.device), self.beta.to(t.device)
+                    break
+        self.k = k if k is not None else (None if labels is None else labels.shape[-1])
+
+    @property
+    def trivial(self):
+        """Every pair of every user with weight 1: the unweighted kernels' law."""
+        return all(t is None for t in (self.alpha, self.labels, self.margin, self.columns, self.users))
+
+    def per_user(self):
+        return (self.labels is not None and self.labels.dim() == 2) or (self.columns is not None and self.columns.dim() == 2)
+
+    def for_rows(self, ids):
+        """The law of the rows of users `ids` (an index tensor): per-user labels and columns restricted to them."""
+        law = copy.copy(self)
+        if self.labels is not None and self.labels.dim() == 2:
+            law.labels = self.labels[ids].contiguous()
+        if self.columns is not None and self.columns.dim() == 2:
+            law.columns = self.columns[ids]
+        return law
+
+    def take(self, rows):
+        """A block [b, m] restricted to the law's columns → [b, k]."""
+        if self.columns is None:
+            return rows
+        return rows[:, self.columns] if self.columns.dim() == 1 else torch.gather(rows, 1, self.columns)
+
+    def put_back(self, Gk, m):
+        """The transpose of `take`: [b, k] → [b, m], adding where a column is named twice (at most two addends per
+        destination for a law of `strategy_law`, so the sum does not depend on their order)."""
+        if self.columns is None:
+            return Gk
+        cols = self.columns if self.columns.dim() == 2 else self.columns.expand(Gk.shape[0], -1)
+        return torch.zeros((Gk.shape[0], m), dtype=Gk.dtype, device=Gk.device).scatter_add_(1, cols, Gk)
+
+    def _c(self, rows, m):
+        """The filled mfcd_pair_law of a call on `rows` rows of `m` columns."""
+        c = _lib.PairLawC()
+        for t in (self.alpha, self.beta):
+            if t is not None and t.numel() != m:
+                raise ValueError(f"the law has {t.numel()} weights for rows of {m} columns")
+        if self.labels is not None:
+            lab = self.labels
+            if lab.shape[-1] != m or (lab.dim() == 2 and lab.shape[0] != rows):
+                raise ValueError(f"labels {tuple(lab.shape)} do not fit {rows} rows of {m} columns")
+            c.labels, c.label_stride = _lib.ptr(lab), (m if lab.dim() == 2 else 0)
+        c.alpha, c.beta = _lib.ptr(self.alpha), _lib.ptr(self.beta)
+        c.use_margin, c.margin = (0, 0.0) if self.margin is None else (1, self.margin)
+        return c
+
+
+def pair_law_stats_rows(A, X, law, scale=1.0):
+    """`pair_stats_rows`' sums under a `PairLaw`, for rows already restricted to the law's columns (include/mfcd.h:
+    mfcd_pair_law_stats_rows) → (support int64 [rows]: the pairs i < j with w > 0, exact; sums f64 [rows, 5] = W, risk,
+    bayes_risk, exp_acc, bayes_acc, each the sum of w * term), on the device.  A row without weight has sums of exactly
+    +0, a row with a non-finite entry NaN sums.  Deterministic: two calls are bit-equal."""
+    A, X, rows, m, lda, ldx = _lib.row_pair(A, X, "pair_law_stats_rows")
+    L = _lib.load()
+    c = law._c(rows, m)
+    support = torch.empty(rows, dtype=torch.int64, device=A.device)
+    sums = torch.empty((rows, 5), dtype=torch.float64, device=A.device)
+    if rows == 0:
+        return support, sums
+    need = L.mfcd_pair_law_stats_workspace_bytes(rows, m)
+    if need == 0:
+        raise _lib.MfcdError(f"rows of {m} columns are outside the pair kernel's range [1, 1048576]")
+    ws = _lib.workspace(need, A.device)
+    _lib.check(L.mfcd_pair_law_stats_rows(A.data_ptr(), lda, X.data_ptr(), ldx, rows, m, float(scale), ctypes.byref(c),
+                                          _lib.ptr(support), _lib.ptr(sums), _lib.ptr(ws), ws.numel(),
+                                          _lib.stream_ptr(A.device)))
+    return support, sums
+
+
+def pair_law_grad_rows(A, X, law, scale=1.0):
+    """`pair_grad_rows` under a `PairLaw`, for rows already restricted to the law's columns (mfcd_pair_law_grad_rows) →
+    G fp32 [rows, m], g_i = sum over j != i of w_ij (sigmoid(a_i - a_j) - sigmoid(scale (x_i - x_j))): the gradient of
+    the `risk` sum of `pair_law_stats_rows`.  Exactly +0 where no pair of i has weight; a row with a non-finite entry is
+    all NaN.  Deterministic."""
+    A, X, rows, m, lda, ldx = _lib.row_pair(A, X, "pair_law_grad_rows")
+    L = _lib.load()
+    c = law._c(rows, m)
+    G = torch.empty((rows, m), dtype=torch.float32, device=A.device)
+    if rows == 0:
+        return G
+    if not 1 <= m <= 1 << 20:
+        raise _lib.MfcdError(f"rows of {m} columns are outside the pair kernel's range [1, 1048576]")
+    _lib.check(L.mfcd_pair_law_grad_rows(A.data_ptr(), lda, X.data_ptr(), ldx, rows, m, float(scale), ctypes.byref(c),
+                                         G.data_ptr(), m, _lib.stream_ptr(A.device)))
+    return G
+
+
+def strategy_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha=1.5, k=None, n_clusters=10, seed=0):
+    """The pair law a sampling strategy draws its attempts from, symmetrised (the loss of an ordered pair with label z is
+    that of the swapped pair with 1 - z, so an attempt law P(i, j) enters only through P(i, j) + P(j, i)) → PairLaw on
+    `device`.  The set-up of every strategy is the one `sampling.build_law` uses; `num_triplets` sets the margin's
+    threshold and svd's rank.  X: dense or a FactoredMatrix (nothing n x m is formed for a factored X; `svd` takes a
+    dense X only).
+      random                 every pair, weight 1 (the unweighted kernels)
+      margin                 pairs with |x_i - x_j| <= the threshold
+      popularity, variance   alpha = p / (1 - p), beta = p: two draws without replacement have P(i, j) = p_i p_j / (1 - p_i)
+      top_k                  each user's k best items
+      proximity              each user's k best then k worst items, one from each list; an item in both never pairs
+                             with itself
+      cluster                items of different k-means clusters, alpha = beta = 1 / |cluster|
+      svd                    the top items, for the top users only
+    `user_similarity` has no attempt law (its loop depends on the set built so far): ValueError."""
+    import generation_data as _gd
+    from . import sampling
+    device = torch.device(device)
+    m = X.shape[1]
+    if strategy == "random":
+        return PairLaw(device=device)
+    if strategy == "margin":
+        return PairLaw(margin=float(_gd._margin_threshold(X, num_triplets)), device=device)
+    if strategy in ("popularity", "variance"):
+        p = sampling.item_probs(X, strategy, device, popularity_method, alpha)
+        return PairLaw(alpha=p / (1.0 - p), beta=p, device=device)
+    if strategy == "top_k":
+        return PairLaw(columns=sampling.item_lists(X, strategy, k, device)[1], device=device)
+    if strategy == "proximity":
+        kk, best, worst = sampling.item_lists(X, strategy, k, device)
+        cols = torch.cat((best, worst), dim=1)
+        first = torch.cat((torch.ones(kk), torch.zeros(kk)))
+        return PairLaw(alpha=first, beta=1.0 - first, labels=cols, columns=cols, device=device)
+    if strategy == "cluster":
+        kk, labels = sampling.cluster_labels(X, n_clusters, seed, device)
+        w = 1.0 / torch.bincount(labels.long(), minlength=kk).double()[labels.long()]
+        return PairLaw(alpha=w, beta=w, labels=labels, device=device)
+    if strategy == "svd":
+        top_users, top_items = _gd._svd_top_sets(X, num_triplets)
+        return PairLaw(columns=top_items.astype(np.int64), users=top_users.astype(np.int64), device=device)
+    if strategy == "user_similarity":
+        raise ValueError("user_similarity has no attempt law: its loop depends on the set built so far")
+    raise ValueError(f"no pair law for triplet sampling strategy: {strategy}")
+
+
 def _host(t):
     return None if t is None else t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
 
@@ -90,6 +299,52 @@ def pairwise_from_counts(counts, sums, m):
 
 _KEYS = ("kendall_tau", "pairwise_accuracy", "expected_log_likelihood", "bayes_log_likelihood", "expected_accuracy",
          "bayes_accuracy")
+
+
+_LAW_KEYS = ("expected_log_likelihood", "bayes_log_likelihood", "expected_accuracy", "bayes_accuracy")
+
+
+def _law_src(U, V, X, users, row_block, law, what):
+    """RowBlocks over the law's users (users=None) with the law checked against the model's shape."""
+    src = RowBlocks(U, V, X, law.users if users is None else users, row_block, what)
+    if law.columns is not None and law.max_column >= src.m:
+        raise IndexError(f"the law names column {law.max_column} of a model of {src.m} items")
+    for t in (law.columns, law.labels):
+        if t is not None and t.dim() == 2 and t.shape[0] != src.n:
+            raise ValueError(f"the law has {t.shape[0]} per-user rows for a model of {src.n} users")
+    return src
+
+
+def _law_block(src, law, r0, r1):
+    """A block's law, scores and truth, restricted to the law's columns."""
+    lb = law.for_rows(src.ids[r0:r1]) if law.per_user() else law
+    return lb, lb.take(src.scores(r0, r1)), lb.take(src.truth(r0, r1))
+
+
+def law_metrics(U, V, X, law, s=1.0, users=None, row_block=2048):
+    """`pairwise_metrics` under a `PairLaw` (structure.compute_law_metrics): the four likelihood / accuracy values
+    weighted by the law, from `pair_law_stats_rows`; there are no Kendall keys.  The plain key is normalised globally,
+    sum over the users of the weighted sum / sum over the users of W (NaN for a law without weight; users with a
+    non-finite row stay out); the `_per_user` arrays are normalised per user (NaN where W_u = 0).  users=None: the
+    law's users."""
+    if law.trivial:
+        out = pairwise_metrics(U, V, X, s, users, row_block)
+        return {k: v for k, v in out.items() if k.startswith(_LAW_KEYS)}
+    src = _law_src(U.detach(), V.detach(), X, users, row_block, law, "pairwise metrics")
+    sums = torch.empty((src.k, 5), dtype=torch.float64, device=src.dev)
+    for r0, r1 in src.blocks():
+        lb, scores, truth = _law_block(src, law, r0, r1)
+        sums[r0:r1] = pair_law_stats_rows(scores, truth, lb, s)[1]
+    h = _host(sums)
+    good = ~np.isnan(h[:, 1])
+    W = h[good, 0].sum()
+    out = {}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for q, name in enumerate(_LAW_KEYS, start=1):
+            sign = -1.0 if q <= 2 else 1.0
+            out[name] = float(sign * h[good, q].sum() / W) if W > 0 else float("nan")
+            out[name + "_per_user"] = np.where(h[:, 0] > 0, sign * h[:, q] / h[:, 0], np.nan)
+    return out
 
 
 def pairwise_metrics(U, V, X, s=1.0, users=None, row_block=2048):
@@ -143,6 +398,37 @@ class _PopulationRisk(torch.autograd.Function):
         return dU, dV, None, None
 
 
+class _LawRisk(torch.autograd.Function):
+    """_PopulationRisk under a PairLaw: sum over the users of the weighted risk sums / sum over the users of W.  Blocks
+    are gathered to the law's columns, the k-column gradient is scattered back; 1 / sum W stays on the device."""
+
+    @staticmethod
+    def forward(ctx, U, V, src, s, law):
+        total = torch.zeros(5, dtype=torch.float64, device=src.dev)
+        for r0, r1 in src.blocks():
+            lb, scores, truth = _law_block(src, law, r0, r1)
+            total += pair_law_stats_rows(scores, truth, lb, s)[1].sum(0)
+        ctx.src, ctx.s, ctx.law, ctx.inv_w = src, s, law, (1.0 / total[0]).float()
+        return (total[1] / total[0]).float()               # 0 / 0 = NaN: a law without weight
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        src, law = ctx.src, ctx.law
+        coef = grad_out.float() * ctx.inv_w
+        dU_rows = torch.empty((src.k, src.U.shape[1]), dtype=torch.float32, device=src.dev)
+        dV = torch.zeros_like(src.V)
+        for r0, r1 in src.blocks():
+            lb, scores, truth = _law_block(src, law, r0, r1)
+            G = lb.put_back(pair_law_grad_rows(scores, truth, lb, ctx.s).mul_(coef), src.m)
+            torch.mm(G, src.V, out=dU_rows[r0:r1])
+            dV.addmm_(G.t(), src.rows_of(src.U, r0, r1))
+        if src.whole:
+            dU = dU_rows
+        else:
+            dU = torch.zeros_like(src.U).index_put_((src.ids,), dU_rows, accumulate=True)
+        return dU, dV, None, None, None
+
+
 def population_risk(U, V, X, s=1.0, users=None, row_block=2048):
     """The exact BTL population risk of the model U V^T against the label law q = sigmoid(s (x_i - x_j)): the mean, over
     the chosen users (None: every user; a user named twice counts twice) and over all m (m - 1) / 2 item pairs, of
@@ -156,6 +442,22 @@ def population_risk(U, V, X, s=1.0, users=None, row_block=2048):
     if src.k == 0:
         raise ValueError("the population risk needs at least one user")
     return _PopulationRisk.apply(U, V, src, float(s))
+
+
+def law_risk(U, V, X, law, s=1.0, users=None, row_block=2048):
+    """`population_risk` under a `PairLaw`, normalised globally: the sum over the users and the law's pairs of w * loss
+    divided by the sum of w → 0-dim fp32 device tensor, differentiable with respect to fp32 `U` and `V`.  It is not a
+    mean of per-user values: under `margin` a user with more close pairs is drawn more often.  users=None: the law's
+    users (every user if it names none).  A law without weight gives NaN; nothing waits for the device.  The law of
+    `random` is `population_risk` itself."""
+    if law.trivial:
+        return population_risk(U, V, X, s, users, row_block)
+    if torch.is_tensor(U) and U.is_cuda and (U.dtype != torch.float32 or V.dtype != torch.float32):
+        raise _lib.MfcdError("the population risk takes float32 factor tables")
+    src = _law_src(U.detach(), V.detach(), X, users, row_block, law, "the population risk")
+    if src.k == 0:
+        raise ValueError("the population risk needs at least one user")
+    return _LawRisk.apply(U, V, src, float(s), law)
 
 
 def fit_population(binding, X, s, steps, log_every=0, row_block=2048):
@@ -212,4 +514,72 @@ def fit_population(binding, X, s, steps, log_every=0, row_block=2048):
         return [], []
     for r0, r1 in blocks:
         risk_into(log[len(at) - 1], src.scores(r0, r1), src.truth(r0, r1))
+    return at, (log[:len(at)] * inv).cpu().tolist()       # the one device->host transfer of the run
+
+
+def fit_law(binding, X, s, steps, law, log_every=0, row_block=2048):
+    """`fit_population` on the risk of `law_risk`: descends and logs the law's globally normalised risk over the law's
+    users, blocks gathered to the law's columns and the gradient scattered back.  The law's total weight is a function of
+    X alone: it is computed once, before the loop (the one host wait; ValueError if it is 0).  The gradient rows of users
+    outside the law stay zero; weight decay still moves them, as the reference's dense Adam does.  The law of `random`
+    is `fit_population` itself."""
+    from . import engine
+    if law.trivial:
+        return fit_population(binding, X, s, steps, log_every, row_block)
+    if not isinstance(binding, engine.AdamBinding):
+        binding = engine.AdamBinding(*binding)
+    for name, t in zip(("model.U", "model.V"), binding.tensors()[:2]):
+        engine._require_cuda_param(t, name)                    # fp32 only: bf16 tables are refused here
+    L = _lib.load()
+    U, V, mU, vU, mV, vV = binding.tensors()
+    src = _law_src(U, V, X, None, row_block, law, "the population fit")
+    n, m, d, dev = src.n, src.m, U.shape[1], src.dev
+    steps, k = int(steps), int(log_every)
+    blocks = src.blocks()
+    total = torch.zeros((), dtype=torch.float64, device=dev)
+    for r0, r1 in blocks:                                   # W depends on X alone: truth rows stand in for the scores
+        lb = law.for_rows(src.ids[r0:r1]) if law.per_user() else law
+        truth = lb.take(src.truth(r0, r1))
+        total += pair_law_stats_rows(truth, truth, lb, s)[1][:, 0].sum()
+    total = float(total)                                    # the one host wait, outside the loop
+    if not total > 0:
+        raise ValueError("the law gives no pair of any user a weight: there is no risk to descend")
+    inv = 1.0 / total
+    at = ([t for t in range(0, steps, k)] + [steps]) if k > 0 else []
+    log = torch.zeros(max(len(at), 1), dtype=torch.float64, device=dev)
+    gU, gV = torch.zeros_like(U), torch.empty_like(V)
+    ptrs = [_lib.ptr(t) for t in (U, V, mU, vU, mV, vV, gU, gV)]
+    lr, b1, b2, eps, wd = binding.hyper()
+    stream = _lib.stream_ptr(dev)
+
+    def risk_into(slot, lb, scores, truth):
+        slot += pair_law_stats_rows(scores, truth, lb, s)[1][:, 1].sum()
+
+    try:
+        for t in range(steps):
+            logging = k > 0 and t % k == 0
+            if not src.whole:
+                gU.zero_()
+            for b, (r0, r1) in enumerate(blocks):
+                lb, scores, truth = _law_block(src, law, r0, r1)
+                if logging:
+                    risk_into(log[t // k], lb, scores, truth)
+                G = lb.put_back(pair_law_grad_rows(scores, truth, lb, s).mul_(inv), m)
+                Ub = src.rows_of(U, r0, r1)
+                if src.whole:
+                    torch.mm(G, V, out=gU[r0:r1])
+                else:                                       # users outside the law keep a zero gradient row
+                    gU.index_add_(0, src.ids[r0:r1], G @ V)
+                if b == 0:
+                    torch.mm(G.t(), Ub, out=gV)
+                else:
+                    gV.addmm_(G.t(), Ub)
+            _lib.check(L.mfcd_adam_dense(*ptrs, binding.step + 1, n, m, d, lr, b1, b2, eps, wd, stream))
+            binding.advance(1, defer=True)
+    finally:
+        binding.flush()         # an interrupt must not leave the moments ahead of the optimizer's `step` tensors
+    if k <= 0:
+        return [], []
+    for r0, r1 in blocks:
+        risk_into(log[len(at) - 1], *_law_block(src, law, r0, r1))
     return at, (log[:len(at)] * inv).cpu().tolist()       # the one device->host transfer of the run

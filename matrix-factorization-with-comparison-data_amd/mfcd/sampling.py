@@ -62,6 +62,52 @@ def group_tables(labels, k):
     return members, offsets
 
 
+def item_probs(X, strategy, device, popularity_method="zipf", alpha=1.5):
+    """The item probabilities p [m] (float64 numpy) of `popularity` (generation_data.py:110-119) and `variance`
+    (generation_data.py:90-91)."""
+    import generation_data as _gd
+    if strategy == "popularity":
+        return _gd._popularity_probs(X.shape[1], popularity_method, alpha)
+    var = _gd._factored_column_variances(X).numpy() if _lib.is_factored(X) else \
+        torch.var(_on(X, device).dense, dim=0).double().cpu().numpy()
+    probs = var / var.sum()
+    if not np.isfinite(probs).all() or (probs < 0).any():          # e.g. one user: the unbiased variance is NaN
+        raise RuntimeError("probability tensor contains either `inf`, `nan` or element < 0")   # as torch.multinomial (ref:95)
+    return probs
+
+
+def item_lists(X, strategy, k, device):
+    """The per-user item lists of `proximity` (k best and k worst) and `top_k` (k best) → (k, best int32 [n, k],
+    worst int32 [n, k] or None), on the device.  A factored X never becomes dense: its lists come from mfcd_topk_rows
+    over the factors (one call, all n rows)."""
+    import generation_data as _gd
+    m = X.shape[1]
+    Xd = _on(X, device)
+    fac, Xd = ((Xd.A, Xd.B), None) if Xd.factored else (None, Xd.dense)
+    if strategy == "proximity":
+        kk = int(_gd._proximity_k(m, k))
+        if fac:
+            best, worst = _topk.topk_rows(fac, kk, ends="both")
+        else:
+            best = torch.topk(Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
+            worst = torch.topk(-Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
+        return kk, best, worst
+    kk = int(_gd._top_k_k(m, k))
+    if fac:
+        best = _topk.topk_rows(fac, kk, ends="best")
+    else:
+        best = torch.topk(Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
+    return kk, best, None
+
+
+def cluster_labels(X, n_clusters, seed, device):
+    """The item clusters of `cluster` (generation_data.py:229-239) → (k, labels int32 [m] on the device)."""
+    kk = int(n_clusters)
+    if kk < 2:
+        raise ValueError("Cannot take a larger sample than population when 'replace=False'")   # numpy's (ref:241)
+    return kk, _cluster.kmeans(_cluster.item_points(X, device), kk, (int(seed) ^ 0x6B6D65616E73) & (2 ** 63 - 1))[0]
+
+
 def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha=1.5, k=None, max_attempts=5_000_000,
               n_clusters=10, seed=0):
     """The reference's per-strategy set-up (everything in front of its attempt loop, as generation_data defines it) → a
@@ -84,39 +130,18 @@ def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha
         law.report = lambda got, attempts: _gd._report_short_margin(X, got, num_triplets, c.margin, attempts)
         return law
     if strategy in ("popularity", "variance"):
-        if strategy == "popularity":                                    # generation_data.py:110-119
-            probs = _gd._popularity_probs(m, popularity_method, alpha)
-            c.pair_rule = 0
-        else:                                                            # generation_data.py:90-91
-            var = _gd._factored_column_variances(X).numpy() if _lib.is_factored(X) else \
-                torch.var(_on(X, device).dense, dim=0).double().cpu().numpy()
-            probs = var / var.sum()
-            c.pair_rule = 1
-            if not np.isfinite(probs).all() or (probs < 0).any():      # e.g. one user: the unbiased variance is NaN
-                raise RuntimeError("probability tensor contains either `inf`, `nan` or element < 0")   # as torch.multinomial (ref:95)
+        probs = item_probs(X, strategy, device, popularity_method, alpha)
+        c.pair_rule = 0 if strategy == "popularity" else 1
         cdf = np.cumsum(probs)
         cdf /= cdf[-1]
         c.law = LAW_ITEM_CDF
         c.cdf = law.hold(torch.from_numpy(cdf).to(device))
         return law
     if strategy in ("proximity", "top_k"):
-        # a factored X never becomes dense: its lists come from mfcd_topk_rows over the factors (one call, all n rows)
-        Xd = _on(X, device)
-        fac, Xd = ((Xd.A, Xd.B), None) if Xd.factored else (None, Xd.dense)
+        kk, best, worst = item_lists(X, strategy, k, device)
         if strategy == "proximity":
-            kk = int(_gd._proximity_k(m, k))
-            if fac:
-                best, worst = _topk.topk_rows(fac, kk, ends="both")
-            else:
-                best = torch.topk(Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
-                worst = torch.topk(-Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
             c.list_i, c.list_j, c.pair_rule = law.hold(best), law.hold(worst), 0
         else:
-            kk = int(_gd._top_k_k(m, k))
-            if fac:
-                best = _topk.topk_rows(fac, kk, ends="best")
-            else:
-                best = torch.topk(Xd, k=kk, dim=1)[1].to(torch.int32).contiguous()
             c.list_i = c.list_j = law.hold(best)
             c.pair_rule = 1
             law.budget = 3 * int(num_triplets)
@@ -133,10 +158,7 @@ def build_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha
         law.report = lambda got, attempts: _gd._report_short(got, num_triplets)
         return law
     if strategy == "cluster":                                           # generation_data.py:229-239
-        kk = int(n_clusters)
-        if kk < 2:
-            raise ValueError("Cannot take a larger sample than population when 'replace=False'")   # numpy's (ref:241)
-        labels = _cluster.kmeans(_cluster.item_points(X, device), kk, (int(seed) ^ 0x6B6D65616E73) & (2 ** 63 - 1))[0]
+        kk, labels = cluster_labels(X, n_clusters, seed, device)
         members, offsets = group_tables(labels, kk)
         c.law, c.k, c.list_row_stride = LAW_GROUPS, kk, int(members.numel())
         c.list_i, c.list_j = law.hold(members), law.hold(offsets)

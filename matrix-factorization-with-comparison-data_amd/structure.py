@@ -212,6 +212,70 @@ def train_model_population(model, X, s, optimizer, device, num_steps=1000, log_e
     return out
 
 
+def sampling_law(X, num_triplets, strategy="random", **kw):
+    """Extension (not in the reference): the law `get_triplets_from_X(X, num_triplets, strategy, **kw)` draws its attempts
+    from, as a weight on every user's item pairs → mfcd.pairs.PairLaw on the GPU (device=..., default: X's if it is on
+    one), for `law_risk`, `train_model_law` and `compute_law_metrics`: the exact value a test split drawn with that
+    strategy estimates, and what training with it converges to with unlimited comparisons.  kw: popularity_method,
+    alpha, k, n_clusters, seed, as the strategy takes them.  `user_similarity` has no such law (ValueError): its loop
+    depends on the set built so far.  Not part of the result dict / .pkl layout."""
+    device = kw.pop("device", None)
+    if device is None:
+        device = X.device if torch.is_tensor(X) and X.is_cuda else torch.device("cuda")
+    _need_gpu(device)
+    return _pairs.strategy_law(X, int(num_triplets), strategy, device, **kw)
+
+
+def compute_law_metrics(model, X, law, s=1.0, users=None, row_block=2048):
+    """Extension (not in the reference): `compute_pairwise_metrics` under a `sampling_law` — expected_log_likelihood,
+    bayes_log_likelihood, expected_accuracy and bayes_accuracy with every item pair weighted by the law (include/mfcd.h
+    mfcd_pair_law_stats_rows); there are no Kendall keys.  The plain key is normalised by the weight of all users (NaN
+    for a law without weight), the `_per_user` arrays by each user's own (NaN where that is 0).  users=None: the law's
+    users.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _pairs.law_metrics(model.U.data, model.V.data, X, law, s, users, row_block)
+
+
+def law_risk(model, X, law, s=1.0, users=None, row_block=2048):
+    """Extension (not in the reference): `population_risk` under a `sampling_law` — the sum over the users and item pairs
+    of w * BCE divided by the sum of w, the exact value that a test split drawn with the law's strategy estimates (a
+    global normalisation, not a mean of per-user values: under `margin` a user with more close pairs is drawn more
+    often).  Returns a 0-dim fp32 tensor on the model's device; `.backward()` fills `model.U.grad` / `model.V.grad`
+    (include/mfcd.h mfcd_pair_law_grad_rows).  users=None: the law's users.  NaN for a law without weight.  Not part of
+    the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _pairs.law_risk(model.U, model.V, X, law, s, users, row_block)
+
+
+def train_model_law(model, X, s, optimizer, device, law, num_steps=1000, log_every=100, row_block=2048):
+    """Extension (not in the reference): `train_model_population` on `law_risk(model, X, law, s)` — what training with the
+    law's sampling strategy converges to with unlimited comparisons.  Returns (steps, risks) as `train_model_population`
+    does, the risks being the law's.  torch.optim.Adam takes the fused loop (mfcd.pairs.fit_law), any other optimiser
+    zero_grad / law_risk / backward / step.  Users outside the law get no gradient, only weight decay; a law without
+    weight is a ValueError on the fused path.  Not part of the result dict / .pkl layout."""
+    _need_gpu(device)
+    model.train()
+    if _engine.fused_step_applies(model, optimizer):
+        out = _pairs.fit_law(_engine.AdamBinding(model, optimizer), X, s, num_steps, law, log_every, row_block)
+    else:
+        at, seen = [], []
+        for t in range(int(num_steps)):
+            optimizer.zero_grad()
+            loss = law_risk(model, X, law, s, None, row_block)
+            loss.backward()
+            optimizer.step()
+            if log_every > 0 and t % log_every == 0:
+                at.append(t)
+                seen.append(loss.detach())
+        if log_every > 0:
+            with torch.no_grad():
+                at.append(int(num_steps))
+                seen.append(law_risk(model, X, law, s, None, row_block))
+        out = (at, torch.stack(seen).double().cpu().tolist() if seen else [])
+    model.eval()
+    return out
+
+
 def compute_ground_truth_metrics(test_loader, X, device):
     """ref:1085-1127: MSE between sigmoid(X[u,i]-X[u,j]) (no scale) and the labels, per batch, and
     the accuracy of (diff > 0).  Two-element gather per sample, once per experiment: torch ops on
