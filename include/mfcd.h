@@ -750,6 +750,53 @@ int mfcd_pair_law_stats_rows(const float *A, int64_t lda, const float *X, int64_
 int mfcd_pair_law_grad_rows(const float *A, int64_t lda, const float *X, int64_t ldx, int rows, int m, double scale,
                             const mfcd_pair_law *law, float *G, int64_t ldg, void *stream);
 
+/*
+ * The exact user step of the BTL fit, "fold-in" (no reference counterpart: the reference only ever moves U and V
+ * together, structure.py:845-852): with the item table V [m][d] held fixed, row r of U_out is the minimiser of
+ *     f(u) = sum over t of  softplus(x_t) - z_t x_t  +  (l2 / 2) |u|^2,     x_t = u . delta_t,  delta_t = V[i_t] - V[j_t],
+ * over the records t in records[row_off[r] .. row_off[r + 1]).  row_off is an ascending device array of rows + 1
+ * entries; the records' u field is not read (grouping is the caller's job); z may be any value in [0, 1].  The sum is
+ * not a mean and l2 > 0 is required: the Hessian is then positive definite and the minimiser unique, also for separable
+ * labels.  The algorithm is fixed (tests/foldin_model.py restates it):
+ *   1. u starts at U_init[r], or at 0 when U_init is NULL.
+ *   2. Per iteration p_t = sigmoid(x_t), g = sum (p_t - z_t) delta_t + l2 u, H = sum p_t (1 - p_t) delta_t delta_t^T
+ *      + l2 I, and H s = -g is solved by Cholesky.
+ *   3. Backtracking with t = 1, 1/2, 1/4, ... until f(u + t s) <= f(u) + 1e-4 t g.s, at most 30 halvings; then
+ *      u <- u + t s.  The test is taken on the decrease f(u + t s) - f(u) summed term by term in f64 — with
+ *      h = t s . delta_t, softplus(x_t + h) - softplus(x_t) = log1p(p_t expm1(h)) for |h| < 1, the difference of the two
+ *      values otherwise, plus l2 (t u.s + t^2 |s|^2 / 2) — not on two rounded values of f: next to the minimiser the
+ *      decrease of a full Newton step is below the last bit of f, and a warm start from an fp32 row would otherwise
+ *      have its steps halved at random.  A step so small that this sum is itself at its rounding level is accepted when
+ *      the two values of f satisfy the test (at the latest when u + t s == u).
+ *   4. Status 0 (converged) when |t s|_inf <= xtol |u|_inf for the new u, or when s is exactly 0.
+ *   5. Status 1 (stopped) after max_iter iterations, when 30 halvings did not decrease f, or when a pivot of the
+ *      Cholesky factor is not positive; u is then the last accepted iterate.
+ * Precision: the iterate, x_t, p_t, g, H, f and the solve are f64; V is read as fp32 and widened exactly, so delta_t is
+ * exact.  U_out is the f64 iterate rounded once to fp32, objective[r] (nullable) is f at the f64 iterate,
+ * iters_status[r] = {iterations taken, status}.
+ * Status 2 is a row with invalid data — an i or j outside [0, m), a z that is NaN or outside [0, 1], a non-finite entry
+ * in a V row the row uses or in its U_init row, records == NULL for a row with records, row_off descending: U_out[r] is
+ * all NaN, the objective NaN, 0 iterations.  Indices are validated before any gather, so nothing is read outside the
+ * tables.  A row without records has u = 0, objective 0, 0 iterations and status 0, whatever its U_init.
+ * One workgroup per row (256 threads, one wave for d <= 16) runs the whole iteration: comparisons are staged in LDS
+ * mfcd_fold_in_chunk() at a time, threads own the gradient entries and 4 x 4 blocks of the Hessian, which is formed on
+ * the f64 vector pipe, and the Cholesky factor lives in LDS.  No floating-point atomics: two calls are bit-equal, and a
+ * row's outputs depend only on its own records, its U_init row, V and the scalars, not on the other rows of the call or
+ * on its position in it.
+ * Limits: 1 <= d <= mfcd_fold_in_max_d() = 64, m >= 1, rows >= 0 (0 = success, nothing launched), l2 finite and > 0,
+ * 1 <= max_iter <= 1000, xtol finite and >= 0, U_out overlapping neither V nor U_init; MFCD_EINVAL outside them and
+ * MFCD_EWORKSPACE for a short workspace, both before anything touches the device.  workspace: as the workspace_bytes
+ * entry says (256: the kernel stages nothing in device memory; 0 = sizes out of range).  No allocation and no host wait.
+ * Out of scope: d > 64 needs conjugate gradients instead of a Cholesky factor in LDS, and the item-side step couples
+ * two items per comparison, so it does not separate into rows.
+ */
+int mfcd_fold_in_max_d(void);
+int mfcd_fold_in_chunk(void);
+size_t mfcd_fold_in_workspace_bytes(int rows, int d);
+int mfcd_fold_in_users(const float *V, int m, int d, const mfcd_sample *records, const int64_t *row_off, int rows,
+                       double l2, const float *U_init, int max_iter, double xtol, float *U_out, double *objective,
+                       int32_t *iters_status, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

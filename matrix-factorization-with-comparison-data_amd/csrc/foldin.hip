@@ -1,0 +1,382 @@
+// foldin.hip — the exact user step of the BTL fit on gfx950: with the item table V held fixed, every
+// user's row u minimises
+//     f(u) = sum over the row's comparisons t of  softplus(x_t) - z_t x_t  +  (l2 / 2) |u|^2,
+//     x_t = u . delta_t,   delta_t = V[i_t] - V[j_t],
+// a strictly convex d-dimensional logistic regression.  Rows are independent, so one workgroup owns one row and runs
+// the whole damped Newton iteration for it: there is no communication between workgroups, no atomic and no workspace.
+//
+// Per iteration (include/mfcd.h states the algorithm; tests/foldin_model.py restates it in numpy):
+//   pass with Hessian   the row's comparisons go through LDS kFoldChunk = 64 at a time.  Staging gathers the two V rows
+//                       of a comparison and stores delta_t = (double)V[i] - (double)V[j], which is exact.  Thread t < 64
+//                       forms x_t by a serial f64 fma chain over k, then p_t, the weight p_t (1 - p_t), the residual
+//                       p_t - z_t and its term of f.  Thread k < d adds the chunk's residual * delta[.][k] to its
+//                       gradient entry; thread (bi, bj) adds the chunk's rank-64 update to the 4 x 4 block of the Hessian
+//                       it owns.  Gradient entries, Hessian blocks and the f partials live in registers for the whole
+//                       pass: every sum has one owner and a fixed order, so no reduction over d^2 entries is needed.
+//   Cholesky            in place in LDS on the lower triangle, right-looking, two barriers per column; the two
+//                       triangular solves keep one right-hand-side entry per thread, one barrier per column.
+//   line search         the same staging without the Hessian part.  The Armijo test is taken on the decrease
+//                       f(u + t s) - f(u) summed term by term, softplus(x + h) - softplus(x) = log1p(p expm1(h)) for
+//                       |h| < 1, not on two rounded values of f: close to the minimiser (a warm start from an fp32 row)
+//                       the decrease of a full Newton step is below the last bit of f, and a test on f itself would
+//                       halve such steps at random.
+//
+// Which pipe forms the Hessian: the f64 vector pipe (v_fma_f64).  On gfx950 the fp32 MFMA runs at the fp32 vector
+// rate and the f64 MFMA at the f64 vector rate, so a matrix form would save instruction issue and LDS reads, not
+// arithmetic; an fp32 Hessian is allowed by the contract but costs iterations where the weights span many orders of
+// magnitude (separable rows), and the pass is shared with the gradient, which has to be f64.  With 4 x 4 register
+// blocks a thread reads 8 doubles and one weight from LDS per 16 fma; all 64 lanes of a wave read at most 5 distinct
+// block columns of one staged row, which the LDS serves as broadcasts.
+//
+// LDS at d = 64: H 64 x 65 doubles (33 280 B, the odd stride keeps a column walk off one bank), the stage 64 x 65
+// doubles (33 280 B), seven vectors of 64 doubles and three of kFoldChunk: 72 KiB, two workgroups of 256 threads per
+// CU.  d <= 16 takes one wave per row (H and the stage are then at most 4.4 KiB each).  More rows than CUs is the
+// normal case; the hardware's workgroup dispatcher balances ragged rows.
+//
+// Out of scope: d > 64 needs conjugate gradients on Hessian-vector products instead of a Cholesky factor in LDS; the
+// item-side step couples two items per comparison and is not separable.
+#include <cmath>
+
+#include "common.h"
+
+namespace {
+
+constexpr int kFoldMaxD = 64;
+constexpr int kFoldChunk = 64;        // T: comparisons staged per pass of the inner loop
+constexpr int kFoldHalvings = 30;
+constexpr double kFoldArmijo = 1e-4;
+
+// doubles of LDS a workgroup needs for width d (the int flag rides in the last one)
+inline size_t fold_lds_doubles(int d)
+{
+    const int dpad = ((d + 3) >> 2) << 2, ld = dpad + 1;
+    return (size_t)dpad * ld + (size_t)kFoldChunk * ld + 6 * (size_t)dpad + 3 * (size_t)kFoldChunk + 5 + 1;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V, int m, int d,
+                                                     const mfcd_sample *__restrict__ rec,
+                                                     const int64_t *__restrict__ row_off, double l2,
+                                                     const float *__restrict__ U_init, int max_iter, double xtol,
+                                                     float *__restrict__ U_out, double *__restrict__ objective,
+                                                     int32_t *__restrict__ iters_status)
+{
+    constexpr int T = kFoldChunk;
+    constexpr int G = NT == 256 ? 16 : 8;              // the Cholesky update walks the trailing block on a G x G grid
+    extern __shared__ double fold_lds[];
+    const int tid = threadIdx.x, r = blockIdx.x;
+    const int nb = (d + 3) >> 2, dpad = nb << 2, ld = dpad + 1;
+    double *H = fold_lds, *D = H + dpad * ld, *u = D + T * ld, *g = u + dpad, *s = g + dpad, *ut = s + dpad;
+    double *sol = ut + dpad, *diag = sol + dpad, *w = diag + dpad, *res = w + T, *fpart = res + T, *scal = fpart + T;
+    int *flag = (int *)(scal + 5);
+    float *out = U_out + (int64_t)r * d;
+
+    const int64_t b = row_off[r], e = row_off[r + 1];
+    if (e == b) {                                      // no comparisons: u = 0 whatever U_init holds
+        for (int k = tid; k < d; k += NT) out[k] = 0.0f;
+        if (tid == 0) {
+            if (objective) objective[r] = 0.0;
+            iters_status[2 * r] = 0;
+            iters_status[2 * r + 1] = 0;
+        }
+        return;
+    }
+
+    // ---- validation: indices and labels before any gather, the start vector; V rows are checked as they are staged ----
+    if (tid == 0) *flag = 0;
+    __syncthreads();
+    {
+        bool bad = e < b || rec == nullptr;
+        if (!bad)
+            for (int64_t t = b + tid; t < e; t += NT) {
+                const mfcd_sample q = rec[t];
+                if ((unsigned)q.i >= (unsigned)m || (unsigned)q.j >= (unsigned)m || !(q.z >= 0.0f && q.z <= 1.0f)) bad = true;
+            }
+        if (U_init)
+            for (int k = tid; k < d; k += NT)
+                if (is_nonfinite_bits(U_init[(int64_t)r * d + k])) bad = true;
+        if (bad) *flag = 1;
+    }
+    __syncthreads();
+
+    auto invalid_row = [&]() {
+        const float qnan = __uint_as_float(0x7fc00000u);
+        for (int k = tid; k < d; k += NT) out[k] = qnan;
+        if (tid == 0) {
+            if (objective) objective[r] = (double)qnan;
+            iters_status[2 * r] = 0;
+            iters_status[2 * r + 1] = 2;
+        }
+    };
+    if (*flag) {
+        invalid_row();
+        return;
+    }
+
+    for (int k = tid; k < dpad; k += NT) u[k] = (U_init && k < d) ? (double)U_init[(int64_t)r * d + k] : 0.0;
+
+    // staging geometry: P = the power of two >= dpad lanes per comparison, NT / P comparisons per sweep
+    int lg = 2;
+    while ((1 << lg) < dpad) ++lg;
+    const int sk = tid & ((1 << lg) - 1), st0 = tid >> lg, ststep = NT >> lg;
+    const bool hthread = tid < nb * nb;
+    const int bi = hthread ? tid / nb : 0, bj = hthread ? tid - bi * nb : 0;
+
+    // One pass over the row at the point uv: returns f(uv); with HESS also g (gradient) and H (Hessian) at uv.  Without
+    // HESS uv is the trial point u + tt s, and scal[4] receives the decrease f(u + tt s) - f(u) summed term by term:
+    // with h = tt s . delta_t and p = sigmoid(u . delta_t), softplus(x + h) - softplus(x) = log1p(p expm1(h)), which is
+    // exact to the rounding of the difference itself, so the Armijo test sees decreases far below the rounding of f.
+    auto pass = [&](const double *uv, bool hess, double tt) -> double {
+        double facc = 0.0, gacc = 0.0, dacc = 0.0;
+        double hacc[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) hacc[a][c] = 0.0;
+        for (int64_t c0 = b; c0 < e; c0 += T) {
+            const int cn = (int)(e - c0 < T ? e - c0 : T);
+            __syncthreads();                           // the previous chunk's readers are done; uv is visible
+            if (sk < dpad)
+                for (int t = st0; t < cn; t += ststep) {
+                    double v = 0.0;
+                    if (sk < d) {
+                        const mfcd_sample q = rec[c0 + t];
+                        const float vi = V[(int64_t)q.i * d + sk], vj = V[(int64_t)q.j * d + sk];
+                        if (is_nonfinite_bits(vi) || is_nonfinite_bits(vj)) *flag = 1;
+                        v = (double)vi - (double)vj;
+                    }
+                    D[t * ld + sk] = v;
+                }
+            __syncthreads();
+            if (tid < cn) {
+                const double *row = D + tid * ld;
+                double x = 0.0;
+                for (int k = 0; k < d; ++k) x = fma(uv[k], row[k], x);
+                const double z = (double)rec[c0 + tid].z;
+                const double ex = exp(-fabs(x)), q = 1.0 / (1.0 + ex);
+                facc += (fmax(x, 0.0) + log1p(ex)) - z * x;
+                if (hess) {
+                    w[tid] = ex * q * q;                       // p (1 - p)
+                    res[tid] = (x >= 0.0 ? q : ex * q) - z;    // p - z
+                } else {
+                    double x0 = 0.0, sx = 0.0;
+                    for (int k = 0; k < d; ++k) {
+                        x0 = fma(u[k], row[k], x0);
+                        sx = fma(s[k], row[k], sx);
+                    }
+                    const double h = tt * sx, e0 = exp(-fabs(x0)), q0 = 1.0 / (1.0 + e0);
+                    if (fabs(h) < 1.0) {
+                        dacc += log1p((x0 >= 0.0 ? q0 : e0 * q0) * expm1(h)) - z * h;
+                    } else {                                   // a long step: the two softplus values differ visibly
+                        const double x1 = x0 + h;
+                        dacc += ((fmax(x1, 0.0) + log1p(exp(-fabs(x1)))) - (fmax(x0, 0.0) + log1p(e0))) - z * h;
+                    }
+                }
+            }
+            if (hess) {
+                __syncthreads();
+                if (tid < dpad)
+                    for (int t = 0; t < cn; ++t) gacc = fma(res[t], D[t * ld + tid], gacc);
+                if (hthread)
+                    for (int t = 0; t < cn; ++t) {
+                        const double *ra = D + t * ld + 4 * bi, *rb = D + t * ld + 4 * bj;
+                        const double wt = w[t];
+                        double wa[4], cb[4];
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) {
+                            wa[a] = wt * ra[a];
+                            cb[a] = rb[a];
+                        }
+#pragma unroll
+                        for (int a = 0; a < 4; ++a)
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) hacc[a][c] = fma(wa[a], cb[c], hacc[a][c]);
+                    }
+            }
+        }
+        __syncthreads();
+        if (tid < T) fpart[tid] = facc;
+        if (!hess && tid < T) w[tid] = dacc;
+        if (hess) {
+            if (tid < dpad) g[tid] = tid < d ? gacc + l2 * uv[tid] : 0.0;
+            if (hthread)
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const int hi = 4 * bi + a, hj = 4 * bj + c;
+                        // the padding rows and columns carry an identity block: their solution entries stay 0
+                        H[hi * ld + hj] = hacc[a][c] + (hi == hj ? (hi < d ? l2 : 1.0) : 0.0);
+                    }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double f = 0.0, uu = 0.0;
+            for (int t = 0; t < T; ++t) f += fpart[t];
+            for (int k = 0; k < d; ++k) uu = fma(uv[k], uv[k], uu);
+            scal[0] = f + 0.5 * l2 * uu;
+            if (!hess) {
+                double dsum = 0.0, us = 0.0, ss = 0.0;
+                for (int t = 0; t < T; ++t) dsum += w[t];
+                for (int k = 0; k < d; ++k) {
+                    us = fma(u[k], s[k], us);
+                    ss = fma(s[k], s[k], ss);
+                }
+                scal[4] = dsum + l2 * (tt * us + 0.5 * tt * tt * ss);
+            }
+        }
+        __syncthreads();
+        return scal[0];
+    };
+
+    double fcur = pass(u, true, 0.0);
+    if (*flag) {                                       // a V row of this user holds an inf or a NaN
+        invalid_row();
+        return;
+    }
+
+    int it = 0, status = 1;
+    for (;;) {                                         // g, H and fcur belong to u
+        ++it;
+        // ---- Cholesky of H (lower triangle, in place; the diagonal of L goes to diag[]) ----
+        bool pd = true;
+        for (int k = 0; k < dpad; ++k) {
+            __syncthreads();
+            const double dk = H[k * ld + k];
+            if (!(dk > 0.0)) {
+                pd = false;
+                break;
+            }
+            const double lkk = sqrt(dk);
+            if (tid == 0) diag[k] = lkk;
+            for (int i = k + 1 + tid; i < dpad; i += NT) H[i * ld + k] = H[i * ld + k] / lkk;
+            __syncthreads();
+            for (int i = k + 1 + (tid / G); i < dpad; i += G)
+                for (int j = k + 1 + (tid % G); j <= i; j += G)
+                    H[i * ld + j] = fma(-H[i * ld + k], H[j * ld + k], H[i * ld + j]);
+        }
+        if (!pd) break;                                // not reached for l2 > 0 and finite data; u stays as it is
+        // ---- L y = -g, then L^T s = y: one entry per thread, one barrier per column ----
+        double rhs = tid < dpad ? -g[tid] : 0.0;
+        for (int k = 0; k < dpad; ++k) {
+            if (tid == k) sol[k] = rhs / diag[k];
+            __syncthreads();
+            if (tid > k && tid < dpad) rhs = fma(-H[tid * ld + k], sol[k], rhs);
+        }
+        rhs = tid < dpad ? sol[tid] : 0.0;
+        for (int k = dpad - 1; k >= 0; --k) {
+            if (tid == k) s[k] = rhs / diag[k];
+            __syncthreads();
+            if (tid < k) rhs = fma(-H[k * ld + tid], s[k], rhs);
+        }
+        if (tid == 0) {
+            double smax = 0.0, gs = 0.0;
+            for (int k = 0; k < d; ++k) {
+                smax = fmax(smax, fabs(s[k]));
+                gs = fma(g[k], s[k], gs);
+            }
+            scal[1] = smax;
+            scal[2] = gs;
+        }
+        __syncthreads();
+        const double smax = scal[1], gs = scal[2];
+        if (smax == 0.0) {
+            status = 0;
+            break;
+        }
+        // ---- backtracking: t = 1, 1/2, ... until the Armijo decrease holds ----
+        double t = 1.0, fnew = 0.0;
+        bool accepted = false;
+        for (int h = 0; h <= kFoldHalvings; ++h) {
+            if (tid < dpad) ut[tid] = fma(t, s[tid], u[tid]);
+            fnew = pass(ut, false, t);
+            // either evaluation of the rule accepts: the term-wise decrease resolves steps that f cannot show, the values
+            // of f settle a step so small that the term-wise sum is itself at its rounding level (u + t s == u at last)
+            if (scal[4] <= kFoldArmijo * t * gs || fnew <= fcur + kFoldArmijo * t * gs) {
+                accepted = true;
+                break;
+            }
+            t *= 0.5;
+        }
+        if (!accepted) break;                          // status 1: u is the last accepted iterate
+        if (tid < dpad) u[tid] = ut[tid];
+        fcur = fnew;
+        if (tid == 0) {
+            double umax = 0.0;
+            for (int k = 0; k < d; ++k) umax = fmax(umax, fabs(ut[k]));
+            scal[3] = umax;
+        }
+        __syncthreads();
+        if (t * smax <= xtol * scal[3]) {
+            status = 0;
+            break;
+        }
+        if (it >= max_iter) break;
+        fcur = pass(u, true, 0.0);
+    }
+
+    __syncthreads();
+    for (int k = tid; k < d; k += NT) out[k] = (float)u[k];
+    if (tid == 0) {
+        if (objective) objective[r] = fcur;
+        iters_status[2 * r] = it;
+        iters_status[2 * r + 1] = status;
+    }
+}
+
+template <int NT>
+int fold_launch(const float *V, int m, int d, const mfcd_sample *rec, const int64_t *row_off, int rows, double l2,
+                const float *U_init, int max_iter, double xtol, float *U_out, double *objective, int32_t *iters_status,
+                hipStream_t st)
+{
+    const size_t lds = fold_lds_doubles(d) * sizeof(double);
+    static size_t allowed = 48 * 1024;                 // raise the dynamic-LDS limit only when needed
+    if (lds > allowed) {
+        MFCD_HIP_TRY(hipFuncSetAttribute((const void *)fold_in_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)lds));
+        allowed = lds;
+    }
+    hipLaunchKernelGGL(fold_in_kernel<NT>, dim3((unsigned)rows), dim3(NT), lds, st, V, m, d, rec, row_off, l2, U_init,
+                       max_iter, xtol, U_out, objective, iters_status);
+    return (int)hipGetLastError();
+}
+
+inline bool fold_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+}  // namespace
+
+extern "C" int mfcd_fold_in_max_d(void) { return kFoldMaxD; }
+
+extern "C" int mfcd_fold_in_chunk(void) { return kFoldChunk; }
+
+extern "C" size_t mfcd_fold_in_workspace_bytes(int rows, int d)
+{
+    if (rows < 0 || d < 1 || d > kFoldMaxD) return 0;
+    return 256;                                        // every sum of the kernel has one owner: nothing is staged in HBM
+}
+
+extern "C" int mfcd_fold_in_users(const float *V, int m, int d, const mfcd_sample *records, const int64_t *row_off,
+                                  int rows, double l2, const float *U_init, int max_iter, double xtol, float *U_out,
+                                  double *objective, int32_t *iters_status, void *workspace, size_t workspace_bytes,
+                                  void *stream)
+{
+    if (!V || !row_off || !U_out || !iters_status || m < 1 || d < 1 || d > kFoldMaxD || rows < 0) return MFCD_EINVAL;
+    if (!std::isfinite(l2) || !(l2 > 0.0) || max_iter < 1 || max_iter > 1000 || !std::isfinite(xtol) || xtol < 0.0)
+        return MFCD_EINVAL;
+    const size_t out_bytes = (size_t)rows * d * sizeof(float);
+    if (U_out == V || U_out == U_init || fold_overlap(U_out, out_bytes, V, (size_t)m * d * sizeof(float)) ||
+        (U_init && fold_overlap(U_out, out_bytes, U_init, out_bytes)))
+        return MFCD_EINVAL;
+    if (rows == 0) return 0;
+    if (!workspace) return MFCD_EINVAL;
+    if (workspace_bytes < mfcd_fold_in_workspace_bytes(rows, d)) return MFCD_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (d <= 16)
+        return fold_launch<64>(V, m, d, records, row_off, rows, l2, U_init, max_iter, xtol, U_out, objective, iters_status,
+                               st);
+    return fold_launch<256>(V, m, d, records, row_off, rows, l2, U_init, max_iter, xtol, U_out, objective, iters_status, st);
+}

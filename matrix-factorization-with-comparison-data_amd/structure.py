@@ -21,6 +21,7 @@ from torch.utils.data import DataLoader, Dataset
 from generation_data import *  # noqa: F401,F403  (ref:17 re-exports every sampler/generator name)
 import generation_data as _gd
 from mfcd import engine as _engine
+from mfcd import foldin as _foldin
 from mfcd import metrics as _metrics
 from mfcd import pairs as _pairs
 from mfcd import sampling as _sampling
@@ -274,6 +275,58 @@ def train_model_law(model, X, s, optimizer, device, law, num_steps=1000, log_eve
         out = (at, torch.stack(seen).double().cpu().tolist() if seen else [])
     model.eval()
     return out
+
+
+def _grouped_comparisons(data, n, m, device):
+    """The comparisons of `fit_users` / `refit_users` → (records, row_off, n) on `device`: a DataLoader's dataset is read
+    through mfcd.engine.dataset_records and packed as the training path packs it; a (u, i, j, z) tuple is taken as it
+    is.  n = None: max(u) + 1."""
+    if isinstance(data, (tuple, list)) and len(data) == 4:
+        u, i, j, z = (torch.as_tensor(t).reshape(-1).to(device) for t in data)
+    else:
+        rows = _engine.dataset_records(data.dataset if hasattr(data, "dataset") else data)
+        rec = torch.from_numpy(_engine.pack_records(rows, n, m)).to(device)
+        u, i, j, z = rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3].contiguous().view(torch.float32)
+    if n is None:
+        n = int(u.max()) + 1 if u.numel() else 0
+    return _foldin.group_by_user(u, i, j, z, n) + (n,)
+
+
+def fit_users(V_or_model, data, l2, U_init=None):
+    """Extension (not in the reference): fold-in — with the item table held fixed, the exact minimiser of every user's
+    own objective  sum over the user's comparisons of softplus(x) - z x + (l2 / 2) |u|^2,  x = u . (V[i] - V[j])  (a sum,
+    not a mean; l2 > 0), by one Newton solve per user on the device (include/mfcd.h mfcd_fold_in_users; d <= 64).
+    V_or_model: a model (its V and its number of users) or a bare fp32 V [m, d] on the GPU (n = max(u) + 1).  data: a
+    DataLoader from `split_dataset_from_triplets`, or a tuple of (u, i, j, z) tensors; the users need not have been in
+    training.  U_init: fp32 [n, d] start rows (None: 0).  Returns mfcd.foldin.FoldInResult with tensors U [n, d],
+    objective [n], iters [n], status [n] (0 converged, 1 stopped, 2 invalid data) on V's device; a user without
+    comparisons gets the zero row.  Not part of the result dict / .pkl layout."""
+    is_model = hasattr(V_or_model, "V") and hasattr(V_or_model, "U")
+    V = V_or_model.V.data if is_model else V_or_model
+    if not torch.is_tensor(V):
+        raise TypeError("fit_users takes a model or its V table")
+    _need_gpu(V.device)
+    rec, off, _ = _grouped_comparisons(data, V_or_model.U.shape[0] if is_model else None, V.shape[0], V.device)
+    return _foldin.fold_in_users(V, rec, off, l2, U_init)
+
+
+def refit_users(model, train_loader, weight_decay):
+    """Extension (not in the reference): the exact U-step on the model's own V — `fit_users` on the training comparisons,
+    warm-started from `model.U` — as a yardstick for the optimiser: how far the trained U is from the best U for the
+    trained V.  The reference descends  mean over the N training records of BCE + (wd / 2)(|U|^2 + |V|^2)  (coupled L2 is
+    Adam's weight_decay; structure.py:845-852 of the reference).  Multiplied by N, the part of it that depends on user
+    u's row is  sum over u's records of BCE + (wd N / 2) |U[u]|^2, and BCE(sigmoid(x), z) = softplus(x) - z x, so the
+    row objective of `fit_users` with  l2 = weight_decay * N  has the same minimiser.  weight_decay must be > 0.
+    Returns (result, objective_at_model): the FoldInResult and, per user, the same objective at `model.U[u]` formed with
+    torch ops in f64 (mfcd.foldin.row_objective).  objective_at_model - result.objective >= 0 is the diagnostic: what
+    each user's row still had to gain with V fixed.  The model is not changed.  Not part of the result dict / .pkl
+    layout."""
+    _need_gpu(model.U.device)
+    U, V = model.U.data, model.V.data
+    rec, off, _ = _grouped_comparisons(train_loader, U.shape[0], V.shape[0], V.device)
+    l2 = float(weight_decay) * rec.shape[0]
+    result = _foldin.fold_in_users(V, rec, off, l2, U.float().contiguous())
+    return result, _foldin.row_objective(U, V, rec, off, l2)
 
 
 def compute_ground_truth_metrics(test_loader, X, device):
