@@ -244,7 +244,8 @@ __global__ __launch_bounds__(256) void x_rows_kernel(const float *__restrict__ X
         const float mean = (float)(s1 / (double)m);
         const double mu = (double)mean;
         xm[r] = mean;
-        scc[r] = fmax(0.0, s2 - 2.0 * mu * s1 + (double)m * mu * mu);
+        const double cc = s2 - 2.0 * mu * s1 + (double)m * mu * mu;
+        scc[r] = cc < 0.0 ? 0.0 : cc;   // (not fmax: a NaN in the row must stay a NaN)
         sxx[r] = s2;
     }
 }
@@ -527,7 +528,7 @@ __device__ __forceinline__ double finish_row(const double *part_rows, const floa
     const double cc = s_cc - 2.0 * (mu * s_c - s_cx0) + (mu * mu * s_n - 2.0 * mu * s_nx0 + s_nx00);   // sum (x - mu)^2
     const double qr = s_cc + 2.0 * s_cx0 + s_nx00;                                       // sum x^2
     double *o = row_stats + (size_t)r * 8;
-    o[0] = ac; o[1] = aa; o[2] = fmax(0.0, cc); o[3] = (double)rm[r]; o[4] = mu;
+    o[0] = ac; o[1] = aa; o[2] = cc < 0.0 ? 0.0 : cc; o[3] = (double)rm[r]; o[4] = mu;   // (not fmax: NaN stays NaN)
     o[5] = qr; o[6] = 0.0; o[7] = 0.0;
     return qr;
 }
@@ -1104,6 +1105,9 @@ int g_uvt_target_wgs = 512;    // mfcd_set_tuning(MFCD_TUNE_UVT_TARGET_WGS): wor
 
 int g_uvt_min_stages = 8;      // mfcd_set_tuning(MFCD_TUNE_UVT_MIN_STAGES): stages a workgroup sweeps at least
 
+// tests/uvt_model.py (plan, form_for) repeats this plan and run_uvt's choice of form in Python: the tests' error bounds
+// need the first column of every split.  tests/test_uvt_cpu.py::test_python_plan_is_the_librarys_plan holds the copy to
+// this function through the workspace size, so a change of the plan OR of the layout below moves all three together.
 UvtWs plan_ws(char *base, int n, int m, int d)
 {
     UvtWs w;

@@ -79,6 +79,8 @@ def uvt_rows(U, V, row_ids):
     ids = host_ids.to(dtype=torch.int32, device=U.device).contiguous()
     k, m = ids.numel(), V.shape[0]
     out = torch.empty((k, m), dtype=torch.float32, device=U.device)
+    if k == 0:          # nothing to launch (an empty tensor has no data pointer to hand over)
+        return out
     _lib.check(L.mfcd_uvt_rows(_lib.ptr(U), _lib.ptr(V), _lib.ptr(ids), k, U.shape[0], m, U.shape[1], _lib.ptr(out),
                                _lib.stream_ptr(U.device)))
     return out
