@@ -787,8 +787,7 @@ int mfcd_pair_law_grad_rows(const float *A, int64_t lda, const float *X, int64_t
  * 1 <= max_iter <= 1000, xtol finite and >= 0, U_out overlapping neither V nor U_init; MFCD_EINVAL outside them and
  * MFCD_EWORKSPACE for a short workspace, both before anything touches the device.  workspace: as the workspace_bytes
  * entry says (256: the kernel stages nothing in device memory; 0 = sizes out of range).  No allocation and no host wait.
- * Out of scope: d > 64 needs conjugate gradients instead of a Cholesky factor in LDS, and the item-side step couples
- * two items per comparison, so it does not separate into rows.
+ * Out of scope: d > 64 needs conjugate gradients instead of a Cholesky factor in LDS.
  */
 int mfcd_fold_in_max_d(void);
 int mfcd_fold_in_chunk(void);
@@ -796,6 +795,45 @@ size_t mfcd_fold_in_workspace_bytes(int rows, int d);
 int mfcd_fold_in_users(const float *V, int m, int d, const mfcd_sample *records, const int64_t *row_off, int rows,
                        double l2, const float *U_init, int max_iter, double xtol, float *U_out, double *objective,
                        int32_t *iters_status, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The exact item step (no reference counterpart).  A comparison couples two item rows, but with U and the other items
+ * held fixed, item k's row minimises a logistic regression with an offset over the comparisons that hold k:
+ *     f_k(v) = sum over t of  softplus(x_t) - z_t x_t  +  (l2 / 2) |v|^2,     x_t = sigma_t (U[u_t] . v) + c_t,
+ *     sigma_t = [i_t = k] - [j_t = k]  (+1, -1, or 0 for a comparison of k with itself),
+ *     c_t = -sigma_t (U[u_t] . V[o_t]),  o_t the other item of the comparison.
+ * Row r solves item k = row_item[r] (row_item NULL: k = r, and then rows <= m) over records[row_off[r] .. row_off[r + 1])
+ * in the mfcd_sample layout; every one of them must have i = k or j = k (a comparison appears once in the row of each of
+ * its two items; grouping is the caller's job).  The start is V[k].  The solve is the iteration of the user step above,
+ * unchanged — steps 2 to 5 with delta_t = sigma_t U[u_t] and the x chain started at c_t instead of 0 — and v* is its
+ * result.  Outputs: V_out[r] = v_old + theta (v* - v_old), formed in f64 and rounded once to fp32; objective2 (nullable)
+ * [rows][2] = {f_k(v_old), f_k(v*)}; iters_status as for users.  theta = 1 is the exact minimiser of one item against
+ * the given rows of all others.  With theta = 1/2 every item may be moved in one call and the total objective
+ * F(U, V) = sum of all terms + (l2 / 2)(|U|^2 + |V|^2) still falls: every loss term depends on two item rows only, so by
+ * convexity F(V_new) <= F(V) - (1/2) sum over k of (f_k(v_k) - f_k(v*_k)).
+ * Precision: c_t is an f64 fma chain over the d products (double)U[u_t][k] (double)V[o_t][k], k ascending, formed once
+ * per call and kept in the workspace; delta_t is exact; everything else as for users.
+ * Status 2 (V_out[r] all NaN, both objectives NaN, 0 iterations): row_item[r] outside [0, m); a u outside [0, n) or an i
+ * or j outside [0, m); a record with neither i nor j equal to k; a z that is NaN or outside [0, 1]; a non-finite entry in
+ * V[k], in a U row the row uses or in a V[o_t] row it uses; records == NULL for a row with records, row_off descending
+ * or negative, or records that end beyond the 8 bytes per record the workspace has room for.  Indices are validated
+ * before any gather.  A row without records has v* = 0: V_out[r] = (1 - theta) v_old, objective2 = {(l2 / 2) |v_old|^2,
+ * 0}, 0 iterations, status 0.
+ * Same kernel as the user step with another staging rule: one workgroup per row, no floating-point atomics, no
+ * communication between workgroups; two calls are bit-equal, and a row's outputs do not depend on the other rows of the
+ * call or on its position in it (two rows may name one item and then agree bit for bit).
+ * Limits: 1 <= d <= 64, n >= 1, m >= 1, rows >= 0 (0 = success, nothing launched), l2 finite and > 0, 0 < theta <= 1,
+ * max_iter and xtol as for users, V_out [rows][d] overlapping neither U nor V; MFCD_EINVAL outside them and
+ * MFCD_EWORKSPACE for a workspace below the size for 0 records, both before anything touches the device.  workspace: as
+ * the workspace_bytes entry says for the number of records (256 + 8 per record, rounded up to 256; 0 = sizes out of
+ * range); the host cannot see row_off, so a workspace too short for a row's records shows as status 2 of that row.  No
+ * allocation and no host wait.
+ */
+size_t mfcd_item_step_workspace_bytes(int rows, int d, int64_t records);
+int mfcd_item_step(const float *U, int n, const float *V, int m, int d, const mfcd_sample *records,
+                   const int64_t *row_off, const int32_t *row_item, int rows, double l2, double theta, int max_iter,
+                   double xtol, float *V_out, double *objective2, int32_t *iters_status, void *workspace,
+                   size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

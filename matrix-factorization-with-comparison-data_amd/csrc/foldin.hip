@@ -1,9 +1,19 @@
-// foldin.hip — the exact user step of the BTL fit on gfx950: with the item table V held fixed, every
-// user's row u minimises
+// foldin.hip — the exact block steps of the BTL fit on gfx950.  The user step: with the item table V held
+// fixed, every user's row u minimises
 //     f(u) = sum over the row's comparisons t of  softplus(x_t) - z_t x_t  +  (l2 / 2) |u|^2,
 //     x_t = u . delta_t,   delta_t = V[i_t] - V[j_t],
 // a strictly convex d-dimensional logistic regression.  Rows are independent, so one workgroup owns one row and runs
 // the whole damped Newton iteration for it: there is no communication between workgroups, no atomic and no workspace.
+//
+// The item step is the same kernel with another staging policy (template parameter ITEM): with U and the other items
+// fixed, item k's row v minimises the same f over the comparisons that hold k, with
+//     x_t = v . delta_t + c_t,   delta_t = sigma_t U[u_t],   sigma_t = [i_t = k] - [j_t = k],   c_t = -sigma_t U[u_t] . V[o_t],
+// o_t the other item of the comparison: a logistic regression with an offset.  c_t does not change during a row's
+// iteration, so the workgroup forms it once in a prologue (an f64 fma chain over k per comparison, one thread each) and
+// keeps it in the call's workspace, 8 bytes per record that only this workgroup reads back; staging then gathers one U
+// row per comparison and puts c_t into the stage's pad column D[t * ld + dpad], which the user step leaves unused, so
+// the LDS budget is the same.  The x chains start at c_t instead of 0; everything after staging is shared code.  The
+// output is v_old + theta (v* - v_old): at theta = 1/2 all items may move at once and F still descends.
 //
 // Per iteration (include/mfcd.h states the algorithm; tests/foldin_model.py restates it in numpy):
 //   pass with Hessian   the row's comparisons go through LDS kFoldChunk = 64 at a time.  Staging gathers the two V rows
@@ -33,8 +43,7 @@
 // CU.  d <= 16 takes one wave per row (H and the stage are then at most 4.4 KiB each).  More rows than CUs is the
 // normal case; the hardware's workgroup dispatcher balances ragged rows.
 //
-// Out of scope: d > 64 needs conjugate gradients on Hessian-vector products instead of a Cholesky factor in LDS; the
-// item-side step couples two items per comparison and is not separable.
+// Out of scope: d > 64 needs conjugate gradients on Hessian-vector products instead of a Cholesky factor in LDS.
 #include <cmath>
 
 #include "common.h"
@@ -53,13 +62,26 @@ inline size_t fold_lds_doubles(int d)
     return (size_t)dpad * ld + (size_t)kFoldChunk * ld + 6 * (size_t)dpad + 3 * (size_t)kFoldChunk + 5 + 1;
 }
 
-template <int NT>
+// What the item step adds to a launch; the user step passes an empty one and never reads it.
+struct FoldItem {
+    const float *V;            // the item table [m][d]: the start rows and the partner rows of c_t
+    int m;
+    const int32_t *row_item;   // nullable: row r solves item r
+    double theta;
+    double *c;                 // c_t per record, indexed as the records are; written and read by the row's workgroup only
+    int64_t cap;               // records the workspace has room for: a row that ends beyond it is invalid
+};
+
+// ITEM = false: the user step.  V [m][d] is the gathered table, U_init the start rows, objective [rows].
+// ITEM = true: the item step.  V is the gathered table U [m = n][d], U_init is unused, item holds the rest,
+// objective [rows][2] = {f at the start, f at the solution}.
+template <int NT, bool ITEM>
 __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V, int m, int d,
                                                      const mfcd_sample *__restrict__ rec,
                                                      const int64_t *__restrict__ row_off, double l2,
                                                      const float *__restrict__ U_init, int max_iter, double xtol,
                                                      float *__restrict__ U_out, double *__restrict__ objective,
-                                                     int32_t *__restrict__ iters_status)
+                                                     int32_t *__restrict__ iters_status, const FoldItem item)
 {
     constexpr int T = kFoldChunk;
     constexpr int G = NT == 256 ? 16 : 8;              // the Cholesky update walks the trailing block on a G x G grid
@@ -72,7 +94,8 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
     float *out = U_out + (int64_t)r * d;
 
     const int64_t b = row_off[r], e = row_off[r + 1];
-    if (e == b) {                                      // no comparisons: u = 0 whatever U_init holds
+    const int own = ITEM ? (item.row_item ? item.row_item[r] : r) : 0;      // the item this row solves
+    if (!ITEM && e == b) {                             // no comparisons: u = 0 whatever U_init holds
         for (int k = tid; k < d; k += NT) out[k] = 0.0f;
         if (tid == 0) {
             if (objective) objective[r] = 0.0;
@@ -85,7 +108,7 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
     // ---- validation: indices and labels before any gather, the start vector; V rows are checked as they are staged ----
     if (tid == 0) *flag = 0;
     __syncthreads();
-    {
+    if constexpr (!ITEM) {
         bool bad = e < b || rec == nullptr;
         if (!bad)
             for (int64_t t = b + tid; t < e; t += NT) {
@@ -96,6 +119,21 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
             for (int k = tid; k < d; k += NT)
                 if (is_nonfinite_bits(U_init[(int64_t)r * d + k])) bad = true;
         if (bad) *flag = 1;
+    } else {
+        // the row's own item first, then every index of its records (m is the user count here), that each record holds
+        // the item, the labels, and that the row's c_t fit into the workspace
+        bool bad = (unsigned)own >= (unsigned)item.m || e < b || b < 0 || e > item.cap || (e > b && rec == nullptr);
+        if (!bad) {
+            for (int64_t t = b + tid; t < e; t += NT) {
+                const mfcd_sample q = rec[t];
+                if ((unsigned)q.u >= (unsigned)m || (unsigned)q.i >= (unsigned)item.m || (unsigned)q.j >= (unsigned)item.m ||
+                    (q.i != own && q.j != own) || !(q.z >= 0.0f && q.z <= 1.0f))
+                    bad = true;
+            }
+            for (int k = tid; k < d; k += NT)
+                if (is_nonfinite_bits(item.V[(int64_t)own * d + k])) bad = true;
+        }
+        if (bad) *flag = 1;
     }
     __syncthreads();
 
@@ -103,7 +141,11 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
         const float qnan = __uint_as_float(0x7fc00000u);
         for (int k = tid; k < d; k += NT) out[k] = qnan;
         if (tid == 0) {
-            if (objective) objective[r] = (double)qnan;
+            if constexpr (ITEM) {
+                if (objective) objective[2 * r] = objective[2 * r + 1] = (double)qnan;
+            } else {
+                if (objective) objective[r] = (double)qnan;
+            }
             iters_status[2 * r] = 0;
             iters_status[2 * r + 1] = 2;
         }
@@ -113,7 +155,46 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
         return;
     }
 
-    for (int k = tid; k < dpad; k += NT) u[k] = (U_init && k < d) ? (double)U_init[(int64_t)r * d + k] : 0.0;
+    if constexpr (ITEM) {
+        const float *vold = item.V + (int64_t)own * d;
+        if (e == b) {                                  // no comparisons: v* = 0, the row moves theta of the way to it
+            for (int k = tid; k < d; k += NT) out[k] = (float)fma(item.theta, -(double)vold[k], (double)vold[k]);
+            if (tid == 0) {
+                double vv = 0.0;
+                for (int k = 0; k < d; ++k) vv = fma((double)vold[k], (double)vold[k], vv);
+                if (objective) {
+                    objective[2 * r] = 0.5 * l2 * vv;
+                    objective[2 * r + 1] = 0.0;
+                }
+                iters_status[2 * r] = 0;
+                iters_status[2 * r + 1] = 0;
+            }
+            return;
+        }
+        // ---- prologue: c_t = -sigma_t U[u_t] . V[o_t], one thread per comparison, k ascending; both rows are checked ----
+        bool bad = false;
+        for (int64_t t = b + tid; t < e; t += NT) {
+            const mfcd_sample q = rec[t];
+            const int sigma = (q.i == own) - (q.j == own);
+            const float *ur = V + (int64_t)q.u * d, *vr = item.V + (int64_t)(q.i == own ? q.j : q.i) * d;
+            double acc = 0.0;
+            for (int k = 0; k < d; ++k) {
+                const float a = ur[k], c = vr[k];
+                if (is_nonfinite_bits(a) || is_nonfinite_bits(c)) bad = true;
+                acc = fma((double)a, (double)c, acc);
+            }
+            item.c[t] = sigma == 0 ? 0.0 : -(double)sigma * acc;
+        }
+        if (bad) *flag = 1;
+        __syncthreads();                               // c_t is visible to the workgroup that wrote it
+        if (*flag) {
+            invalid_row();
+            return;
+        }
+        for (int k = tid; k < dpad; k += NT) u[k] = k < d ? (double)vold[k] : 0.0;
+    } else {
+        for (int k = tid; k < dpad; k += NT) u[k] = (U_init && k < d) ? (double)U_init[(int64_t)r * d + k] : 0.0;
+    }
 
     // staging geometry: P = the power of two >= dpad lanes per comparison, NT / P comparisons per sweep
     int lg = 2;
@@ -139,7 +220,11 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
             if (sk < dpad)
                 for (int t = st0; t < cn; t += ststep) {
                     double v = 0.0;
-                    if (sk < d) {
+                    if constexpr (ITEM) {              // delta = sigma U[u] (exact); c_t rides in the pad column
+                        const mfcd_sample q = rec[c0 + t];
+                        if (sk < d) v = (double)((q.i == own) - (q.j == own)) * (double)V[(int64_t)q.u * d + sk];
+                        if (sk == 0) D[t * ld + dpad] = item.c[c0 + t];
+                    } else if (sk < d) {
                         const mfcd_sample q = rec[c0 + t];
                         const float vi = V[(int64_t)q.i * d + sk], vj = V[(int64_t)q.j * d + sk];
                         if (is_nonfinite_bits(vi) || is_nonfinite_bits(vj)) *flag = 1;
@@ -151,6 +236,7 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
             if (tid < cn) {
                 const double *row = D + tid * ld;
                 double x = 0.0;
+                if constexpr (ITEM) x = row[dpad];
                 for (int k = 0; k < d; ++k) x = fma(uv[k], row[k], x);
                 const double z = (double)rec[c0 + tid].z;
                 const double ex = exp(-fabs(x)), q = 1.0 / (1.0 + ex);
@@ -160,6 +246,7 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
                     res[tid] = (x >= 0.0 ? q : ex * q) - z;    // p - z
                 } else {
                     double x0 = 0.0, sx = 0.0;
+                    if constexpr (ITEM) x0 = row[dpad];
                     for (int k = 0; k < d; ++k) {
                         x0 = fma(u[k], row[k], x0);
                         sx = fma(s[k], row[k], sx);
@@ -230,6 +317,7 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
     };
 
     double fcur = pass(u, true, 0.0);
+    const double fstart = fcur;
     if (*flag) {                                       // a V row of this user holds an inf or a NaN
         invalid_row();
         return;
@@ -316,28 +404,40 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
     }
 
     __syncthreads();
-    for (int k = tid; k < d; k += NT) out[k] = (float)u[k];
+    if constexpr (ITEM) {                              // v_old + theta (v* - v_old) in f64, rounded once
+        const float *vold = item.V + (int64_t)own * d;
+        for (int k = tid; k < d; k += NT) out[k] = (float)fma(item.theta, u[k] - (double)vold[k], (double)vold[k]);
+    } else {
+        for (int k = tid; k < d; k += NT) out[k] = (float)u[k];
+    }
     if (tid == 0) {
-        if (objective) objective[r] = fcur;
+        if constexpr (ITEM) {
+            if (objective) {
+                objective[2 * r] = fstart;
+                objective[2 * r + 1] = fcur;
+            }
+        } else {
+            if (objective) objective[r] = fcur;
+        }
         iters_status[2 * r] = it;
         iters_status[2 * r + 1] = status;
     }
 }
 
-template <int NT>
+template <int NT, bool ITEM>
 int fold_launch(const float *V, int m, int d, const mfcd_sample *rec, const int64_t *row_off, int rows, double l2,
                 const float *U_init, int max_iter, double xtol, float *U_out, double *objective, int32_t *iters_status,
-                hipStream_t st)
+                const FoldItem &item, hipStream_t st)
 {
     const size_t lds = fold_lds_doubles(d) * sizeof(double);
-    static size_t allowed = 48 * 1024;                 // raise the dynamic-LDS limit only when needed
+    static size_t allowed = 48 * 1024;                 // raise the dynamic-LDS limit only when needed (per kernel)
     if (lds > allowed) {
-        MFCD_HIP_TRY(hipFuncSetAttribute((const void *)fold_in_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds));
+        MFCD_HIP_TRY(hipFuncSetAttribute((const void *)fold_in_kernel<NT, ITEM>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         allowed = lds;
     }
-    hipLaunchKernelGGL(fold_in_kernel<NT>, dim3((unsigned)rows), dim3(NT), lds, st, V, m, d, rec, row_off, l2, U_init,
-                       max_iter, xtol, U_out, objective, iters_status);
+    hipLaunchKernelGGL((fold_in_kernel<NT, ITEM>), dim3((unsigned)rows), dim3(NT), lds, st, V, m, d, rec, row_off, l2,
+                       U_init, max_iter, xtol, U_out, objective, iters_status, item);
     return (int)hipGetLastError();
 }
 
@@ -375,8 +475,45 @@ extern "C" int mfcd_fold_in_users(const float *V, int m, int d, const mfcd_sampl
     if (!workspace) return MFCD_EINVAL;
     if (workspace_bytes < mfcd_fold_in_workspace_bytes(rows, d)) return MFCD_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
+    const FoldItem none{};
     if (d <= 16)
-        return fold_launch<64>(V, m, d, records, row_off, rows, l2, U_init, max_iter, xtol, U_out, objective, iters_status,
-                               st);
-    return fold_launch<256>(V, m, d, records, row_off, rows, l2, U_init, max_iter, xtol, U_out, objective, iters_status, st);
+        return fold_launch<64, false>(V, m, d, records, row_off, rows, l2, U_init, max_iter, xtol, U_out, objective,
+                                      iters_status, none, st);
+    return fold_launch<256, false>(V, m, d, records, row_off, rows, l2, U_init, max_iter, xtol, U_out, objective,
+                                   iters_status, none, st);
+}
+
+extern "C" size_t mfcd_item_step_workspace_bytes(int rows, int d, int64_t records)
+{
+    if (rows < 0 || d < 1 || d > kFoldMaxD || records < 0 || records > (int64_t)1 << 56) return 0;
+    return 256 + align_up(sizeof(double) * (size_t)records);      // c_t per record behind the common 256 bytes
+}
+
+extern "C" int mfcd_item_step(const float *U, int n, const float *V, int m, int d, const mfcd_sample *records,
+                              const int64_t *row_off, const int32_t *row_item, int rows, double l2, double theta,
+                              int max_iter, double xtol, float *V_out, double *objective2, int32_t *iters_status,
+                              void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!U || !V || !row_off || !V_out || !iters_status || n < 1 || m < 1 || d < 1 || d > kFoldMaxD || rows < 0) return MFCD_EINVAL;
+    if (!row_item && rows > m) return MFCD_EINVAL;
+    if (!std::isfinite(l2) || !(l2 > 0.0) || !(theta > 0.0 && theta <= 1.0) || max_iter < 1 || max_iter > 1000 ||
+        !std::isfinite(xtol) || xtol < 0.0)
+        return MFCD_EINVAL;
+    const size_t out_bytes = (size_t)rows * d * sizeof(float);
+    if (V_out == V || V_out == U || fold_overlap(V_out, out_bytes, V, (size_t)m * d * sizeof(float)) ||
+        fold_overlap(V_out, out_bytes, U, (size_t)n * d * sizeof(float)))
+        return MFCD_EINVAL;
+    if (rows == 0) return 0;
+    if (!workspace) return MFCD_EINVAL;
+    // the record count is on the device (row_off[rows]): the host requires the fixed part, and a row whose records end
+    // beyond what the workspace holds is refused by its own workgroup (status 2)
+    if (workspace_bytes < mfcd_item_step_workspace_bytes(rows, d, 0)) return MFCD_EWORKSPACE;
+    const FoldItem item{V, m, row_item, theta, (double *)((char *)workspace + 256),
+                        (int64_t)((workspace_bytes - 256) / sizeof(double))};
+    hipStream_t st = (hipStream_t)stream;
+    if (d <= 16)
+        return fold_launch<64, true>(U, n, d, records, row_off, rows, l2, nullptr, max_iter, xtol, V_out, objective2,
+                                     iters_status, item, st);
+    return fold_launch<256, true>(U, n, d, records, row_off, rows, l2, nullptr, max_iter, xtol, V_out, objective2,
+                                  iters_status, item, st);
 }

@@ -6,8 +6,10 @@
 `metrics`  dense UV^T reconstruction / alignment metrics from the MFMA pass.
 `topk`     the k best / worst columns of rows of a dense or factored score matrix (mfcd_topk_rows).
 `pairs`    exact all-pairs BTL risk, pairwise accuracy and Kendall counts per row (mfcd_pair_stats_rows).
-`foldin`   the exact user step with V held fixed: one Newton solve per user (mfcd_fold_in_users).
+`foldin`   the exact block steps: one Newton solve per user with V fixed (mfcd_fold_in_users), one per item with U and
+           the other items fixed (mfcd_item_step).
+`alternating` the two block steps alternated: monotone exact-block descent of the regularised BTL objective.
 """
-from . import _lib, batching, engine, foldin, metrics, pairs, topk  # noqa: F401
+from . import _lib, alternating, batching, engine, foldin, metrics, pairs, topk  # noqa: F401
 
-__all__ = ["_lib", "batching", "engine", "foldin", "metrics", "pairs", "topk"]
+__all__ = ["_lib", "alternating", "batching", "engine", "foldin", "metrics", "pairs", "topk"]

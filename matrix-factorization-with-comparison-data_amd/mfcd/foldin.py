@@ -1,10 +1,12 @@
-"""The exact user step of the BTL fit on the device (include/mfcd.h: mfcd_fold_in_users): with the item table V held
-fixed, every user's row is the minimiser of its own l2-regularised logistic regression on delta_t = V[i_t] - V[j_t], found
-by a damped Newton iteration, one workgroup per user.
+"""The exact block steps of the BTL fit on the device (include/mfcd.h: mfcd_fold_in_users, mfcd_item_step).  With the item
+table V held fixed, every user's row is the minimiser of its own l2-regularised logistic regression on
+delta_t = V[i_t] - V[j_t]; with U and the other items held fixed, an item's row is the minimiser of a logistic regression
+with an offset over the comparisons that hold it.  Both are found by the same damped Newton iteration, one workgroup
+per row.
 
-`group_by_user` sorts comparisons by user (stable) into the records and row offsets the kernel reads; `fold_in_users` is
-the kernel call; `row_objective` forms the same objective at given rows with torch ops in f64 (a diagnostic, not a
-second solver).  There is no CPU form of the solve."""
+`group_by_user` / `group_by_item` sort comparisons (stable) into the records and row offsets the kernel reads;
+`fold_in_users` / `fold_in_items` are the kernel calls; `row_objective` and `total_objective` form the objectives with
+torch ops in f64 (diagnostics, not second solvers).  There is no CPU form of the solves."""
 import collections
 
 import torch
@@ -89,3 +91,87 @@ def row_objective(U, V, records, row_off, l2):
     terms = torch.clamp(x, min=0.0) + torch.log1p(torch.exp(-x.abs())) - z * x
     f = torch.zeros(rows, dtype=torch.float64, device=U.device).index_add_(0, owner, terms)
     return f + 0.5 * float(l2) * (Ud * Ud).sum(1)
+
+
+ItemStepResult = collections.namedtuple("ItemStepResult", ("V", "objective_start", "objective", "iters", "status"))
+ItemStepResult.__doc__ = """What `fold_in_items` returns, all on V's device: V fp32 [rows, d], the rows
+v_old + theta (v* - v_old); objective_start / objective f64 [rows], the item's objective f_k at v_old and at v*; iters
+int32 [rows]; status int32 [rows] as in FoldInResult."""
+
+
+def group_by_item(u, i, j, z, m):
+    """Comparisons (u, i, j, z) as four tensors of one length on one device → (records int32 [2 N, 4], row_off int64
+    [m + 1]) on that device, for `fold_in_items`: every comparison appears once in the row of its i and once in the row of
+    its j (so one with i = j appears twice in one row), item k's are records[row_off[k]:row_off[k + 1]].  The sort is
+    stable: a row keeps the order of the comparisons, and of the two copies of one comparison the i-copy comes first.
+    IndexError for an item outside [0, m)."""
+    u, i, j, z = (torch.as_tensor(t).reshape(-1) for t in (u, i, j, z))
+    if not (u.numel() == i.numel() == j.numel() == z.numel()):
+        raise ValueError("u, i, j and z must have one length")
+    m = int(m)
+    dev = i.device
+    i, j = i.to(torch.int64), j.to(device=dev, dtype=torch.int64)
+    for t in (i, j):
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= m):
+            raise IndexError(f"an item number lies outside [0, {m})")
+    zbits = z.to(device=dev, dtype=torch.float32).view(torch.int32)
+    rec = torch.stack((u.to(device=dev, dtype=torch.int32), i.to(torch.int32), j.to(torch.int32), zbits), dim=1)
+    key = torch.stack((i, j), dim=1).reshape(-1)                 # comparison t: its i-copy at 2 t, its j-copy at 2 t + 1
+    order = torch.sort(key, stable=True)[1]
+    rec = rec[order >> 1].contiguous()
+    row_off = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+    row_off[1:] = torch.cumsum(torch.bincount(key, minlength=m), 0)
+    return rec, row_off
+
+
+def fold_in_items(U, V, records, row_off, l2, row_item=None, theta=1.0, max_iter=50, xtol=2.0 ** -30):
+    """U fp32 [n, d] and V fp32 [m, d] on a GPU, `records` / `row_off` as `group_by_item` returns them (rows =
+    len(row_off) - 1), l2 > 0 → ItemStepResult.  Row r solves item k = row_item[r] (int32 [rows]; None: k = r): with U and
+    the other rows of V fixed, v* minimises sum_t softplus(x_t) - z_t x_t + (l2 / 2) |v|^2 over the row's records,
+    x_t = +-U[u_t] . (v - V[other item]), by the Newton iteration include/mfcd.h fixes, started at V[k]; the row returned
+    is V[k] + theta (v* - V[k]).  theta = 1: the exact minimiser of each row on its own; theta = 1/2: all items may move
+    in one call and the total objective still falls.  Rows with invalid data get status 2 and NaN; nothing is read
+    outside the tables.  Deterministic, and a row's result does not depend on the other rows.  Nothing waits for the
+    device."""
+    if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 for t in (U, V)) \
+            or U.shape[1] != V.shape[1]:
+        raise _lib.MfcdError("fold_in_items needs U [n, d] and V [m, d] as float32 tensors on a GPU device (there is no "
+                             "CPU fallback)")
+    if not torch.is_tensor(records) or not records.is_cuda or records.dtype != torch.int32 or records.dim() != 2 \
+            or records.shape[1] != 4 or not torch.is_tensor(row_off) or not row_off.is_cuda \
+            or row_off.dtype != torch.int64 or row_off.dim() != 1 or row_off.numel() < 1:
+        raise _lib.MfcdError("fold_in_items needs int32 [N, 4] records and int64 [rows + 1] offsets on the GPU "
+                             "(mfcd.foldin.group_by_item makes them)")
+    L = _lib.load()
+    dev = V.device
+    U, V = U.detach().to(dev).contiguous(), V.detach().contiguous()
+    records, row_off = records.to(dev).contiguous(), row_off.to(dev).contiguous()
+    (n, d), m = U.shape, V.shape[0]
+    rows = row_off.numel() - 1
+    if row_item is not None:
+        if not torch.is_tensor(row_item) or tuple(row_item.shape) != (rows,) or row_item.dtype != torch.int32:
+            raise _lib.MfcdError(f"row_item must be an int32 [{rows}] tensor")
+        row_item = row_item.to(dev).contiguous()
+    out = torch.empty((rows, d), dtype=torch.float32, device=dev)
+    objective = torch.empty((rows, 2), dtype=torch.float64, device=dev)
+    info = torch.empty((rows, 2), dtype=torch.int32, device=dev)
+    need = L.mfcd_item_step_workspace_bytes(rows, d, records.shape[0])
+    if need == 0:
+        raise _lib.MfcdError(f"d = {d} is outside the item step's range [1, {L.mfcd_fold_in_max_d()}]")
+    ws = _lib.workspace(need, dev)
+    _lib.check(L.mfcd_item_step(U.data_ptr(), n, V.data_ptr(), m, d, records.data_ptr() if records.numel() else None,
+                                row_off.data_ptr(), _lib.ptr(row_item), rows, float(l2), float(theta), int(max_iter),
+                                float(xtol), out.data_ptr(), objective.data_ptr(), info.data_ptr(), _lib.ptr(ws),
+                                ws.numel(), _lib.stream_ptr(dev)))
+    return ItemStepResult(out, objective[:, 0], objective[:, 1], info[:, 0], info[:, 1])
+
+
+def total_objective(U, V, u, i, j, z, l2):
+    """F = sum_t softplus(x_t) - z_t x_t + (l2 / 2)(|U|^2 + |V|^2), x_t = U[u_t] . (V[i_t] - V[j_t]), with torch ops in
+    f64 → a 0-dim f64 tensor on U's device.  Only torch.sum reductions: the value is the same from call to call."""
+    Ud, Vd = U.detach().double(), V.detach().double()
+    u, i, j = (torch.as_tensor(t).reshape(-1).to(device=Ud.device, dtype=torch.int64) for t in (u, i, j))
+    z = torch.as_tensor(z).reshape(-1).to(device=Ud.device, dtype=torch.float64)
+    x = torch.sum(Ud[u] * (Vd[i] - Vd[j]), 1)
+    terms = torch.clamp(x, min=0.0) + torch.log1p(torch.exp(-x.abs())) - z * x
+    return torch.sum(terms) + 0.5 * float(l2) * (torch.sum(Ud * Ud) + torch.sum(Vd * Vd))

@@ -20,6 +20,7 @@ from torch.utils.data import DataLoader, Dataset
 
 from generation_data import *  # noqa: F401,F403  (ref:17 re-exports every sampler/generator name)
 import generation_data as _gd
+from mfcd import alternating as _alternating
 from mfcd import engine as _engine
 from mfcd import foldin as _foldin
 from mfcd import metrics as _metrics
@@ -277,16 +278,20 @@ def train_model_law(model, X, s, optimizer, device, law, num_steps=1000, log_eve
     return out
 
 
-def _grouped_comparisons(data, n, m, device):
-    """The comparisons of `fit_users` / `refit_users` → (records, row_off, n) on `device`: a DataLoader's dataset is read
-    through mfcd.engine.dataset_records and packed as the training path packs it; a (u, i, j, z) tuple is taken as it
-    is.  n = None: max(u) + 1."""
+def _comparisons(data, n, m, device):
+    """The comparisons the exact steps take → (u, i, j, z) on `device`: a DataLoader's dataset is read through
+    mfcd.engine.dataset_records and packed as the training path packs it; a (u, i, j, z) tuple is taken as it is."""
     if isinstance(data, (tuple, list)) and len(data) == 4:
-        u, i, j, z = (torch.as_tensor(t).reshape(-1).to(device) for t in data)
-    else:
-        rows = _engine.dataset_records(data.dataset if hasattr(data, "dataset") else data)
-        rec = torch.from_numpy(_engine.pack_records(rows, n, m)).to(device)
-        u, i, j, z = rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3].contiguous().view(torch.float32)
+        return tuple(torch.as_tensor(t).reshape(-1).to(device) for t in data)
+    rows = _engine.dataset_records(data.dataset if hasattr(data, "dataset") else data)
+    rec = torch.from_numpy(_engine.pack_records(rows, n, m)).to(device)
+    return rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3].contiguous().view(torch.float32)
+
+
+def _grouped_comparisons(data, n, m, device):
+    """The comparisons of `fit_users` / `refit_users` → (records, row_off, n) on `device`, grouped by user.  n = None:
+    max(u) + 1."""
+    u, i, j, z = _comparisons(data, n, m, device)
     if n is None:
         n = int(u.max()) + 1 if u.numel() else 0
     return _foldin.group_by_user(u, i, j, z, n) + (n,)
@@ -327,6 +332,80 @@ def refit_users(model, train_loader, weight_decay):
     l2 = float(weight_decay) * rec.shape[0]
     result = _foldin.fold_in_users(V, rec, off, l2, U.float().contiguous())
     return result, _foldin.row_objective(U, V, rec, off, l2)
+
+
+def _tables(model_or_UV, who):
+    """(U, V) of a model or of a (U, V) pair of tensors."""
+    if hasattr(model_or_UV, "U") and hasattr(model_or_UV, "V"):
+        return model_or_UV.U.data, model_or_UV.V.data
+    if isinstance(model_or_UV, (tuple, list)) and len(model_or_UV) == 2 and all(torch.is_tensor(t) for t in model_or_UV):
+        return tuple(model_or_UV)
+    raise TypeError(f"{who} takes a model or a (U, V) pair of tensors")
+
+
+def fit_items(model_or_UV, data, l2, items=None):
+    """Extension (not in the reference): fold-in for items — with U and the other items held fixed, the exact minimiser
+    of an item's own objective  sum over the comparisons that hold item k of softplus(x) - z x + (l2 / 2) |V[k]|^2,
+    x = U[u] . (V[i] - V[j])  (a sum, not a mean; l2 > 0), by one Newton solve per item on the device (include/mfcd.h
+    mfcd_item_step at theta = 1; d <= 64), started at the item's row.  model_or_UV: a model or a (U, V) pair of fp32
+    tensors on the GPU.  data: a DataLoader from `split_dataset_from_triplets`, or a tuple of (u, i, j, z) tensors.
+    items: the item numbers to solve (a sequence or an integer tensor, each once; None: all m).  Several items named
+    together are solved independently, each against the *given* rows of all the others — not jointly: the rows returned
+    are not a joint minimiser over the named items when comparisons couple them.  An item that was not in training is a
+    zero row appended to V before the call (V must have a row for every item the comparisons name).  Returns
+    mfcd.foldin.ItemStepResult with tensors V [rows, d] (the solved rows, in the order of `items`), objective_start
+    [rows] (the item's objective at its given row), objective [rows], iters [rows], status [rows] (0 converged, 1
+    stopped, 2 invalid data); an item without comparisons gets the zero row.  Not part of the result dict / .pkl
+    layout."""
+    U, V = _tables(model_or_UV, "fit_items")
+    _need_gpu(V.device)
+    m = V.shape[0]
+    u, i, j, z = _comparisons(data, U.shape[0], m, V.device)
+    rec, off = _foldin.group_by_item(u, i, j, z, m)
+    row_item = None
+    if items is not None:
+        items = torch.as_tensor(items).reshape(-1).to(device=V.device, dtype=torch.int64)
+        if items.numel() and (int(items.min()) < 0 or int(items.max()) >= m):
+            raise IndexError(f"an item number lies outside [0, {m})")
+        if torch.unique(items).numel() != items.numel():
+            raise ValueError("fit_items: an item is named twice")
+        lengths = off[items + 1] - off[items]
+        new_off = torch.zeros(items.numel() + 1, dtype=torch.int64, device=V.device)
+        new_off[1:] = torch.cumsum(lengths, 0)
+        total = int(new_off[-1])
+        src = torch.arange(total, device=V.device) + torch.repeat_interleave(off[items] - new_off[:-1], lengths,
+                                                                              output_size=total)
+        rec, off, row_item = rec[src].contiguous(), new_off, items.to(torch.int32)
+    return _foldin.fold_in_items(U.float(), V.float(), rec, off, l2, row_item, 1.0)
+
+
+def refit_items(model, train_loader, weight_decay):
+    """Extension (not in the reference): the exact step of every item on the model's own tables — `fit_items` on the
+    training comparisons with  l2 = weight_decay * N  (the mirror of `refit_users`: the reference's objective times N,
+    restricted to the terms that hold V[k]).  Returns (result, gap): the ItemStepResult and, per item,
+    gap = result.objective_start - result.objective >= 0, what the item's row still had to gain with U and the other
+    items fixed.  Both objectives come from the kernel's f64 sums.  Items move one at a time in this diagnostic: the gaps
+    do not add up to what a joint move would gain.  weight_decay must be > 0.  The model is not changed.  Not part of
+    the result dict / .pkl layout."""
+    _need_gpu(model.V.device)
+    u, i, j, z = _comparisons(train_loader, model.U.shape[0], model.V.shape[0], model.V.device)
+    result = fit_items(model, (u, i, j, z), float(weight_decay) * u.numel())
+    return result, result.objective_start - result.objective
+
+
+def refit_alternating(model, train_loader, weight_decay, sweeps=10, item_steps=2):
+    """Extension (not in the reference): exact-block descent of the regularised empirical objective from the trained
+    tables — mfcd.alternating.fit_alternating on the training comparisons with  l2 = weight_decay * N, so that
+    F = N x (mean BCE + (wd / 2)(|U|^2 + |V|^2)), N times what the reference's optimiser descends.  Each sweep is one
+    exact user step and `item_steps` simultaneous half steps of all items; F falls at every sub-step.  Returns
+    (result, F_at_model): the AlternatingResult (tables, F after every sub-step, statuses of the last sweep) and F at
+    the model's tables; F_at_model - result.history[-1, -1] is how much of F the optimiser had left to these sweeps.
+    weight_decay must be > 0.  The model is not changed.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.V.device)
+    U, V = model.U.data, model.V.data
+    u, i, j, z = _comparisons(train_loader, U.shape[0], V.shape[0], V.device)
+    result = _alternating.fit_alternating(U, V, u, i, j, z, float(weight_decay) * u.numel(), sweeps, item_steps)
+    return result, result.objective_start
 
 
 def compute_ground_truth_metrics(test_loader, X, device):
