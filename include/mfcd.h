@@ -787,7 +787,7 @@ int mfcd_pair_law_grad_rows(const float *A, int64_t lda, const float *X, int64_t
  * 1 <= max_iter <= 1000, xtol finite and >= 0, U_out overlapping neither V nor U_init; MFCD_EINVAL outside them and
  * MFCD_EWORKSPACE for a short workspace, both before anything touches the device.  workspace: as the workspace_bytes
  * entry says (256: the kernel stages nothing in device memory; 0 = sizes out of range).  No allocation and no host wait.
- * Out of scope: d > 64 needs conjugate gradients instead of a Cholesky factor in LDS.
+ * Wider tables (d up to 256): mfcd_fold_in_users_cg below solves the same problem without forming the Hessian.
  */
 int mfcd_fold_in_max_d(void);
 int mfcd_fold_in_chunk(void);
@@ -822,7 +822,8 @@ int mfcd_fold_in_users(const float *V, int m, int d, const mfcd_sample *records,
  * Same kernel as the user step with another staging rule: one workgroup per row, no floating-point atomics, no
  * communication between workgroups; two calls are bit-equal, and a row's outputs do not depend on the other rows of the
  * call or on its position in it (two rows may name one item and then agree bit for bit).
- * Limits: 1 <= d <= 64, n >= 1, m >= 1, rows >= 0 (0 = success, nothing launched), l2 finite and > 0, 0 < theta <= 1,
+ * Limits: 1 <= d <= 64 (wider tables: mfcd_item_step_cg below), n >= 1, m >= 1, rows >= 0 (0 = success, nothing
+ * launched), l2 finite and > 0, 0 < theta <= 1,
  * max_iter and xtol as for users, V_out [rows][d] overlapping neither U nor V; MFCD_EINVAL outside them and
  * MFCD_EWORKSPACE for a workspace below the size for 0 records, both before anything touches the device.  workspace: as
  * the workspace_bytes entry says for the number of records (256 + 8 per record, rounded up to 256; 0 = sizes out of
@@ -834,6 +835,61 @@ int mfcd_item_step(const float *U, int n, const float *V, int m, int d, const mf
                    const int64_t *row_off, const int32_t *row_item, int rows, double l2, double theta, int max_iter,
                    double xtol, float *V_out, double *objective2, int32_t *iters_status, void *workspace,
                    size_t workspace_bytes, void *stream);
+
+/*
+ * The two exact block steps for 1 <= d <= mfcd_fold_in_cg_max_d() = 256 (no reference counterpart): the problems of
+ * mfcd_fold_in_users and mfcd_item_step, solved by damped Newton whose step comes from conjugate gradients on
+ * Hessian-vector products, so that no d x d matrix is formed or factored.  The narrow widths are accepted too, so the
+ * two solvers can be compared where both apply.  The objective f, delta_t, c_t, sigma_t, the start (U_init[r] or 0; V[k]),
+ * the validation rules and status 2 with its NaN row, the rows without records, theta and the two objectives of the
+ * item step, the line search (step 3 above) and the precision rules are those of the two entries above.  Three things
+ * differ (tests/foldin_cg_model.py restates them):
+ *   The step.  H s = -g with H = sum w_t delta_t delta_t^T + l2 I, w_t = p_t (1 - p_t), by preconditioned CG from
+ *     s = 0.  H is applied only as q = sum_t w_t (delta_t . p) delta_t + l2 p.  The preconditioner is Jacobi,
+ *     diag(H)_k = sum_t w_t delta_t[k]^2 + l2.  CG stops when |r|_2 <= eta |g|_2 with eta = 1e-3, or after 4 d + 50
+ *     iterations; the iterate it then holds is a descent direction (every CG iterate from s = 0 is), and the line search
+ *     takes it as it is, with g.s of that iterate in the Armijo rule.
+ *   The order of an iteration.  Every pass forms f, g and the diagonal at the current u; then the stop rule; then, if
+ *     fewer than max_iter solves were made, a CG solve, the line search and u <- u + t s.  iters_status[r][0] counts
+ *     the CG solves, so a start that is already certified reports 0 iterations; cg_iters[r] (nullable) is the total of
+ *     CG iterations of the row — the number that tells why a row was slow.
+ *   The certificate.  The Cholesky form stops on a Newton step below xtol, which certifies a row only because an exact
+ *     Newton step converges quadratically; an inexact step does not.  Here f is l2-strongly convex, so for every u
+ *     |u - u*|_2 <= |g(u)|_2 / l2, and status 0 is given when |g|_2 <= l2 gtol |u|_inf on the gradient of a pass, which
+ *     implies |u - u*|_inf <= gtol |u|_inf.  With the default gtol = 2^-26 and the one fp32 rounding of the output
+ *     (2^-24), U_out is within 2^-22 |u*|_inf of the minimiser.  g = 0 exactly passes.  A row whose minimiser is exactly
+ *     0 is certified only from the start 0 (|u|_inf shrinks with |g|_2), as in the Cholesky form.  Where l2 is so small
+ *     that the rounding floor of g, about 2^-53 sum |p_t - z_t| |delta_t|, lies above l2 gtol |u|_inf, the test cannot
+ *     be met: the row ends with status 1 and its last iterate.
+ *   Status 1 (stopped): max_iter solves made and the gradient of the next pass not certified; 30 halvings without
+ *     decrease; or p.q not positive or not finite inside CG.  u is the last accepted iterate, the objective is f there.
+ * objective (users) is f at the f64 iterate, objective2 (items) = {f_k(v_old), f_k(v*)}, both from a gradient pass.
+ * One workgroup of 256 threads per row, no floating-point atomics, every sum with one owner and a fixed order: two
+ * calls are bit-equal, and a row's outputs depend only on its own records, its start row, the tables and the scalars.
+ * A row of at most mfcd_fold_in_cg_resident(d) comparisons keeps its delta_t (and w_t, x_t) in LDS for the whole solve;
+ * a longer one is gathered again on every pass, mfcd_fold_in_cg_chunk(d) comparisons at a time, and keeps w_t, x_t and
+ * s . delta_t in the workspace.  Which of the two a row takes depends on its length and d alone; both numbers are 0 for
+ * d outside [1, 256].
+ * Limits: 1 <= d <= 256, gtol finite and >= 0 in place of xtol, cg_iters NULL or [rows]; everything else as for the two
+ * entries above, MFCD_EINVAL and MFCD_EWORKSPACE before anything touches the device.  workspace: as the workspace_bytes
+ * entries say for the number of records (256 + 24 per record for users, 256 + 32 per record for items, rounded up to
+ * 256; 0 = sizes out of range); the host cannot see row_off, so it requires the size for 0 records, and a row whose
+ * records end beyond the room the workspace has is status 2 of that row, for users as for items.  No allocation and no
+ * host wait.
+ */
+int mfcd_fold_in_cg_max_d(void);
+int mfcd_fold_in_cg_chunk(int d);
+int mfcd_fold_in_cg_resident(int d);
+size_t mfcd_fold_in_cg_workspace_bytes(int rows, int d, int64_t records);
+int mfcd_fold_in_users_cg(const float *V, int m, int d, const mfcd_sample *records, const int64_t *row_off, int rows,
+                          double l2, const float *U_init, int max_iter, double gtol, float *U_out, double *objective,
+                          int32_t *iters_status, int32_t *cg_iters, void *workspace, size_t workspace_bytes,
+                          void *stream);
+size_t mfcd_item_step_cg_workspace_bytes(int rows, int d, int64_t records);
+int mfcd_item_step_cg(const float *U, int n, const float *V, int m, int d, const mfcd_sample *records,
+                      const int64_t *row_off, const int32_t *row_item, int rows, double l2, double theta, int max_iter,
+                      double gtol, float *V_out, double *objective2, int32_t *iters_status, int32_t *cg_iters,
+                      void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -43,17 +43,14 @@
 // CU.  d <= 16 takes one wave per row (H and the stage are then at most 4.4 KiB each).  More rows than CUs is the
 // normal case; the hardware's workgroup dispatcher balances ragged rows.
 //
-// Out of scope: d > 64 needs conjugate gradients on Hessian-vector products instead of a Cholesky factor in LDS.
-#include <cmath>
-
-#include "common.h"
+// d > 64: foldin_cg.hip solves the same two problems by conjugate gradients on Hessian-vector products instead of a
+// Cholesky factor in LDS; what the two kernels share is in foldin_common.h.
+#include "foldin_common.h"
 
 namespace {
 
 constexpr int kFoldMaxD = 64;
 constexpr int kFoldChunk = 64;        // T: comparisons staged per pass of the inner loop
-constexpr int kFoldHalvings = 30;
-constexpr double kFoldArmijo = 1e-4;
 
 // doubles of LDS a workgroup needs for width d (the int flag rides in the last one)
 inline size_t fold_lds_doubles(int d)
@@ -61,16 +58,6 @@ inline size_t fold_lds_doubles(int d)
     const int dpad = ((d + 3) >> 2) << 2, ld = dpad + 1;
     return (size_t)dpad * ld + (size_t)kFoldChunk * ld + 6 * (size_t)dpad + 3 * (size_t)kFoldChunk + 5 + 1;
 }
-
-// What the item step adds to a launch; the user step passes an empty one and never reads it.
-struct FoldItem {
-    const float *V;            // the item table [m][d]: the start rows and the partner rows of c_t
-    int m;
-    const int32_t *row_item;   // nullable: row r solves item r
-    double theta;
-    double *c;                 // c_t per record, indexed as the records are; written and read by the row's workgroup only
-    int64_t cap;               // records the workspace has room for: a row that ends beyond it is invalid
-};
 
 // ITEM = false: the user step.  V [m][d] is the gathered table, U_init the start rows, objective [rows].
 // ITEM = true: the item step.  V is the gathered table U [m = n][d], U_init is unused, item holds the rest,
@@ -95,61 +82,22 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
 
     const int64_t b = row_off[r], e = row_off[r + 1];
     const int own = ITEM ? (item.row_item ? item.row_item[r] : r) : 0;      // the item this row solves
-    if (!ITEM && e == b) {                             // no comparisons: u = 0 whatever U_init holds
-        for (int k = tid; k < d; k += NT) out[k] = 0.0f;
-        if (tid == 0) {
-            if (objective) objective[r] = 0.0;
-            iters_status[2 * r] = 0;
-            iters_status[2 * r + 1] = 0;
-        }
+    if (!ITEM && e == b) {
+        fold_empty_user_row<NT>(out, d, objective, iters_status, r, tid);
         return;
     }
 
     // ---- validation: indices and labels before any gather, the start vector; V rows are checked as they are staged ----
     if (tid == 0) *flag = 0;
     __syncthreads();
-    if constexpr (!ITEM) {
-        bool bad = e < b || rec == nullptr;
-        if (!bad)
-            for (int64_t t = b + tid; t < e; t += NT) {
-                const mfcd_sample q = rec[t];
-                if ((unsigned)q.i >= (unsigned)m || (unsigned)q.j >= (unsigned)m || !(q.z >= 0.0f && q.z <= 1.0f)) bad = true;
-            }
-        if (U_init)
-            for (int k = tid; k < d; k += NT)
-                if (is_nonfinite_bits(U_init[(int64_t)r * d + k])) bad = true;
-        if (bad) *flag = 1;
+    if constexpr (ITEM) {
+        if (fold_item_row_is_bad<NT>(m, d, rec, b, e, own, item, tid)) *flag = 1;
     } else {
-        // the row's own item first, then every index of its records (m is the user count here), that each record holds
-        // the item, the labels, and that the row's c_t fit into the workspace
-        bool bad = (unsigned)own >= (unsigned)item.m || e < b || b < 0 || e > item.cap || (e > b && rec == nullptr);
-        if (!bad) {
-            for (int64_t t = b + tid; t < e; t += NT) {
-                const mfcd_sample q = rec[t];
-                if ((unsigned)q.u >= (unsigned)m || (unsigned)q.i >= (unsigned)item.m || (unsigned)q.j >= (unsigned)item.m ||
-                    (q.i != own && q.j != own) || !(q.z >= 0.0f && q.z <= 1.0f))
-                    bad = true;
-            }
-            for (int k = tid; k < d; k += NT)
-                if (is_nonfinite_bits(item.V[(int64_t)own * d + k])) bad = true;
-        }
-        if (bad) *flag = 1;
+        if (fold_user_row_is_bad<NT>(m, d, rec, b, e, U_init ? U_init + (int64_t)r * d : nullptr, tid)) *flag = 1;
     }
     __syncthreads();
 
-    auto invalid_row = [&]() {
-        const float qnan = __uint_as_float(0x7fc00000u);
-        for (int k = tid; k < d; k += NT) out[k] = qnan;
-        if (tid == 0) {
-            if constexpr (ITEM) {
-                if (objective) objective[2 * r] = objective[2 * r + 1] = (double)qnan;
-            } else {
-                if (objective) objective[r] = (double)qnan;
-            }
-            iters_status[2 * r] = 0;
-            iters_status[2 * r + 1] = 2;
-        }
-    };
+    auto invalid_row = [&]() { fold_invalid_row<NT, ITEM>(out, d, objective, iters_status, r, tid); };
     if (*flag) {
         invalid_row();
         return;
@@ -157,35 +105,11 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
 
     if constexpr (ITEM) {
         const float *vold = item.V + (int64_t)own * d;
-        if (e == b) {                                  // no comparisons: v* = 0, the row moves theta of the way to it
-            for (int k = tid; k < d; k += NT) out[k] = (float)fma(item.theta, -(double)vold[k], (double)vold[k]);
-            if (tid == 0) {
-                double vv = 0.0;
-                for (int k = 0; k < d; ++k) vv = fma((double)vold[k], (double)vold[k], vv);
-                if (objective) {
-                    objective[2 * r] = 0.5 * l2 * vv;
-                    objective[2 * r + 1] = 0.0;
-                }
-                iters_status[2 * r] = 0;
-                iters_status[2 * r + 1] = 0;
-            }
+        if (e == b) {
+            fold_empty_item_row<NT>(out, d, vold, item.theta, l2, objective, iters_status, r, tid);
             return;
         }
-        // ---- prologue: c_t = -sigma_t U[u_t] . V[o_t], one thread per comparison, k ascending; both rows are checked ----
-        bool bad = false;
-        for (int64_t t = b + tid; t < e; t += NT) {
-            const mfcd_sample q = rec[t];
-            const int sigma = (q.i == own) - (q.j == own);
-            const float *ur = V + (int64_t)q.u * d, *vr = item.V + (int64_t)(q.i == own ? q.j : q.i) * d;
-            double acc = 0.0;
-            for (int k = 0; k < d; ++k) {
-                const float a = ur[k], c = vr[k];
-                if (is_nonfinite_bits(a) || is_nonfinite_bits(c)) bad = true;
-                acc = fma((double)a, (double)c, acc);
-            }
-            item.c[t] = sigma == 0 ? 0.0 : -(double)sigma * acc;
-        }
-        if (bad) *flag = 1;
+        if (fold_form_offsets<NT>(V, d, rec, b, e, own, item, tid)) *flag = 1;
         __syncthreads();                               // c_t is visible to the workgroup that wrote it
         if (*flag) {
             invalid_row();
@@ -219,18 +143,9 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
             __syncthreads();                           // the previous chunk's readers are done; uv is visible
             if (sk < dpad)
                 for (int t = st0; t < cn; t += ststep) {
-                    double v = 0.0;
-                    if constexpr (ITEM) {              // delta = sigma U[u] (exact); c_t rides in the pad column
-                        const mfcd_sample q = rec[c0 + t];
-                        if (sk < d) v = (double)((q.i == own) - (q.j == own)) * (double)V[(int64_t)q.u * d + sk];
+                    D[t * ld + sk] = sk < d ? fold_delta<ITEM>(V, d, rec[c0 + t], own, sk, flag) : 0.0;
+                    if constexpr (ITEM)                // c_t rides in the pad column
                         if (sk == 0) D[t * ld + dpad] = item.c[c0 + t];
-                    } else if (sk < d) {
-                        const mfcd_sample q = rec[c0 + t];
-                        const float vi = V[(int64_t)q.i * d + sk], vj = V[(int64_t)q.j * d + sk];
-                        if (is_nonfinite_bits(vi) || is_nonfinite_bits(vj)) *flag = 1;
-                        v = (double)vi - (double)vj;
-                    }
-                    D[t * ld + sk] = v;
                 }
             __syncthreads();
             if (tid < cn) {
@@ -239,11 +154,11 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
                 if constexpr (ITEM) x = row[dpad];
                 for (int k = 0; k < d; ++k) x = fma(uv[k], row[k], x);
                 const double z = (double)rec[c0 + tid].z;
-                const double ex = exp(-fabs(x)), q = 1.0 / (1.0 + ex);
-                facc += (fmax(x, 0.0) + log1p(ex)) - z * x;
+                const FoldLogit at(x);
+                facc += at.term(z);
                 if (hess) {
-                    w[tid] = ex * q * q;                       // p (1 - p)
-                    res[tid] = (x >= 0.0 ? q : ex * q) - z;    // p - z
+                    w[tid] = at.weight();
+                    res[tid] = at.p() - z;
                 } else {
                     double x0 = 0.0, sx = 0.0;
                     if constexpr (ITEM) x0 = row[dpad];
@@ -251,13 +166,7 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
                         x0 = fma(u[k], row[k], x0);
                         sx = fma(s[k], row[k], sx);
                     }
-                    const double h = tt * sx, e0 = exp(-fabs(x0)), q0 = 1.0 / (1.0 + e0);
-                    if (fabs(h) < 1.0) {
-                        dacc += log1p((x0 >= 0.0 ? q0 : e0 * q0) * expm1(h)) - z * h;
-                    } else {                                   // a long step: the two softplus values differ visibly
-                        const double x1 = x0 + h;
-                        dacc += ((fmax(x1, 0.0) + log1p(exp(-fabs(x1)))) - (fmax(x0, 0.0) + log1p(e0))) - z * h;
-                    }
+                    dacc += fold_decrease_term(FoldLogit(x0), tt * sx, z);
                 }
             }
             if (hess) {
@@ -375,16 +284,11 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
         // ---- backtracking: t = 1, 1/2, ... until the Armijo decrease holds ----
         double t = 1.0, fnew = 0.0;
         bool accepted = false;
-        for (int h = 0; h <= kFoldHalvings; ++h) {
+        for (int h = 0; h <= kFoldHalvings && !accepted; ++h) {
             if (tid < dpad) ut[tid] = fma(t, s[tid], u[tid]);
             fnew = pass(ut, false, t);
-            // either evaluation of the rule accepts: the term-wise decrease resolves steps that f cannot show, the values
-            // of f settle a step so small that the term-wise sum is itself at its rounding level (u + t s == u at last)
-            if (scal[4] <= kFoldArmijo * t * gs || fnew <= fcur + kFoldArmijo * t * gs) {
-                accepted = true;
-                break;
-            }
-            t *= 0.5;
+            accepted = fold_armijo_accepts(scal[4], fnew, fcur, t, gs);
+            if (!accepted) t *= 0.5;
         }
         if (!accepted) break;                          // status 1: u is the last accepted iterate
         if (tid < dpad) u[tid] = ut[tid];
@@ -404,24 +308,7 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
     }
 
     __syncthreads();
-    if constexpr (ITEM) {                              // v_old + theta (v* - v_old) in f64, rounded once
-        const float *vold = item.V + (int64_t)own * d;
-        for (int k = tid; k < d; k += NT) out[k] = (float)fma(item.theta, u[k] - (double)vold[k], (double)vold[k]);
-    } else {
-        for (int k = tid; k < d; k += NT) out[k] = (float)u[k];
-    }
-    if (tid == 0) {
-        if constexpr (ITEM) {
-            if (objective) {
-                objective[2 * r] = fstart;
-                objective[2 * r + 1] = fcur;
-            }
-        } else {
-            if (objective) objective[r] = fcur;
-        }
-        iters_status[2 * r] = it;
-        iters_status[2 * r + 1] = status;
-    }
+    fold_finish<NT, ITEM>(out, u, d, item, own, objective, iters_status, r, fstart, fcur, it, status, tid);
 }
 
 template <int NT, bool ITEM>
@@ -439,12 +326,6 @@ int fold_launch(const float *V, int m, int d, const mfcd_sample *rec, const int6
     hipLaunchKernelGGL((fold_in_kernel<NT, ITEM>), dim3((unsigned)rows), dim3(NT), lds, st, V, m, d, rec, row_off, l2,
                        U_init, max_iter, xtol, U_out, objective, iters_status, item);
     return (int)hipGetLastError();
-}
-
-inline bool fold_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
 }
 
 }  // namespace

@@ -1,24 +1,47 @@
-"""The exact block steps of the BTL fit on the device (include/mfcd.h: mfcd_fold_in_users, mfcd_item_step).  With the item
-table V held fixed, every user's row is the minimiser of its own l2-regularised logistic regression on
-delta_t = V[i_t] - V[j_t]; with U and the other items held fixed, an item's row is the minimiser of a logistic regression
-with an offset over the comparisons that hold it.  Both are found by the same damped Newton iteration, one workgroup
-per row.
+"""The exact block steps of the BTL fit on the device (include/mfcd.h: mfcd_fold_in_users, mfcd_item_step and their
+_cg forms).  With the item table V held fixed, every user's row is the minimiser of its own l2-regularised logistic
+regression on delta_t = V[i_t] - V[j_t]; with U and the other items held fixed, an item's row is the minimiser of a
+logistic regression with an offset over the comparisons that hold it.  Both are found by a damped Newton iteration, one
+workgroup per row, in one of two forms (`method`): "cholesky" factors the d x d Hessian in LDS (d <= 64), "cg" takes the
+step from conjugate gradients on Hessian-vector products (d <= 256); "auto" is cholesky wherever it applies.
 
 `group_by_user` / `group_by_item` sort comparisons (stable) into the records and row offsets the kernel reads;
-`fold_in_users` / `fold_in_items` are the kernel calls; `row_objective` and `total_objective` form the objectives with
-torch ops in f64 (diagnostics, not second solvers).  There is no CPU form of the solves."""
+`fold_in_users` / `fold_in_items` / `fold_in_items_cg` are the kernel calls; `row_objective` and `total_objective` form
+the objectives with torch ops in f64 (diagnostics, not second solvers).  There is no CPU form of the solves."""
 import collections
 
 import torch
 
 from . import _lib
 
-FoldInResult = collections.namedtuple("FoldInResult", ("U", "objective", "iters", "status"))
-FoldInResult.__doc__ = """What `fold_in_users` returns, all on V's device: U fp32 [rows, d]; objective f64 [rows], the sum
-over the row's comparisons of softplus(x) - z x plus (l2 / 2) |u|^2 at the solution; iters int32 [rows]; status int32
-[rows]: 0 converged, 1 stopped (iteration cap or a line search without decrease), 2 invalid data (the row is NaN)."""
+class FoldInResult(collections.namedtuple("FoldInResult", ("U", "objective", "iters", "status"))):
+    """What `fold_in_users` returns, all on V's device: U fp32 [rows, d]; objective f64 [rows], the sum over the row's
+    comparisons of softplus(x) - z x plus (l2 / 2) |u|^2 at the solution; iters int32 [rows] (Newton iterations; CG
+    solves for the CG form); status int32 [rows]: 0 converged, 1 stopped (iteration cap or a line search without
+    decrease), 2 invalid data (the row is NaN).  The attribute `cg_iters` (not a field of the tuple) is int32 [rows],
+    the CG iterations of each row, for the CG form and None for the Cholesky form."""
+    cg_iters = None
 
 CONVERGED, STOPPED, INVALID = 0, 1, 2
+METHODS = ("auto", "cholesky", "cg")
+
+
+def _use_cg(L, d, method, what):
+    """Which solver a call of width d takes: False the Cholesky form, True the CG form; MfcdError beyond both."""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, not {method!r}")
+    top = L.mfcd_fold_in_cg_max_d() if method != "cholesky" else L.mfcd_fold_in_max_d()
+    if not 1 <= d <= top:
+        raise _lib.MfcdError(f"d = {d} is outside {what}'s range [1, {top}]"
+                             + (" (method=\"cholesky\")" if method == "cholesky" else ""))
+    return method == "cg" or (method == "auto" and d > L.mfcd_fold_in_max_d())
+
+
+def _with_cg_iters(result, cg_iters):
+    """`cg_iters` rides on the result as an attribute (not a field of the tuple): int32 [rows], the CG iterations of
+    each row in all; None for the Cholesky form."""
+    result.cg_iters = cg_iters
+    return result
 
 
 def group_by_user(u, i, j, z, n):
@@ -42,12 +65,15 @@ def group_by_user(u, i, j, z, n):
     return rec, row_off
 
 
-def fold_in_users(V, records, row_off, l2, U_init=None, max_iter=50, xtol=2.0 ** -30):
+def fold_in_users(V, records, row_off, l2, U_init=None, max_iter=50, xtol=2.0 ** -30, gtol=2.0 ** -26, method="auto"):
     """V fp32 [m, d] on a GPU, `records` / `row_off` as `group_by_user` returns them (rows = len(row_off) - 1), l2 > 0 →
     FoldInResult: per row the minimiser of sum_t softplus(u . delta_t) - z_t u . delta_t + (l2 / 2) |u|^2 by the Newton
-    iteration include/mfcd.h fixes, started at U_init (fp32 [rows, d]; None: at 0).  Rows with invalid data get status 2
-    and NaN; nothing is read outside the tables.  Deterministic, and a row's result does not depend on the other rows.
-    Nothing waits for the device."""
+    iteration include/mfcd.h fixes, started at U_init (fp32 [rows, d]; None: at 0).  method: "cholesky" (d <= 64; stops
+    on a step below xtol |u|_inf), "cg" (d <= 256; stops on |g|_2 <= l2 gtol |u|_inf), "auto": cholesky for d <= 64 and
+    cg above.  Rows with invalid data get status 2 and NaN; nothing is read outside the tables.  Deterministic, and a
+    row's result does not depend on the other rows.  Nothing waits for the device."""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, not {method!r}")
     if not torch.is_tensor(V) or not V.is_cuda or V.dtype != torch.float32 or V.dim() != 2:
         raise _lib.MfcdError("fold_in_users needs V as a float32 [m, d] tensor on a GPU device (there is no CPU fallback)")
     if not torch.is_tensor(records) or not records.is_cuda or records.dtype != torch.int32 or records.dim() != 2 \
@@ -68,12 +94,18 @@ def fold_in_users(V, records, row_off, l2, U_init=None, max_iter=50, xtol=2.0 **
     U = torch.empty((rows, d), dtype=torch.float32, device=dev)
     objective = torch.empty(rows, dtype=torch.float64, device=dev)
     info = torch.empty((rows, 2), dtype=torch.int32, device=dev)
-    need = L.mfcd_fold_in_workspace_bytes(rows, d)
-    if need == 0:
-        raise _lib.MfcdError(f"d = {d} is outside the fold-in kernel's range [1, {L.mfcd_fold_in_max_d()}]")
-    ws = _lib.workspace(need, dev)
-    _lib.check(L.mfcd_fold_in_users(V.data_ptr(), m, d, records.data_ptr() if records.numel() else None,
-                                    row_off.data_ptr(), rows, float(l2), _lib.ptr(U_init), int(max_iter), float(xtol),
+    rec_ptr = records.data_ptr() if records.numel() else None
+    if _use_cg(L, d, method, "the fold-in kernel"):
+        cg_iters = torch.empty(rows, dtype=torch.int32, device=dev)
+        ws = _lib.workspace(L.mfcd_fold_in_cg_workspace_bytes(rows, d, records.shape[0]), dev)
+        _lib.check(L.mfcd_fold_in_users_cg(V.data_ptr(), m, d, rec_ptr, row_off.data_ptr(), rows, float(l2),
+                                           _lib.ptr(U_init), int(max_iter), float(gtol), U.data_ptr(),
+                                           objective.data_ptr(), info.data_ptr(), cg_iters.data_ptr(), _lib.ptr(ws),
+                                           ws.numel(), _lib.stream_ptr(dev)))
+        return _with_cg_iters(FoldInResult(U, objective, info[:, 0], info[:, 1]), cg_iters)
+    ws = _lib.workspace(L.mfcd_fold_in_workspace_bytes(rows, d), dev)
+    _lib.check(L.mfcd_fold_in_users(V.data_ptr(), m, d, rec_ptr, row_off.data_ptr(), rows, float(l2), _lib.ptr(U_init),
+                                    int(max_iter), float(xtol),
                                     U.data_ptr(), objective.data_ptr(), info.data_ptr(), _lib.ptr(ws), ws.numel(),
                                     _lib.stream_ptr(dev)))
     return FoldInResult(U, objective, info[:, 0], info[:, 1])
@@ -93,10 +125,11 @@ def row_objective(U, V, records, row_off, l2):
     return f + 0.5 * float(l2) * (Ud * Ud).sum(1)
 
 
-ItemStepResult = collections.namedtuple("ItemStepResult", ("V", "objective_start", "objective", "iters", "status"))
-ItemStepResult.__doc__ = """What `fold_in_items` returns, all on V's device: V fp32 [rows, d], the rows
-v_old + theta (v* - v_old); objective_start / objective f64 [rows], the item's objective f_k at v_old and at v*; iters
-int32 [rows]; status int32 [rows] as in FoldInResult."""
+class ItemStepResult(collections.namedtuple("ItemStepResult", ("V", "objective_start", "objective", "iters", "status"))):
+    """What `fold_in_items` returns, all on V's device: V fp32 [rows, d], the rows v_old + theta (v* - v_old);
+    objective_start / objective f64 [rows], the item's objective f_k at v_old and at v*; iters int32 [rows]; status int32
+    [rows] as in FoldInResult, and the attribute `cg_iters` likewise."""
+    cg_iters = None
 
 
 def group_by_item(u, i, j, z, m):
@@ -130,9 +163,21 @@ def fold_in_items(U, V, records, row_off, l2, row_item=None, theta=1.0, max_iter
     the other rows of V fixed, v* minimises sum_t softplus(x_t) - z_t x_t + (l2 / 2) |v|^2 over the row's records,
     x_t = +-U[u_t] . (v - V[other item]), by the Newton iteration include/mfcd.h fixes, started at V[k]; the row returned
     is V[k] + theta (v* - V[k]).  theta = 1: the exact minimiser of each row on its own; theta = 1/2: all items may move
-    in one call and the total objective still falls.  Rows with invalid data get status 2 and NaN; nothing is read
-    outside the tables.  Deterministic, and a row's result does not depend on the other rows.  Nothing waits for the
-    device."""
+    in one call and the total objective still falls.  The solver is chosen by d as `fold_in_users` does with
+    method="auto": the Cholesky form with `xtol` for d <= 64, the CG form with its default gtol above, up to 256
+    (`fold_in_items_cg` is the CG form for any d <= 256, with gtol as a parameter).  Rows with invalid data get status 2
+    and NaN; nothing is read outside the tables.  Deterministic, and a row's result does not depend on the other rows.
+    Nothing waits for the device."""
+    return _fold_in_items(U, V, records, row_off, l2, row_item, theta, max_iter, xtol, 2.0 ** -26, "auto")
+
+
+def fold_in_items_cg(U, V, records, row_off, l2, row_item=None, theta=1.0, max_iter=50, gtol=2.0 ** -26):
+    """`fold_in_items` by the CG form (include/mfcd.h: mfcd_item_step_cg) for any 1 <= d <= 256: a row is certified when
+    |g|_2 <= l2 gtol |v|_inf.  The result's attribute `cg_iters` holds the CG iterations of each row."""
+    return _fold_in_items(U, V, records, row_off, l2, row_item, theta, max_iter, 2.0 ** -30, gtol, "cg")
+
+
+def _fold_in_items(U, V, records, row_off, l2, row_item, theta, max_iter, xtol, gtol, method):
     if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 for t in (U, V)) \
             or U.shape[1] != V.shape[1]:
         raise _lib.MfcdError("fold_in_items needs U [n, d] and V [m, d] as float32 tensors on a GPU device (there is no "
@@ -155,12 +200,18 @@ def fold_in_items(U, V, records, row_off, l2, row_item=None, theta=1.0, max_iter
     out = torch.empty((rows, d), dtype=torch.float32, device=dev)
     objective = torch.empty((rows, 2), dtype=torch.float64, device=dev)
     info = torch.empty((rows, 2), dtype=torch.int32, device=dev)
-    need = L.mfcd_item_step_workspace_bytes(rows, d, records.shape[0])
-    if need == 0:
-        raise _lib.MfcdError(f"d = {d} is outside the item step's range [1, {L.mfcd_fold_in_max_d()}]")
-    ws = _lib.workspace(need, dev)
-    _lib.check(L.mfcd_item_step(U.data_ptr(), n, V.data_ptr(), m, d, records.data_ptr() if records.numel() else None,
-                                row_off.data_ptr(), _lib.ptr(row_item), rows, float(l2), float(theta), int(max_iter),
+    rec_ptr = records.data_ptr() if records.numel() else None
+    if _use_cg(L, d, method, "the item step"):
+        cg_iters = torch.empty(rows, dtype=torch.int32, device=dev)
+        ws = _lib.workspace(L.mfcd_item_step_cg_workspace_bytes(rows, d, records.shape[0]), dev)
+        _lib.check(L.mfcd_item_step_cg(U.data_ptr(), n, V.data_ptr(), m, d, rec_ptr, row_off.data_ptr(),
+                                       _lib.ptr(row_item), rows, float(l2), float(theta), int(max_iter), float(gtol),
+                                       out.data_ptr(), objective.data_ptr(), info.data_ptr(), cg_iters.data_ptr(),
+                                       _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        return _with_cg_iters(ItemStepResult(out, objective[:, 0], objective[:, 1], info[:, 0], info[:, 1]), cg_iters)
+    ws = _lib.workspace(L.mfcd_item_step_workspace_bytes(rows, d, records.shape[0]), dev)
+    _lib.check(L.mfcd_item_step(U.data_ptr(), n, V.data_ptr(), m, d, rec_ptr, row_off.data_ptr(), _lib.ptr(row_item),
+                                rows, float(l2), float(theta), int(max_iter),
                                 float(xtol), out.data_ptr(), objective.data_ptr(), info.data_ptr(), _lib.ptr(ws),
                                 ws.numel(), _lib.stream_ptr(dev)))
     return ItemStepResult(out, objective[:, 0], objective[:, 1], info[:, 0], info[:, 1])

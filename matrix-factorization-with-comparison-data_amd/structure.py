@@ -300,7 +300,7 @@ def _grouped_comparisons(data, n, m, device):
 def fit_users(V_or_model, data, l2, U_init=None):
     """Extension (not in the reference): fold-in — with the item table held fixed, the exact minimiser of every user's
     own objective  sum over the user's comparisons of softplus(x) - z x + (l2 / 2) |u|^2,  x = u . (V[i] - V[j])  (a sum,
-    not a mean; l2 > 0), by one Newton solve per user on the device (include/mfcd.h mfcd_fold_in_users; d <= 64).
+    not a mean; l2 > 0), by one Newton solve per user on the device (include/mfcd.h mfcd_fold_in_users; d <= 256).
     V_or_model: a model (its V and its number of users) or a bare fp32 V [m, d] on the GPU (n = max(u) + 1).  data: a
     DataLoader from `split_dataset_from_triplets`, or a tuple of (u, i, j, z) tensors; the users need not have been in
     training.  U_init: fp32 [n, d] start rows (None: 0).  Returns mfcd.foldin.FoldInResult with tensors U [n, d],
@@ -347,7 +347,7 @@ def fit_items(model_or_UV, data, l2, items=None):
     """Extension (not in the reference): fold-in for items — with U and the other items held fixed, the exact minimiser
     of an item's own objective  sum over the comparisons that hold item k of softplus(x) - z x + (l2 / 2) |V[k]|^2,
     x = U[u] . (V[i] - V[j])  (a sum, not a mean; l2 > 0), by one Newton solve per item on the device (include/mfcd.h
-    mfcd_item_step at theta = 1; d <= 64), started at the item's row.  model_or_UV: a model or a (U, V) pair of fp32
+    mfcd_item_step at theta = 1; d <= 256), started at the item's row.  model_or_UV: a model or a (U, V) pair of fp32
     tensors on the GPU.  data: a DataLoader from `split_dataset_from_triplets`, or a tuple of (u, i, j, z) tensors.
     items: the item numbers to solve (a sequence or an integer tensor, each once; None: all m).  Several items named
     together are solved independently, each against the *given* rows of all the others — not jointly: the rows returned

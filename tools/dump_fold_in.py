@@ -1,6 +1,6 @@
-"""Diagnostic: write every output of the user step (mfcd/foldin.py: fold_in_users) as .npy files, for the inputs of
-tests/test_fold_in.py at d = 2 and d = 64 (all three label kinds, both starts, both l2), so that two builds of the
-library can be compared byte for byte: run it once per build with another --out (MFCD_LIB selects the library, as for
+"""Diagnostic: write every output of the user step and of the item step (mfcd/foldin.py: fold_in_users, fold_in_items at
+theta = 1/2) as .npy files, for the inputs of tests/test_fold_in.py and tests/test_item_step.py at d = 2, 16 and 64 (all
+three label kinds, both starts, both l2), so that two builds of the library can be compared byte for byte: run it once per build with another --out (MFCD_LIB selects the library, as for
 every tool), then `python tools/dump_fold_in.py --compare DIR_A DIR_B`.
 
 Usage: dump_fold_in.py --out DIR | --compare DIR_A DIR_B
@@ -13,6 +13,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "matrix-factorization-with-comparison-d
 import numpy as np  # noqa: E402
 
 NAMES = ("U", "objective", "iters", "status")
+ITEM_NAMES = ("V", "objective_start", "objective", "iters", "status")
 
 
 def compare(a, b):
@@ -30,13 +31,14 @@ def main():
     out = args[args.index("--out") + 1]
     import torch
     import foldin_model as FM
+    import itemstep_model as IM
     from mfcd import _lib, foldin
     dev = torch.device("cuda:0")
     T = _lib.load().mfcd_fold_in_chunk()
     os.makedirs(out, exist_ok=True)
     to = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
     count = 0
-    for d in (2, 64):
+    for d in (2, 16, 64):
         for labels in FM.LABELS:
             for start in (False, True):
                 seed = 1000 * d + 10 * FM.LABELS.index(labels) + int(start)      # tests/test_fold_in.py: case()
@@ -45,6 +47,14 @@ def main():
                     res = foldin.fold_in_users(to(V), to(rec), to(off), l2, to(U0))
                     for name, t in zip(NAMES, res):
                         np.save(os.path.join(out, f"d{d}_{labels}_{'init' if start else 'zero'}_l2_{l2:g}_{name}.npy"),
+                                t.cpu().numpy())
+                        count += 1
+                seed = 5000 + 1000 * d + 10 * IM.LABELS.index(labels) + int(start)      # tests/test_item_step.py: case()
+                U, Vi, rec, off, items = IM.make_case(d, labels, FM.row_lengths(T), seed, start)
+                for l2 in (1e-3, 1.0):
+                    res = foldin.fold_in_items(to(U), to(Vi), to(rec), to(off), l2, to(items), 0.5)
+                    for name, t in zip(ITEM_NAMES, res):
+                        np.save(os.path.join(out, f"item_d{d}_{labels}_{'init' if start else 'zero'}_l2_{l2:g}_{name}.npy"),
                                 t.cpu().numpy())
                         count += 1
     print(f"{count} files written to {out} with {_lib.LIB_PATH}")
