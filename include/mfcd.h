@@ -751,6 +751,37 @@ int mfcd_pair_law_grad_rows(const float *A, int64_t lda, const float *X, int64_t
                             const mfcd_pair_law *law, float *G, int64_t ldg, void *stream);
 
 /*
+ * The Hessian of the `risk` sums above with respect to the scores, applied to a vector (no reference counterpart: the
+ * curvature of the population risk, for second-order steps on it).  The risk sum of a row is a function of the score
+ * differences alone, so its Hessian is the weighted graph Laplacian L(a): row r of Q [rows][ldq] receives, for every
+ * column i < m,
+ *     q_i = sum over j != i of  w_ij s_ij (y_i - y_j),     s_ij = sigmoid'(a_i - a_j) = p (1 - p),  p = sigmoid(a_i - a_j),
+ * with y row r of Y and w_ij = 1 for the plain entry, the weight of mfcd_pair_law for the law entry.  deg is optional
+ * (NULL: not computed, and the kernel compiled without it runs): row r of deg [rows][ldd] receives the diagonal of L,
+ *     deg_i = sum over j != i of  w_ij s_ij,
+ * with the column j = i excluded by a mask (its s is 1/4 whatever its weight).  Neither the labels' law nor `scale`
+ * enters a second derivative; X is read by the law entry only, for the margin factor and for the finiteness rule.
+ * Columns >= m of Q and deg are not written.
+ * Kernel: the decomposition of mfcd_pair_grad_rows — one 256-thread workgroup per (row, tile of 1024 columns) against
+ * EVERY tile of the row, four elements per thread in registers, each thread owning and storing its sums; no workspace,
+ * no finishing kernel, no atomic.  Per ordered pair s = e h h with e = exp(-|a_i - a_j|), h = 1 / (1 + e): one hardware
+ * exp and one reciprocal, symmetric in the sign, nothing selected and nothing cancelled; the term is s (y_i - y_j) with
+ * the difference formed first, so a constant row of Y gives a row of Q of exactly +0, and a column whose every weight is
+ * 0 gives exactly +0 in Q and deg.  An accumulator adds at most 64 terms in fp32 before it is widened to f64; q_i and
+ * deg_i are rounded to fp32 once, on the store.  A row with a non-finite entry in A or Y (or X, for the law entry) gets
+ * an all-NaN row of Q and of deg.  Two calls are bit-equal, Q does not depend on whether deg is asked for, and a row's
+ * result does not depend on the other rows of the call or on the leading dimensions.  The law's flags compile to
+ * kernels of their own as for the two law entries above: an absent factor costs nothing.
+ * Limits: rows >= 0 (0 = success, nothing launched), 1 <= m <= 1 048 576, lda, ldy, ldq (ldx; ldd with deg) >= m, Q and
+ * deg none of the inputs nor each other, and the law rules of mfcd_pair_law_grad_rows; MFCD_EINVAL outside them, before
+ * anything touches the device.  Long inputs go through in blocks of rows.  No allocation and no host wait.
+ */
+int mfcd_pair_hvp_rows(const float *A, int64_t lda, const float *Y, int64_t ldy, int rows, int m, float *Q, int64_t ldq,
+                       float *deg, int64_t ldd, void *stream);
+int mfcd_pair_law_hvp_rows(const float *A, int64_t lda, const float *X, int64_t ldx, const float *Y, int64_t ldy, int rows,
+                           int m, const mfcd_pair_law *law, float *Q, int64_t ldq, float *deg, int64_t ldd, void *stream);
+
+/*
  * The exact user step of the BTL fit, "fold-in" (no reference counterpart: the reference only ever moves U and V
  * together, structure.py:845-852): with the item table V [m][d] held fixed, row r of U_out is the minimiser of
  *     f(u) = sum over t of  softplus(x_t) - z_t x_t  +  (l2 / 2) |u|^2,     x_t = u . delta_t,  delta_t = V[i_t] - V[j_t],

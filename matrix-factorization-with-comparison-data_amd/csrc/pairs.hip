@@ -618,6 +618,126 @@ __global__ __launch_bounds__(kPairThreads) void pair_law_grad_kernel(const float
     }
 }
 
+// ---- the Hessian of a row's risk sum times a vector (third follow-on) ----
+// q_i = sum over j != i of w_ij s_ij (y_i - y_j),  s_ij = sigmoid'(a_i - a_j),  and optionally deg_i = sum over j != i of
+// w_ij s_ij: the weighted graph Laplacian L(a) applied to y, and its diagonal.  The decomposition is pair_grad_kernel's
+// (every tile J visited, a thread owns its four sums and stores them itself); one template serves the plain entry
+// (LAW = false: no x, w = 1) and the law entry, whose flags are pair_law_grad_kernel's.
+//   s = e h h with e = exp(-|v|), h = 1 / (1 + e): symmetric in the sign of v, so nothing is selected and nothing
+//   cancels; one exp and one reciprocal per ordered pair.  The term is s (y_i - y_j), the difference formed first.
+// The column j == i adds exactly 0 to q (its difference is +0) but s = 1/4 to deg: with DEG the element that can meet its
+// own column in a run of the diagonal tile (element c in run c, at column tid of the run) has s zeroed there.
+template <bool DEG, int KMASK, bool HW, bool HM, bool HL>
+__device__ __forceinline__ void hvp_run(const float2 *tile, const float *tx, const float2 *tab, const int *lab, int j0,
+                                        int j1, const float (&ai)[kPairIpt], const float (&yi)[kPairIpt],
+                                        const float (&xi)[kPairIpt], const float (&ali)[kPairIpt],
+                                        const float (&bei)[kPairIpt], const int (&li)[kPairIpt], int tid, float mg,
+                                        double (&acc)[kPairIpt], double (&dacc)[kPairIpt])
+{
+    for (int jb = j0; jb < j1; jb += kGradFlush) {
+        const int je = jb + kGradFlush < j1 ? jb + kGradFlush : j1;
+        float f[kPairIpt] = {0.0f, 0.0f, 0.0f, 0.0f}, g[kPairIpt] = {0.0f, 0.0f, 0.0f, 0.0f};   // <= 64 terms each
+#pragma unroll 4
+        for (int j = jb; j < je; ++j) {
+            const float2 v = tile[j];
+            const float xj = HM ? tx[j] : 0.0f;
+            float alj = 0.0f, bej = 0.0f;
+            if constexpr (HW) {
+                alj = tab[j].x;
+                bej = tab[j].y;
+            }
+            const int lj = HL ? lab[j] : 0;
+#pragma unroll
+            for (int k = 0; k < kPairIpt; ++k) {
+                const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * fabsf(ai[k] - v.x));   // exp(-|da|) <= 1
+                const float h = __builtin_amdgcn_rcpf(1.0f + e);
+                float s = e * h * h;
+                if (HW || HM || HL)
+                    s = __fmul_rn(law_weight<HW, HM, HL>(HM ? xi[k] - xj : 0.0f, ali[k], bei[k], li[k], alj, bej, lj, mg), s);
+                if (DEG && k == KMASK) s = j - j0 == tid ? 0.0f : s;
+                f[k] = fmaf(s, yi[k] - v.y, f[k]);
+                if (DEG) g[k] += s;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kPairIpt; ++k) {
+            acc[k] += (double)f[k];
+            if (DEG) dacc[k] += (double)g[k];
+        }
+    }
+}
+
+template <bool LAW, bool HW, bool HM, bool HL, bool DEG>
+__global__ __launch_bounds__(kPairThreads) void pair_hvp_kernel(const float *__restrict__ A, int64_t lda,
+                                                                const float *__restrict__ X, int64_t ldx,
+                                                                const float *__restrict__ Y, int64_t ldy, LawArgs law, int m,
+                                                                int T, float *__restrict__ Q, int64_t ldq,
+                                                                float *__restrict__ Dg, int64_t ldd)
+{
+    __shared__ float2 tile[kPairTile];                 // (a, y)
+    __shared__ float tx[HM ? kPairTile : 1];
+    __shared__ float2 tab[HW ? kPairTile : 1];         // (alpha, beta)
+    __shared__ int lab[HL ? kPairTile : 1];
+    const int tid = threadIdx.x;
+    const int64_t r = blockIdx.x / T;
+    const int I = (int)(blockIdx.x - r * T);
+    const float *a = A + r * lda, *y = Y + r * ldy, *x = LAW ? X + r * ldx : nullptr;
+    const int32_t *lb = HL ? law.labels + r * law.label_stride : nullptr;
+
+    float ai[kPairIpt], yi[kPairIpt], xi[kPairIpt], ali[kPairIpt], bei[kPairIpt];
+    int li[kPairIpt];
+#pragma unroll
+    for (int k = 0; k < kPairIpt; ++k) {
+        const int p = I * kPairTile + k * kPairThreads + tid;
+        const bool in = p < m;                         // an element past m is computed and never stored
+        ai[k] = in ? a[p] : 0.0f;
+        yi[k] = in ? y[p] : 0.0f;
+        xi[k] = HM && in ? x[p] : 0.0f;
+        ali[k] = HW && in ? law.alpha[p] : 0.0f;
+        bei[k] = HW && in ? law.beta[p] : 0.0f;
+        li[k] = HL && in ? lb[p] : 0;
+    }
+
+    int bad = 0;                                       // the workgroup stages the whole row: it sees every entry
+    double acc[kPairIpt] = {0.0, 0.0, 0.0, 0.0}, dacc[kPairIpt] = {0.0, 0.0, 0.0, 0.0};
+    for (int J = 0; J < T; ++J) {
+        __syncthreads();                               // the previous tile's readers are done
+#pragma unroll
+        for (int k = 0; k < kPairIpt; ++k) {
+            const int e = k * kPairThreads + tid, p = J * kPairTile + e;
+            const bool in = p < m;
+            const float va = in ? a[p] : 0.0f, vy = in ? y[p] : 0.0f, vx = LAW && in ? x[p] : 0.0f;
+            bad |= (int)(is_nonfinite_bits(va) || is_nonfinite_bits(vy) || is_nonfinite_bits(vx));
+            tile[e] = make_float2(va, vy);
+            if (HM) tx[e] = vx;
+            if (HW) tab[e] = make_float2(in ? law.alpha[p] : 0.0f, in ? law.beta[p] : 0.0f);
+            if (HL) lab[e] = in ? lb[p] : 0;
+        }
+        __syncthreads();
+        const int jn = m - J * kPairTile < kPairTile ? m - J * kPairTile : kPairTile;   // pad columns stay out
+        if (DEG && J == I) {                           // run c holds element c's own column
+            const auto end = [jn](int j1) { return j1 < jn ? j1 : jn; };
+            hvp_run<DEG, 0, HW, HM, HL>(tile, tx, tab, lab, 0, end(256), ai, yi, xi, ali, bei, li, tid, law.margin, acc, dacc);
+            hvp_run<DEG, 1, HW, HM, HL>(tile, tx, tab, lab, 256, end(512), ai, yi, xi, ali, bei, li, tid, law.margin, acc, dacc);
+            hvp_run<DEG, 2, HW, HM, HL>(tile, tx, tab, lab, 512, end(768), ai, yi, xi, ali, bei, li, tid, law.margin, acc, dacc);
+            hvp_run<DEG, 3, HW, HM, HL>(tile, tx, tab, lab, 768, end(1024), ai, yi, xi, ali, bei, li, tid, law.margin, acc, dacc);
+        } else {
+            hvp_run<DEG, -1, HW, HM, HL>(tile, tx, tab, lab, 0, jn, ai, yi, xi, ali, bei, li, tid, law.margin, acc, dacc);
+        }
+    }
+
+    bad = __syncthreads_or(bad);
+    float *q = Q + r * ldq, *dg = DEG ? Dg + r * ldd : nullptr;
+#pragma unroll
+    for (int k = 0; k < kPairIpt; ++k) {
+        const int p = I * kPairTile + k * kPairThreads + tid;
+        if (p < m) {                                   // rounded to fp32 once
+            q[p] = bad ? __uint_as_float(0x7fc00000u) : (float)acc[k];
+            if (DEG) dg[p] = bad ? __uint_as_float(0x7fc00000u) : (float)dacc[k];
+        }
+    }
+}
+
 // The largest fp32 <= margin (margin >= 0, not NaN).
 inline float floor32(double margin)
 {
@@ -673,6 +793,39 @@ template <bool HW, bool HM, bool HL> struct LawGradLaunch {
                            A, lda, X, ldx, law, m, T, scale, G, ldg);
     }
 };
+
+template <bool LAW, bool HW, bool HM, bool HL>
+void hvp_launch(const float *A, int64_t lda, const float *X, int64_t ldx, const float *Y, int64_t ldy, LawArgs law, int nr,
+                int m, int T, float *Q, int64_t ldq, float *deg, int64_t ldd, hipStream_t st)
+{
+    const dim3 grid((unsigned)((int64_t)nr * T)), block(kPairThreads);
+    if (deg)
+        hipLaunchKernelGGL((pair_hvp_kernel<LAW, HW, HM, HL, true>), grid, block, 0, st, A, lda, X, ldx, Y, ldy, law, m, T, Q,
+                           ldq, deg, ldd);
+    else
+        hipLaunchKernelGGL((pair_hvp_kernel<LAW, HW, HM, HL, false>), grid, block, 0, st, A, lda, X, ldx, Y, ldy, law, m, T, Q,
+                           ldq, deg, ldd);
+}
+
+template <bool HW, bool HM, bool HL> struct LawHvpLaunch {
+    static void go(const float *A, int64_t lda, const float *X, int64_t ldx, const float *Y, int64_t ldy, LawArgs law, int nr,
+                   int m, int T, float *Q, int64_t ldq, float *deg, int64_t ldd, hipStream_t st)
+    {
+        hvp_launch<true, HW, HM, HL>(A, lda, X, ldx, Y, ldy, law, nr, m, T, Q, ldq, deg, ldd, st);
+    }
+};
+
+// The shared argument check of the two Hessian-vector entries → 0, or MFCD_EINVAL (X = nullptr: the plain entry).
+inline int hvp_args(const float *A, int64_t lda, const float *X, int64_t ldx, const float *Y, int64_t ldy, int rows, int m,
+                    const float *Q, int64_t ldq, const float *deg, int64_t ldd)
+{
+    if (!A || !Y || !Q || rows < 0 || m < 1 || m > kPairMaxCols || lda < m || ldy < m || ldq < m) return MFCD_EINVAL;
+    if (X && ldx < m) return MFCD_EINVAL;
+    if (deg && ldd < m) return MFCD_EINVAL;
+    if (Q == A || Q == Y || Q == X || Q == deg) return MFCD_EINVAL;
+    if (deg && (deg == A || deg == Y || deg == X)) return MFCD_EINVAL;
+    return 0;
+}
 
 }  // namespace
 
@@ -782,6 +935,44 @@ extern "C" int mfcd_pair_law_grad_rows(const float *A, int64_t lda, const float 
         law_dispatch<LawGradLaunch>(la.alpha != nullptr, law->use_margin != 0, la.labels != nullptr,
                                     A + (int64_t)r0 * lda, lda, X + (int64_t)r0 * ldx, ldx, lr, nr, m, T, (float)scale,
                                     G + (int64_t)r0 * ldg, ldg, (hipStream_t)stream);
+        MFCD_HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int mfcd_pair_hvp_rows(const float *A, int64_t lda, const float *Y, int64_t ldy, int rows, int m, float *Q,
+                                  int64_t ldq, float *deg, int64_t ldd, void *stream)
+{
+    if (hvp_args(A, lda, nullptr, 0, Y, ldy, rows, m, Q, ldq, deg, ldd)) return MFCD_EINVAL;
+    if (rows == 0) return 0;
+    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
+    for (int r0 = 0; r0 < rows; r0 += R) {
+        const int nr = rows - r0 < R ? rows - r0 : R;
+        hvp_launch<false, false, false, false>(A + (int64_t)r0 * lda, lda, nullptr, 0, Y + (int64_t)r0 * ldy, ldy, LawArgs{}, nr,
+                                               m, T, Q + (int64_t)r0 * ldq, ldq, deg ? deg + (int64_t)r0 * ldd : nullptr, ldd,
+                                               (hipStream_t)stream);
+        MFCD_HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int mfcd_pair_law_hvp_rows(const float *A, int64_t lda, const float *X, int64_t ldx, const float *Y, int64_t ldy,
+                                      int rows, int m, const mfcd_pair_law *law, float *Q, int64_t ldq, float *deg,
+                                      int64_t ldd, void *stream)
+{
+    if (!X || hvp_args(A, lda, X, ldx, Y, ldy, rows, m, Q, ldq, deg, ldd)) return MFCD_EINVAL;
+    LawArgs la;
+    if (law_args(law, m, &la)) return MFCD_EINVAL;
+    if (rows == 0) return 0;
+    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
+    for (int r0 = 0; r0 < rows; r0 += R) {
+        const int nr = rows - r0 < R ? rows - r0 : R;
+        LawArgs lr = la;
+        if (lr.labels) lr.labels += (int64_t)r0 * lr.label_stride;
+        law_dispatch<LawHvpLaunch>(la.alpha != nullptr, law->use_margin != 0, la.labels != nullptr, A + (int64_t)r0 * lda, lda,
+                                   X + (int64_t)r0 * ldx, ldx, Y + (int64_t)r0 * ldy, ldy, lr, nr, m, T,
+                                   Q + (int64_t)r0 * ldq, ldq, deg ? deg + (int64_t)r0 * ldd : nullptr, ldd,
+                                   (hipStream_t)stream);
         MFCD_HIP_TRY(hipGetLastError());
     }
     return 0;

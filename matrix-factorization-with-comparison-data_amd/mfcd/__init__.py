@@ -9,7 +9,8 @@
 `foldin`   the exact block steps: one Newton solve per user with V fixed (mfcd_fold_in_users), one per item with U and
            the other items fixed (mfcd_item_step).
 `alternating` the two block steps alternated: monotone exact-block descent of the regularised BTL objective.
+`population` the exact block steps of the ridge-regularised population risk: Newton-CG on mfcd_pair_hvp_rows.
 """
-from . import _lib, alternating, batching, engine, foldin, metrics, pairs, topk  # noqa: F401
+from . import _lib, alternating, batching, engine, foldin, metrics, pairs, population, topk  # noqa: F401
 
-__all__ = ["_lib", "alternating", "batching", "engine", "foldin", "metrics", "pairs", "topk"]
+__all__ = ["_lib", "alternating", "batching", "engine", "foldin", "metrics", "pairs", "population", "topk"]

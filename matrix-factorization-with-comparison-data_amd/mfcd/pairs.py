@@ -14,6 +14,10 @@ All of it also exists under a pair law (`PairLaw`; `strategy_law` builds the one
 from): `pair_law_stats_rows` / `pair_law_grad_rows` are the weighted kernel calls, and `law_risk`, `law_metrics` and
 `fit_law` are `population_risk`, `pairwise_metrics` and `fit_population` under it.  The law's risk is normalised
 globally, by the weight of all users.
+
+Second order: `pair_hvp_rows` / `pair_law_hvp_rows` (mfcd_pair_hvp_rows, mfcd_pair_law_hvp_rows) apply the Hessian of a
+row's risk sum, a weighted graph Laplacian, to a vector, and `population_hvp` carries it to the factor tables: the
+Hessian-vector product of `population_risk` / `law_risk`.  mfcd/population.py builds the exact block steps on it.
 """
 import copy
 import ctypes
@@ -221,6 +225,46 @@ def pair_law_grad_rows(A, X, law, scale=1.0):
     _lib.check(L.mfcd_pair_law_grad_rows(A.data_ptr(), lda, X.data_ptr(), ldx, rows, m, float(scale), ctypes.byref(c),
                                          G.data_ptr(), m, _lib.stream_ptr(A.device)))
     return G
+
+
+def _range_check(m):
+    if not 1 <= m <= 1 << 20:
+        raise _lib.MfcdError(f"rows of {m} columns are outside the pair kernel's range [1, 1048576]")
+
+
+def pair_hvp_rows(A, Y, deg=False):
+    """Two [rows, m] fp32 GPU matrices (rows may be strided views): scores A, directions Y → Q fp32 [rows, m] on the
+    device, q_i = sum over j != i of s_ij (y_i - y_j) with s_ij = sigmoid'(a_i - a_j): the Hessian of the `risk` sum of
+    `pair_stats_rows` with respect to the scores (a graph Laplacian; it depends on neither X nor the scale), applied to
+    the row of Y.  deg=True → (Q, deg), deg_i = sum over j != i of s_ij, the Hessian's diagonal.  A constant row of Y
+    gives exactly +0; a row with a non-finite entry is all NaN.  Deterministic, and Q does not depend on `deg`."""
+    A, Y, rows, m, lda, ldy = _lib.row_pair(A, Y, "pair_hvp_rows")
+    L = _lib.load()
+    Q = torch.empty((rows, m), dtype=torch.float32, device=A.device)
+    D = torch.empty((rows, m), dtype=torch.float32, device=A.device) if deg else None
+    if rows:
+        _range_check(m)
+        _lib.check(L.mfcd_pair_hvp_rows(A.data_ptr(), lda, Y.data_ptr(), ldy, rows, m, Q.data_ptr(), m, _lib.ptr(D), m,
+                                        _lib.stream_ptr(A.device)))
+    return (Q, D) if deg else Q
+
+
+def pair_law_hvp_rows(A, X, Y, law, deg=False):
+    """`pair_hvp_rows` under a `PairLaw`, for rows already restricted to the law's columns (mfcd_pair_law_hvp_rows):
+    q_i = sum over j != i of w_ij s_ij (y_i - y_j), deg_i = sum over j != i of w_ij s_ij, the Hessian of the `risk` sum
+    of `pair_law_stats_rows` and its diagonal.  X enters through the law's margin only.  Exactly +0 where no pair of i
+    has weight; a row with a non-finite entry in A, X or Y is all NaN.  Deterministic."""
+    A, X, rows, m, lda, ldx = _lib.row_pair(A, X, "pair_law_hvp_rows")
+    A, Y, _, _, lda, ldy = _lib.row_pair(A, Y, "pair_law_hvp_rows")
+    L = _lib.load()
+    c = law._c(rows, m)
+    Q = torch.empty((rows, m), dtype=torch.float32, device=A.device)
+    D = torch.empty((rows, m), dtype=torch.float32, device=A.device) if deg else None
+    if rows:
+        _range_check(m)
+        _lib.check(L.mfcd_pair_law_hvp_rows(A.data_ptr(), lda, X.data_ptr(), ldx, Y.data_ptr(), ldy, rows, m,
+                                            ctypes.byref(c), Q.data_ptr(), m, _lib.ptr(D), m, _lib.stream_ptr(A.device)))
+    return (Q, D) if deg else Q
 
 
 def strategy_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha=1.5, k=None, n_clusters=10, seed=0):
@@ -458,6 +502,74 @@ def law_risk(U, V, X, law, s=1.0, users=None, row_block=2048):
     if src.k == 0:
         raise ValueError("the population risk needs at least one user")
     return _LawRisk.apply(U, V, src, float(s), law)
+
+
+def law_weight_total(src, law, s=1.0):
+    """Sum over the users of a RowBlocks of W, the law's pair weight → 0-dim f64 device tensor.  W depends on X alone
+    (truth rows stand in for the scores).  A user with a non-finite truth row stays out, as in `law_metrics`: its W is
+    NaN, and `law_risk` — which sums plainly — is NaN as a whole for such an input, so the Hessian product and the exact
+    steps that use this total have no finite risk to agree with there; they normalise by the users that have one."""
+    total = torch.zeros((), dtype=torch.float64, device=src.dev)
+    for r0, r1 in src.blocks():
+        lb = law.for_rows(src.ids[r0:r1]) if law.per_user() else law
+        truth = lb.take(src.truth(r0, r1))
+        total += torch.nansum(pair_law_stats_rows(truth, truth, lb, s)[1][:, 0])
+    return total
+
+
+def population_hvp(U, V, X, dU, dV, s=1.0, law=None, users=None, row_block=2048, gauss_newton=False):
+    """The Hessian of `population_risk` (law=None or a trivial law) or of `law_risk` at the fp32 tables (U, V), applied
+    to the direction (dU [n, d], dV [m, d]) → (HU [n, d], HV [m, d]) fp32 on the device.  With A = U V^T,
+    Y = dU V^T + U dV^T, L the row Laplacians of `pair_hvp_rows`, G the score gradients of `pair_grad_rows` and c the
+    risk's normaliser (1 / (users x pairs), or 1 / sum of W under a law),
+        HU = c (L Y V + G dV),     HV = c ((L Y)^T U + G^T dU).
+    gauss_newton=True drops the two G terms (and the gradient kernel): the product is then positive semidefinite.
+    Block by block as `population_risk`: per block the scores, Y by two GEMMs, the kernel(s) and the GEMMs back.  users:
+    None = every user (the law's users under a law); rows of HU of users not named are 0, a user named twice counts
+    twice.  Under a law a user with a non-finite truth row stays out of c (`law_weight_total`; `law_risk` itself is NaN
+    then) and its own rows of the product are NaN.  Nothing waits for the device inside the block loop; a `users` list
+    is range-checked on the host once, before it."""
+    if not all(torch.is_tensor(t) and t.is_cuda for t in (U, V, dU, dV)):
+        raise _lib.MfcdError("the population Hessian needs the tables and the direction on a GPU (there is no CPU fallback)")
+    if any(t.dtype != torch.float32 for t in (U, V, dU, dV)):
+        raise _lib.MfcdError("the population Hessian takes float32 factor tables and directions")
+    if dU.shape != U.shape or dV.shape != V.shape:
+        raise ValueError(f"the direction must have the tables' shapes {tuple(U.shape)}, {tuple(V.shape)}")
+    U, V, dU, dV = (t.detach() for t in (U, V, dU, dV))
+    plain = law is None or law.trivial
+    if plain:
+        src = RowBlocks(U, V, X, users, row_block, "the population Hessian")
+        if src.m < 2:
+            raise ValueError("the population risk needs at least two items (m >= 2)")
+    else:
+        src = _law_src(U, V, X, users, row_block, law, "the population Hessian")
+    if src.k == 0:
+        raise ValueError("the population risk needs at least one user")
+    coef = 1.0 / (src.k * (src.m * (src.m - 1) // 2)) if plain else (1.0 / law_weight_total(src, law, s)).float()
+    HU_rows = torch.empty((src.k, U.shape[1]), dtype=torch.float32, device=src.dev)
+    HV = torch.zeros_like(src.V)
+    dVt = dV.t()
+    for r0, r1 in src.blocks():
+        Ub, dUb = src.rows_of(src.U, r0, r1), src.rows_of(dU, r0, r1)
+        Y = torch.addmm(dUb @ src.Vt, Ub, dVt)
+        if plain:
+            scores, truth = Ub @ src.Vt, (None if gauss_newton else src.truth(r0, r1))
+            Q = pair_hvp_rows(scores, Y)
+            G = None if gauss_newton else pair_grad_rows(scores, truth, s)
+        else:
+            lb, scores, truth = _law_block(src, law, r0, r1)
+            Q = lb.put_back(pair_law_hvp_rows(scores, truth, lb.take(Y), lb), src.m)
+            G = None if gauss_newton else lb.put_back(pair_law_grad_rows(scores, truth, lb, s), src.m)
+        torch.mm(Q, src.V, out=HU_rows[r0:r1])
+        HV.addmm_(Q.t(), Ub)
+        if G is not None:
+            HU_rows[r0:r1].addmm_(G, dV)
+            HV.addmm_(G.t(), dUb)
+    HU_rows *= coef
+    HV *= coef
+    if src.whole:
+        return HU_rows, HV
+    return torch.zeros_like(src.U).index_put_((src.ids,), HU_rows, accumulate=True), HV
 
 
 def fit_population(binding, X, s, steps, log_every=0, row_block=2048):

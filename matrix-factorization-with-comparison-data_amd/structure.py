@@ -25,6 +25,7 @@ from mfcd import engine as _engine
 from mfcd import foldin as _foldin
 from mfcd import metrics as _metrics
 from mfcd import pairs as _pairs
+from mfcd import population as _population
 from mfcd import sampling as _sampling
 from mfcd import topk as _topk
 
@@ -276,6 +277,52 @@ def train_model_law(model, X, s, optimizer, device, law, num_steps=1000, log_eve
         out = (at, torch.stack(seen).double().cpu().tolist() if seen else [])
     model.eval()
     return out
+
+
+def population_hvp(model, X, dU, dV, s=1.0, law=None, users=None, row_block=2048, gauss_newton=False):
+    """Extension (not in the reference): the Hessian of `population_risk(model, X, s)` (or of `law_risk` under a
+    `sampling_law`) with respect to the factor tables, applied to the direction (dU [n, d], dV [m, d]) → (HU, HV) fp32 on
+    the model's device: the curvature that second-order steps on the population objective use (include/mfcd.h
+    mfcd_pair_hvp_rows, the Laplacian of every user's pair risk, and library GEMMs per block of `row_block` users).
+    gauss_newton=True drops the terms that hold the risk's gradient: the product is then positive semidefinite.  fp32
+    models only.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _pairs.population_hvp(model.U.data, model.V.data, X, dU, dV, s, law, users, row_block, gauss_newton)
+
+
+def refit_users_population(model, X, s, weight_decay, law=None, users=None):
+    """Extension (not in the reference): `refit_users` with unlimited comparisons — for the model's own V, the best
+    response of every user's row on  F = population_risk (or law_risk) + (wd / 2)(|U|^2 + |V|^2),  the objective whose
+    stationary points `train_model_population` / `train_model_law` approach under Adam's coupled weight decay, by
+    mfcd.population.population_user_step started at `model.U`.  Returns (result, gain): the PopulationStepResult (rows,
+    status 0 certified / 1 stopped / 2 invalid, newton_iters, cg_iters, objective_before, objective_after, grad_ratio)
+    and, per user, gain = objective_before - objective_after >= 0: what the trained row still had to gain in F with V
+    fixed.  weight_decay must be > 0.  The model is not changed.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    result = _population.population_user_step(model.U.data, model.V.data, X, s, float(weight_decay), law, users)
+    return result, result.objective_before - result.objective_after
+
+
+def refit_items_population(model, X, s, weight_decay, law=None):
+    """Extension (not in the reference): the mirror of `refit_users_population` — for the model's own U, the minimiser
+    over all of V of F (one problem: pairs couple the items), by mfcd.population.population_item_step started at
+    `model.V`.  Returns (result, gain) with result.rows the best-response V [m, d] and gain the 0-dim decrease of F.
+    weight_decay must be > 0.  The model is not changed.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.V.device)
+    result = _population.population_item_step(model.U.data, model.V.data, X, s, float(weight_decay), law)
+    return result, result.objective_before - result.objective_after
+
+
+def train_model_population_exact(model, X, s, weight_decay, sweeps=10, law=None):
+    """Extension (not in the reference): `train_model_population` by exact block steps instead of Adam — `sweeps` sweeps of
+    one exact user step and one exact item step of  F = population_risk (or law_risk) + (wd / 2)(|U|^2 + |V|^2)
+    (mfcd.population.fit_population_exact), each a Newton-CG solve on the pair Hessian, in place on the model's tables.
+    Returns F after every sub-step as a list of [after the user step, after the item step] per sweep; it does not
+    increase.  fp32 models only; weight_decay must be > 0.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    result = _population.fit_population_exact(model.U.data, model.V.data, X, s, float(weight_decay), sweeps, law)
+    model.eval()
+    return result.history.cpu().tolist()
 
 
 def _comparisons(data, n, m, device):
