@@ -782,6 +782,43 @@ int mfcd_pair_law_hvp_rows(const float *A, int64_t lda, const float *X, int64_t 
                            int m, const mfcd_pair_law *law, float *Q, int64_t ldq, float *deg, int64_t ldd, void *stream);
 
 /*
+ * The same Laplacian applied to every column of an item table in one pass (no reference counterpart): the multi-column
+ * form of mfcd_pair_law_hvp_rows, from which the d x d matrix a row's Laplacian induces on the item vectors,
+ * H_r = B_r^T L(a_r) B_r, is one batched GEMM away (mfcd/pairs.py: pair_info_rows).  For row r of A [rows][lda] (and of X,
+ * read for the law's margin and the finiteness rule only; NULL is allowed when the law has no margin) and every column
+ * i < k of the row, row (r, i) of Z [rows][k][ldz] receives the d numbers
+ *     z_i = sum over j != i of  w_ij s_ij (b_i - b_j),     s_ij = sigmoid'(a_i - a_j),
+ * b_j = row index[r][j] of B [mB][ldb] (fp32, d columns), w the weight of the mfcd_pair_law struct; law = NULL is the
+ * plain risk, w = 1.  index: int32; index_stride = 0, one vector [k] for all rows; index_stride >= k, row r reads index + r *
+ * index_stride; NULL: column j is row j of B, and k must equal mB.  deg is optional: row r of deg [rows][ldd] receives
+ * deg_i = sum over j != i of w_ij s_ij.  The column j = i contributes to neither.
+ * Kernel (csrc/pair_info.hip): one 256-thread workgroup per (row, tile of 128 columns i, chunk of at most 128 columns of
+ * d); the columns j stream through LDS in stages of 64; every lane generates one weight per v_mfma_f32_32x32x2_f32 step
+ * (one exp, one reciprocal, as mfcd_pair_hvp_rows) and every further 32 columns of d reuse it: z_i = deg_i b~_i - sum
+ * over j of c_ij b~_j on the fp32 matrix pipe.  b~ is B gathered and centred: a pre-pass forms the column mean of the
+ * row's gathered table in f64 (one per row under a per-row index, one for all otherwise), and b~ = b - mean is formed
+ * in f64 and rounded to fp32 once; z does not depend on the centre in exact arithmetic (L 1 = 0), and without it the
+ * Laplacian form would cancel at the size of B's offset.  The fp32 accumulators are widened to f64 after every stage
+ * (at most 64 terms; 32 for deg), z_i is formed from the f64 sums and rounded to fp32 once.
+ * The pre-pass checks every index against mB before anything is gathered: a row that names an index outside [0, mB) is
+ * all NaN (Z and deg), as is a row with a non-finite entry in A, in X (when given), or in a row of B it uses.  A column
+ * without a weighted pair gets exactly +0.  No floating-point atomics, every sum has one owner and a fixed order: two
+ * calls are bit-equal, a row's result does not depend on the other rows, on the leading dimensions or on deg being
+ * asked for.
+ * Limits: rows >= 0 (0 = success, nothing launched), 1 <= k <= 1 048 576, 1 <= d <= 256, mB >= 1, lda (ldx with X, ldd
+ * with deg) >= k, ldb, ldz >= d, index_stride 0 or >= k, Z and deg none of the inputs nor each other, the law rules of
+ * mfcd_pair_law_grad_rows for a law that is not NULL, and X not NULL under a law with a margin; MFCD_EINVAL outside them
+ * and MFCD_EWORKSPACE for a short workspace, before anything touches the device.  workspace: as the workspace_bytes
+ * entry says (2080 bytes per row of a block of at most 4096 rows; 0 = sizes out of range), 256-byte aligned.  Long inputs
+ * go through in blocks of rows.  No allocation and no host wait.
+ */
+size_t mfcd_pair_hvp_multi_workspace_bytes(int rows, int k, int d);
+int mfcd_pair_hvp_multi_rows(const float *A, int64_t lda, const float *X, int64_t ldx, const float *B, int64_t ldb, int mB,
+                             int d, const int32_t *index, int64_t index_stride, int rows, int k, const mfcd_pair_law *law,
+                             float *Z, int64_t ldz, float *deg, int64_t ldd, void *workspace, size_t workspace_bytes,
+                             void *stream);
+
+/*
  * The exact user step of the BTL fit, "fold-in" (no reference counterpart: the reference only ever moves U and V
  * together, structure.py:845-852): with the item table V [m][d] held fixed, row r of U_out is the minimiser of
  *     f(u) = sum over t of  softplus(x_t) - z_t x_t  +  (l2 / 2) |u|^2,     x_t = u . delta_t,  delta_t = V[i_t] - V[j_t],

@@ -99,6 +99,9 @@ SIGNATURES = {
     "mfcd_pair_law_grad_rows": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _dbl, _vp, _vp, _i64, _vp]),
     "mfcd_pair_hvp_rows": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),
     "mfcd_pair_law_hvp_rows": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "mfcd_pair_hvp_multi_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "mfcd_pair_hvp_multi_rows": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp,
+                                        _i64, _vp, _sz, _vp]),
     "mfcd_fold_in_max_d": (_i32, []),
     "mfcd_fold_in_chunk": (_i32, []),
     "mfcd_fold_in_workspace_bytes": (_sz, [_i32, _i32]),

@@ -18,7 +18,13 @@ globally, by the weight of all users.
 Second order: `pair_hvp_rows` / `pair_law_hvp_rows` (mfcd_pair_hvp_rows, mfcd_pair_law_hvp_rows) apply the Hessian of a
 row's risk sum, a weighted graph Laplacian, to a vector, and `population_hvp` carries it to the factor tables: the
 Hessian-vector product of `population_risk` / `law_risk`.  mfcd/population.py builds the exact block steps on it.
+
+`pair_hvp_multi_rows` (mfcd_pair_hvp_multi_rows) applies the same Laplacian to all d columns of an item table in one
+pass, `pair_info_rows` contracts the result to the d x d matrix H_r = B_r^T L(a_r) B_r the Laplacian induces on a user's
+row, and `user_information` forms it for the users of a model: the Hessian of a user's risk sum in u (at="model") or the
+Fisher information of the law's comparisons about the row (at="truth").
 """
+import collections
 import copy
 import ctypes
 
@@ -29,6 +35,9 @@ from . import _lib
 from .rows import RowBlocks
 
 TILE = 1024          # columns per workgroup tile of the kernel (csrc/pairs.hip: kPairTile)
+INFO_TILE = 128     # columns per workgroup tile of the multi-column kernel (csrc/pair_info.hip: kInfoTile)
+INFO_MAX_D = 256    # its widest item table (kInfoMaxD)
+_INFO_Z_BYTES = 256 << 20    # `pair_info_rows` takes rows in chunks whose Z stays under this
 _WHAT = {"counts": 1, "sums": 2, "both": 3}
 
 
@@ -265,6 +274,133 @@ def pair_law_hvp_rows(A, X, Y, law, deg=False):
         _lib.check(L.mfcd_pair_law_hvp_rows(A.data_ptr(), lda, X.data_ptr(), ldx, Y.data_ptr(), ldy, rows, m,
                                             ctypes.byref(c), Q.data_ptr(), m, _lib.ptr(D), m, _lib.stream_ptr(A.device)))
     return (Q, D) if deg else Q
+
+
+def pair_hvp_multi_rows(A, B, X=None, law=None, index=None, deg=False):
+    """`pair_law_hvp_rows` for every column of an item table at once (mfcd_pair_hvp_multi_rows): scores A [rows, k] and
+    an item table B [mB, d] (fp32, on the GPU, d <= 256) → Z fp32 [rows, k, d],
+        z_i = sum over j != i of w_ij s_ij (b_i - b_j),   s_ij = sigmoid'(a_i - a_j),
+    with b_j = B[index[j]] (index: int [k] shared by all rows, or [rows, k]; None: column j is row j of B and k = mB) and
+    w the weight of `law` on rows already restricted to its columns (None: the plain risk, w = 1).  X [rows, k] enters
+    through the law's margin and the finiteness rule only; it may be None unless the law has a margin.  deg=True →
+    (Z, deg), deg_i = sum over j != i of w_ij s_ij, fp32 [rows, k].  The kernel centres the gathered table (f64 column
+    mean) before it forms the Laplacian's difference.  Exactly +0 where no pair of i has weight; a row with a non-finite
+    entry in A, X or a row of B it uses, or with an index outside [0, mB), is all NaN.  Deterministic, a row does not
+    depend on its neighbours, and Z does not depend on `deg`."""
+    who = "pair_hvp_multi_rows"
+    if X is None:
+        A, _, rows, k, lda, _ = _lib.row_pair(A, A, who)
+        ldx = 0
+    else:
+        A, X, rows, k, lda, ldx = _lib.row_pair(A, X, who)
+    if not torch.is_tensor(B) or B.dim() != 2 or B.dtype != torch.float32 or not B.is_cuda:
+        raise _lib.MfcdError(f"{who} needs the item table as a float32 GPU matrix (no CPU fallback)")
+    if B.stride(1) != 1:
+        B = B.contiguous()
+    mB, d = B.shape
+    ldb = B.stride(0) if mB > 1 else d
+    stride = 0
+    if index is not None:
+        index = torch.as_tensor(index)
+        if index.dtype.is_floating_point or index.dim() not in (1, 2) or index.shape[-1] != k \
+                or (index.dim() == 2 and index.shape[0] != rows):
+            raise ValueError(f"index must be integers [{k}] or [{rows}, {k}], got {tuple(index.shape)}")
+        stride = k if index.dim() == 2 else 0
+        index = index.to(device=A.device, dtype=torch.int32).contiguous()
+    elif k != mB:
+        raise ValueError(f"without an index the rows need one column per row of B: {k} columns, {mB} rows")
+    c = None if law is None else law._c(rows, k)
+    if law is not None and law.margin is not None and X is None:
+        raise ValueError("a law with a margin needs X")
+    L = _lib.load()
+    Z = torch.empty((rows, k, d), dtype=torch.float32, device=A.device)
+    D = torch.empty((rows, k), dtype=torch.float32, device=A.device) if deg else None
+    if rows:
+        _range_check(k)
+        if not 1 <= d <= INFO_MAX_D:
+            raise _lib.MfcdError(f"an item table of {d} columns is outside the kernel's range [1, {INFO_MAX_D}]")
+        ws = _lib.workspace(L.mfcd_pair_hvp_multi_workspace_bytes(rows, k, d), A.device)
+        _lib.check(L.mfcd_pair_hvp_multi_rows(A.data_ptr(), lda, None if X is None else X.data_ptr(), ldx, B.data_ptr(), ldb,
+                                              mB, d, _lib.ptr(index), stride, rows, k,
+                                              None if c is None else ctypes.byref(c), Z.data_ptr(), d, _lib.ptr(D), k,
+                                              _lib.ptr(ws), ws.numel(), _lib.stream_ptr(A.device)))
+    return (Z, D) if deg else Z
+
+
+def pair_info_rows(A, B, X=None, law=None, index=None):
+    """The d x d matrix a row's Laplacian induces on the item vectors, H_r = B~_r^T L(a_r) B~_r = sum over i < j of
+    w_ij s_ij (b_i - b_j)(b_i - b_j)^T → f64 [rows, d, d] on the device; the arguments are `pair_hvp_multi_rows`'.
+    H_r = B~_r^T Z_r with B~ the gathered table minus its f64 column mean, contracted in f64 by a batched library GEMM,
+    rows taken in chunks so that a chunk's Z stays under 256 MiB; symmetrised, so H[p][q] and H[q][p] are bit-equal.  A
+    NaN row of Z gives a NaN matrix."""
+    if not torch.is_tensor(A) or A.dim() != 2 or not torch.is_tensor(B) or B.dim() != 2 or not A.is_cuda or not B.is_cuda:
+        raise _lib.MfcdError("pair_info_rows needs float32 GPU matrices (no CPU fallback)")
+    rows, k = A.shape
+    mB, d = B.shape
+    idx = None if index is None else torch.as_tensor(index).to(device=A.device, dtype=torch.int64)
+    per_row = idx is not None and idx.dim() == 2
+    B64 = B.double()
+    if not per_row:
+        G = B64 if idx is None else B64[idx.clamp(0, mB - 1)]      # a bad index makes every row NaN in the kernel
+        shared = (G - G.mean(0, keepdim=True)).t().contiguous()    # [d, k]
+    H = torch.empty((rows, d, d), dtype=torch.float64, device=A.device)
+    per = max(1, _INFO_Z_BYTES // max(1, k * d * 4))
+    for r0 in range(0, rows, per):
+        r1 = min(rows, r0 + per)
+        lb = law
+        if law is not None and law.per_user():
+            lb = law.for_rows(torch.arange(r0, r1, device=A.device))
+        Z = pair_hvp_multi_rows(A[r0:r1], B, None if X is None else X[r0:r1], lb, idx[r0:r1] if per_row else idx).double()
+        if per_row:
+            G = B64[idx[r0:r1].clamp(0, mB - 1)]                   # [b, k, d]; a row with a bad index is NaN in Z
+            Hc = torch.bmm((G - G.mean(1, keepdim=True)).transpose(1, 2), Z)
+        else:
+            Hc = torch.matmul(shared, Z)
+        H[r0:r1] = 0.5 * (Hc + Hc.transpose(1, 2))
+    return H
+
+
+class UserInformation(collections.namedtuple("UserInformation", ("info", "weight", "status"))):
+    """What `user_information` returns, on the model's device: info f64 [k, d, d], weight f64 [k] (the user's W: the sum
+    of the law's pair weights, m (m - 1) / 2 for the plain risk), status int32 [k] (0; 2: a non-finite score or truth
+    row, the matrix is NaN)."""
+
+
+def user_information(U, V, X, s=1.0, law=None, users=None, at="model", row_block=2048):
+    """For every user named (None: every user; the law's users under a law) the d x d matrix
+        H_u = sum over the law's pairs i < j of w_ij sigmoid'(a_i - a_j) (v_i - v_j)(v_i - v_j)^T
+    → UserInformation.  at="model": a = U[u] V^T, and H_u is the Hessian of the user's risk sum in the row u (the
+    Gauss-Newton and the exact Hessian coincide: the scores are linear in u).  at="truth": a = s X[u], and H_u / W_u is
+    the Fisher information about the row that one comparison carries when it is drawn from the law and labelled with
+    probability sigmoid(s (x_i - x_j)).  Blocks are formed as `law_metrics` forms them; a law's per-user columns go to
+    the kernel as its index.  A user with a non-finite row gets status 2 and a NaN matrix; the others are untouched."""
+    if at not in ("model", "truth"):
+        raise ValueError(f"at must be 'model' or 'truth', got {at!r}")
+    if not all(torch.is_tensor(t) and t.is_cuda for t in (U, V)):
+        raise _lib.MfcdError("the user information needs U and V on a GPU device (there is no CPU fallback)")
+    if U.dtype != torch.float32 or V.dtype != torch.float32:
+        raise _lib.MfcdError("the user information takes float32 factor tables")
+    plain = law is None or law.trivial
+    if plain:
+        src = RowBlocks(U.detach(), V.detach(), X, users, row_block, "the user information")
+    else:
+        src = _law_src(U.detach(), V.detach(), X, users, row_block, law, "the user information")
+    d = V.shape[1]
+    table = src.V.contiguous()
+    info = torch.empty((src.k, d, d), dtype=torch.float64, device=src.dev)
+    weight = torch.full((src.k,), src.m * (src.m - 1) / 2.0, dtype=torch.float64, device=src.dev)
+    for r0, r1 in src.blocks():
+        if plain:
+            lb, truth = None, src.truth(r0, r1)
+            scores = src.scores(r0, r1) if at == "model" else None
+        else:
+            lb, scores, truth = _law_block(src, law, r0, r1)
+            weight[r0:r1] = pair_law_stats_rows(truth, truth, lb, s)[1][:, 0]
+        if at == "truth":
+            scores = truth * float(s)
+        info[r0:r1] = pair_info_rows(scores, table, truth, lb, None if lb is None else lb.columns)
+    status = torch.where(torch.isnan(info).flatten(1).any(1), 2, 0).to(torch.int32)
+    return UserInformation(info, weight, status)
 
 
 def strategy_law(X, num_triplets, strategy, device, popularity_method="zipf", alpha=1.5, k=None, n_clusters=10, seed=0):

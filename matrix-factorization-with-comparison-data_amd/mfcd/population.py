@@ -22,18 +22,25 @@ and the certificate then cannot be reached: the row stops with status 1 and `gra
 
 `fit_population_exact` alternates the two steps.  No speed is promised: F is invariant under a joint rescaling of U and
 V up to the penalty, so alternation converges linearly and slowly at small l2, as for any alternating scheme.  There is
-no CPU form of any of it."""
+no CPU form of any of it.
+
+The user step also has a direct form (solver="direct"): the d x d Hessian  c V^T L(a) V + l2 I  of every row is formed by
+`pairs.pair_info_rows` (one multi-column kernel call instead of one Hessian-vector call per CG iteration) and the
+direction comes from a batched f64 Cholesky solve on the device; the Armijo rule, the certificate and the statuses are
+the same.  The item step has no such form: its Hessian is (m d) x (m d)."""
 import collections
 
 import torch
 
 from . import _lib
 from . import pairs as P
-from .rows import RowBlocks
+from .rows import RowBlocks, blocks as _blocks
 
 CONVERGED, STOPPED, INVALID = 0, 1, 2
 ARMIJO = 1e-4            # sufficient-decrease constant
 MIN_STEP = 2.0 ** -12    # a row whose step length falls below this has found no Armijo decrease: it stops
+SOLVERS = ("cg", "direct")
+DIRECT_BYTES = 64 << 20  # the direct user step keeps a block's [b, d, d] f64 Hessians under this
 CG_TOL = 1e-4            # relative residual at which a row's CG freezes: the products carry fp32 noise of about 2e-5
 
 
@@ -91,7 +98,7 @@ class _UserProblem:
 
     def __init__(self, blk, V, coef, l2):
         self.blk, self.coef, self.l2 = blk, coef, l2
-        self.Vt, self.V64 = V.t(), V.double()
+        self.V32, self.Vt, self.V64 = V, V.t(), V.double()
         self.VV = self.V64 * self.V64
 
     def prepare(self, u):
@@ -110,6 +117,22 @@ class _UserProblem:
         Q, D = self.blk.hvp(A, self.blk.take(p.float() @ self.Vt), deg)
         out = self.coef * (Q.double() @ self.V64) + self.l2 * p
         return out, (self.coef * (D.double() @ self.VV) + self.l2 if deg else None)
+
+    def direct(self, A, g, active):
+        """H p = -g by a Cholesky factorisation of every active row's c V^T L(a) V + l2 I → p (0 where not active).  A
+        row whose matrix does not factor (the fp32 noise of the Laplacian against a tiny l2) takes the gradient scaled
+        by the matrix's mean diagonal: still a descent direction, and the Armijo rule decides."""
+        law = self.blk.law
+        H = self.coef * P.pair_info_rows(A, self.V32, self.blk.truth, law, None if law is None else law.columns)
+        d = H.shape[1]
+        eye = torch.eye(d, dtype=torch.float64, device=H.device)
+        H = torch.where(active[:, None, None], H + self.l2 * eye, eye)
+        chol, info = torch.linalg.cholesky_ex(H)
+        ok = info == 0
+        chol = torch.where(ok[:, None, None], chol, eye)
+        p = torch.cholesky_solve(-g[:, :, None], chol)[:, :, 0]
+        p = torch.where(ok[:, None], p, -g / H.diagonal(dim1=1, dim2=2).mean(1, keepdim=True))
+        return torch.where(active[:, None], p, torch.zeros_like(p))
 
 
 class _ItemProblem:
@@ -195,8 +218,9 @@ def _cg(prob, state, x, g, active, max_cg):
     return p, its
 
 
-def _newton(prob, x, l2, gtol, max_newton, max_cg):
-    """Damped Newton-CG on the rows of x [b, D] (f64) → (x, status, newton_iters, cg_iters, f0, f, grad_ratio)."""
+def _newton(prob, x, l2, gtol, max_newton, max_cg, solver="cg"):
+    """Damped Newton-CG (solver="direct": damped Newton with `prob.direct`'s directions) on the rows of x [b, D] (f64) →
+    (x, status, newton_iters, cg_iters, f0, f, grad_ratio)."""
     max_newton = int(max_newton)
     if max_newton < 0:
         raise ValueError("max_newton must be >= 0")
@@ -221,7 +245,9 @@ def _newton(prob, x, l2, gtol, max_newton, max_cg):
         n_active, n_moved = torch.stack((active.sum(), (active & moved).sum())).tolist()   # the iteration's one host read
         if n_active == 0:
             break
-        if n_moved or p is None:
+        if (n_moved or p is None) and solver == "direct":
+            p, its = prob.direct(state, g, active), torch.zeros_like(cgs)
+        elif n_moved or p is None:
             p, its = _cg(prob, state, x, g, active, max_cg)
         else:            # every row still active had its step rejected: x, and with it the direction, is what it was
             p, its = torch.where(active[:, None], p, torch.zeros_like(p)), torch.zeros_like(cgs)
@@ -264,7 +290,8 @@ def _setup(U, V, X, s, l2, law, users, row_block, who):
     return src, law, 1.0 / total
 
 
-def population_user_step(U, V, X, s, l2, law=None, users=None, gtol=1e-3, max_newton=20, row_block=2048, max_cg=None):
+def population_user_step(U, V, X, s, l2, law=None, users=None, gtol=1e-3, max_newton=20, row_block=2048, max_cg=None,
+                         solver="cg"):
     """fp32 tables U [n, d], V [m, d] on a GPU, X dense or a FactoredMatrix, l2 > 0 → PopulationStepResult: with V fixed,
     for every user named (None: every user; the law's users under a law) the minimiser over the user's row u of
         f(u) = c * (risk sum of u V^T against the user's truth row) + (l2 / 2) |u|^2,
@@ -274,18 +301,32 @@ def population_user_step(U, V, X, s, l2, law=None, users=None, gtol=1e-3, max_ne
     issued for the whole block since nothing reads the device inside a solve (None: min(d, 64)).  A
     user with a non-finite score or truth row gets status 2 and a NaN row, and under a law stays out of c (see
     `pairs.law_weight_total`: `pairs.law_risk` itself is NaN for such an input, so there is nothing else to agree
-    with); the other users' problems are those of a call that does not name that user.  The inputs are not modified."""
+    with); the other users' problems are those of a call that does not name that user.  The inputs are not modified.
+    solver="direct": every Newton direction from the row's d x d Hessian (`pairs.pair_info_rows`, d <= 256: ValueError
+    beyond) and a batched f64 Cholesky solve instead of CG; `cg_iters` is 0, `max_cg` is not used, and the row block is
+    shrunk so that a block's matrices stay under 64 MiB.  Rule, certificate and statuses are the same."""
+    _check_solver(solver, U.shape[1] if torch.is_tensor(U) and U.dim() == 2 else 0)
     src, law, coef = _setup(U, V, X, s, l2, law, users, row_block, "the population user step")
-    return _user_step(src, law, coef, s, l2, gtol, max_newton, max_cg)
+    return _user_step(src, law, coef, s, l2, gtol, max_newton, max_cg, solver)
 
 
-def _user_step(src, law, coef, s, l2, gtol, max_newton, max_cg):
+def _check_solver(solver, d):
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    if solver == "direct" and d > P.INFO_MAX_D:
+        raise ValueError(f"the direct user step forms d x d matrices for d <= {P.INFO_MAX_D}, got d = {d}")
+
+
+def _user_step(src, law, coef, s, l2, gtol, max_newton, max_cg, solver="cg"):
     d = src.U.shape[1]
+    _check_solver(solver, d)
     max_cg = min(d, 64) if max_cg is None else int(max_cg)
+    row_block = src.row_block if solver == "cg" else min(src.row_block, max(1, DIRECT_BYTES // (8 * d * d)))
     parts = []
-    for r0, r1 in src.blocks():
+    for r0, r1 in _blocks(src.k, row_block):
         prob = _UserProblem(_Block(src, law, r0, r1, float(s)), src.V, coef, float(l2))
-        parts.append(_newton(prob, src.rows_of(src.U, r0, r1).double(), float(l2), float(gtol), max_newton, max_cg))
+        parts.append(_newton(prob, src.rows_of(src.U, r0, r1).double(), float(l2), float(gtol), max_newton, max_cg,
+                             solver))
     x, status, newton, cgs, f0, f, ratio = (torch.cat(t) for t in zip(*parts))
     nan = torch.full((), float("nan"), dtype=torch.float64, device=src.dev)
     rows = torch.where((status == INVALID)[:, None], nan, x).float()
@@ -310,11 +351,13 @@ def _item_step(src, law, coef, s, l2, gtol, max_newton, max_cg):
     return PopulationStepResult(rows, status[0], newton[0], cgs[0], f0[0], f[0], ratio[0])
 
 
-def fit_population_exact(U, V, X, s, l2, sweeps, law=None, gtol=1e-3, max_newton=20, row_block=2048):
+def fit_population_exact(U, V, X, s, l2, sweeps, law=None, gtol=1e-3, max_newton=20, row_block=2048, user_solver="cg"):
     """`sweeps` sweeps of one exact user step and one exact item step of F, in place on the fp32 tables U and V →
     PopulationFitResult; F is recorded after every sub-step and does not increase.  Under a law that names its users the
     rows of the other users are left as they are (only the penalty holds them).  A step with status 2 changes nothing.
-    The set-up (checks, row blocks, a law's weight total and its one host wait) is done once, before the first sweep."""
+    The set-up (checks, row blocks, a law's weight total and its one host wait) is done once, before the first sweep.
+    user_solver: the `solver` of the user steps ("cg" or "direct", see `population_user_step`)."""
+    _check_solver(user_solver, U.shape[1] if torch.is_tensor(U) and U.dim() == 2 else 0)
     sweeps = int(sweeps)
     if sweeps < 0:
         raise ValueError("sweeps must be >= 0")
@@ -332,7 +375,7 @@ def fit_population_exact(U, V, X, s, l2, sweeps, law=None, gtol=1e-3, max_newton
 
     with torch.no_grad():
         for k in range(sweeps):
-            step = _user_step(src, law, coef, s, l2, gtol, max_newton, None)      # src reads U and V in place
+            step = _user_step(src, law, coef, s, l2, gtol, max_newton, None, user_solver)   # src reads U and V in place
             if start is None:
                 start = step.objective_before.sum() + penalty(V) + (0.0 if src.whole else penalty(U) - penalty(U[src.ids]))
             good = (step.status != INVALID)[:, None]

@@ -290,16 +290,18 @@ def population_hvp(model, X, dU, dV, s=1.0, law=None, users=None, row_block=2048
     return _pairs.population_hvp(model.U.data, model.V.data, X, dU, dV, s, law, users, row_block, gauss_newton)
 
 
-def refit_users_population(model, X, s, weight_decay, law=None, users=None):
+def refit_users_population(model, X, s, weight_decay, law=None, users=None, solver="cg"):
     """Extension (not in the reference): `refit_users` with unlimited comparisons — for the model's own V, the best
     response of every user's row on  F = population_risk (or law_risk) + (wd / 2)(|U|^2 + |V|^2),  the objective whose
     stationary points `train_model_population` / `train_model_law` approach under Adam's coupled weight decay, by
     mfcd.population.population_user_step started at `model.U`.  Returns (result, gain): the PopulationStepResult (rows,
     status 0 certified / 1 stopped / 2 invalid, newton_iters, cg_iters, objective_before, objective_after, grad_ratio)
     and, per user, gain = objective_before - objective_after >= 0: what the trained row still had to gain in F with V
-    fixed.  weight_decay must be > 0.  The model is not changed.  Not part of the result dict / .pkl layout."""
+    fixed.  weight_decay must be > 0.  The model is not changed.  solver="direct": every Newton direction from the row's
+    d x d Hessian and a Cholesky solve instead of CG (d <= 256).  Not part of the result dict / .pkl layout."""
     _need_gpu(model.U.device)
-    result = _population.population_user_step(model.U.data, model.V.data, X, s, float(weight_decay), law, users)
+    result = _population.population_user_step(model.U.data, model.V.data, X, s, float(weight_decay), law, users,
+                                              solver=solver)
     return result, result.objective_before - result.objective_after
 
 
@@ -313,16 +315,54 @@ def refit_items_population(model, X, s, weight_decay, law=None):
     return result, result.objective_before - result.objective_after
 
 
-def train_model_population_exact(model, X, s, weight_decay, sweeps=10, law=None):
+def train_model_population_exact(model, X, s, weight_decay, sweeps=10, law=None, user_solver="cg"):
     """Extension (not in the reference): `train_model_population` by exact block steps instead of Adam — `sweeps` sweeps of
     one exact user step and one exact item step of  F = population_risk (or law_risk) + (wd / 2)(|U|^2 + |V|^2)
     (mfcd.population.fit_population_exact), each a Newton-CG solve on the pair Hessian, in place on the model's tables.
     Returns F after every sub-step as a list of [after the user step, after the item step] per sweep; it does not
-    increase.  fp32 models only; weight_decay must be > 0.  Not part of the result dict / .pkl layout."""
+    increase.  fp32 models only; weight_decay must be > 0.  user_solver: "cg" or "direct", the user steps' solver
+    (mfcd.population.population_user_step).  Not part of the result dict / .pkl layout."""
     _need_gpu(model.U.device)
-    result = _population.fit_population_exact(model.U.data, model.V.data, X, s, float(weight_decay), sweeps, law)
+    result = _population.fit_population_exact(model.U.data, model.V.data, X, s, float(weight_decay), sweeps, law,
+                                              user_solver=user_solver)
     model.eval()
     return result.history.cpu().tolist()
+
+
+def user_information(model, X, s=1.0, law=None, users=None, at="model"):
+    """Extension (not in the reference): for every user the d x d matrix the pair Laplacian induces on the user's row,
+    H_u = sum over the law's item pairs of w_ij sigmoid'(a_i - a_j) (v_i - v_j)(v_i - v_j)^T (include/mfcd.h
+    mfcd_pair_hvp_multi_rows, one kernel pass for all d columns, and one batched GEMM) → mfcd.pairs.UserInformation
+    (info f64 [k, d, d], weight f64 [k], status int32 [k]) on the model's device.  at="model": a = U[u] V^T, the Hessian of
+    the user's risk sum in u; at="truth": a = s X[u], and info / weight is the Fisher information about the row that one
+    comparison drawn from the law carries.  law: a `sampling_law` (None: every pair, weight 1); users=None: the law's
+    users.  fp32 models only.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _pairs.user_information(model.U.data, model.V.data, X, s, law, users, at)
+
+
+def strategy_information(model_or_V, X, s, num_triplets, strategies=("random", "margin", "popularity", "variance", "top_k",
+                                                                     "proximity", "cluster"), users=None):
+    """Extension (not in the reference): how much the comparisons of each sampling strategy say about a user's row,
+    without training a model → dict strategy → f64 numpy [k, d]: per user, the ascending eigenvalues of the
+    per-comparison Fisher information H_u / W_u at the truth (`user_information(..., at="truth")` under
+    `sampling_law(X, num_triplets, strategy)`, with the item table of `model_or_V`: a model or V [m, d]).  NaN marks a
+    user without weight (or with a non-finite row).  Which design criterion to read off — the trace of the inverse, the
+    log-determinant, the smallest eigenvalue — is the caller's choice.  Not part of the result dict / .pkl layout."""
+    V = model_or_V.V.data if hasattr(model_or_V, "V") else model_or_V
+    _need_gpu(V.device)
+    V = V.detach().float()
+    U = torch.zeros((X.shape[0], V.shape[1]), dtype=torch.float32, device=V.device)     # at="truth" reads no scores of U
+    out = {}
+    for strategy in strategies:
+        law = sampling_law(X, num_triplets, strategy, device=V.device)
+        res = _pairs.user_information(U, V, X, s, law, users, "truth")
+        per = res.info / res.weight[:, None, None]                                     # 0 / 0 = NaN: a user without weight
+        good = torch.isfinite(per).flatten(1).all(1)
+        eye = torch.eye(V.shape[1], dtype=torch.float64, device=V.device)
+        eig = torch.linalg.eigvalsh(torch.where(good[:, None, None], per, eye))
+        out[strategy] = torch.where(good[:, None], eig, torch.full_like(eig, float("nan"))).cpu().numpy()
+    return out
 
 
 def _comparisons(data, n, m, device):
