@@ -959,6 +959,53 @@ int mfcd_item_step_cg(const float *U, int n, const float *V, int m, int d, const
                       double gtol, float *V_out, double *objective2, int32_t *iters_status, int32_t *cg_iters,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * Gradient and Hessian-vector product of the sampled BTL objective with respect to both tables (no reference
+ * counterpart; tests/newton_model.py restates the arithmetic):
+ *   F(U, V) = sum_t softplus(x_t) - z_t x_t + (l2 / 2)(|U|^2 + |V|^2),   x_t = U[u_t] . (V[i_t] - V[j_t]).
+ * With delta_t = V[i_t] - V[j_t], p_t = sigmoid(x_t), r_t = p_t - z_t, w_t = p_t (1 - p_t), sigma_t = [i_t = k] - [j_t = k]
+ * and a direction (P [n][d], Q [m][d]),  y_t = P[u_t] . delta_t + U[u_t] . (Q[i_t] - Q[j_t]):
+ *   pass 0, side 0:  out[r] = sum_t r_t delta_t + l2 U[u],  diag[r][c] = sum_t w_t delta_t[c]^2 + l2,
+ *                    loss[r] = sum_t softplus(x_t) - z_t x_t        (the sum of loss over all users is F's data term)
+ *   pass 0, side 1:  out[r] = sum_t sigma_t r_t U[u_t] + l2 V[k],  diag[r][c] = sum_t sigma_t^2 w_t U[u_t][c]^2 + l2
+ *   pass 1, side 0:  out[r] = sum_t (w_t y_t delta_t + r_t (Q[i_t] - Q[j_t])) + l2 P[u]
+ *   pass 1, side 1:  out[r] = sum_t sigma_t (w_t y_t U[u_t] + r_t P[u_t]) + l2 Q[k]
+ * the sums over the records of row r, which owns table row u = k = row_id[r] (NULL: r).  gauss_newton = 1 drops the two
+ * r_t terms of pass 1 (the product is then positive semidefinite; the exact one need not be).  diag is the diagonal of
+ * the row's own block of the Hessian.  records / row_off are those of mfcd_fold_in_users (side 0: the comparisons sorted
+ * by user) and of mfcd_item_step (side 1: every comparison once in the row of its i and once in the row of its j; one
+ * with i = j appears twice in one row and adds exactly nothing there).
+ * Segments.  A row's records are cut into row-relative segments of S = mfcd_triplet_rows_segment() records: segment s of
+ * row r covers records [row_off[r] + s S, ...).  The caller passes seg_off [rows + 1], the prefix sum of
+ * ceil(len_r / S), and its total n_seg (the host cannot see row_off, and the entry has no host wait).  A first kernel
+ * gives one wave to every segment: it finds its row by binary search in seg_off and writes the segment's sums to the
+ * workspace in f64.  A second kernel gives every output element one owner, which adds the row's segments in ascending
+ * order and then the l2 term.  Inside a wave a group of L = min(64, next power of two >= d) lanes holds one record, so
+ * 64 / L records are in flight; dot products are cross-lane sums in a fixed order, and so are the sums over the groups.
+ * No floating-point atomics.  So two calls are bit-equal; a row's outputs depend only on its own records, the table
+ * rows they name and the scalars, not on the row's place in the call or on the other rows; and a long row is spread over
+ * many waves.  All tables, directions, outputs and arithmetic are f64.
+ * Validation, before any gather: side 0: u = the row's user, i and j in [0, m); side 1: u in [0, n), i and j in [0, m),
+ * i or j the row's item; z in [0, 1] and not NaN; the row's own index in range; row_off[r] >= 0 and <= row_off[r + 1];
+ * seg_off[r + 1] - seg_off[r] = ceil(len_r / S) inside [0, n_seg].  A row that fails gets status 2, an all-NaN out and
+ * diag and a NaN loss, and nothing is read outside the tables; the other rows are not touched by it.  Non-finite table
+ * entries are not looked for: they propagate by arithmetic.  A row without records gets out = l2 x (its row of the
+ * table, or of the direction in pass 1) exactly, diag = l2, loss = 0, status 0.
+ * Limits: side, pass and gauss_newton in {0, 1}, 1 <= d <= 256, n >= 1, m >= 1, rows >= 0 (0 = success, nothing
+ * launched), rows <= n (m) where row_id is NULL, 0 <= n_seg <= 2^31, l2 finite and > 0, P and Q in pass 1 (ignored in
+ * pass 0), records where n_seg > 0; diag (pass 0) and loss (pass 0, side 0) may be NULL and are ignored elsewhere; out,
+ * diag and loss overlapping none of U, V, P, Q; MFCD_EINVAL outside them and MFCD_EWORKSPACE for a workspace below
+ * mfcd_triplet_rows_workspace_bytes(rows, d, n_seg) (256 + (2 d + 1) doubles and one int32 per segment, each region
+ * rounded up to 256; 0 = sizes out of range), both before anything touches the device.  No allocation and no host wait.
+ */
+int mfcd_triplet_rows_segment(void);
+size_t mfcd_triplet_rows_workspace_bytes(int rows, int d, int64_t n_seg);
+int mfcd_triplet_rows(int side, int pass, int gauss_newton, const double *U, int n, const double *V, int m, int d,
+                      const double *P, const double *Q, const mfcd_sample *records, const int64_t *row_off,
+                      const int32_t *row_id, int rows, const int64_t *seg_off, int64_t n_seg, double l2, double *out,
+                      double *diag, double *loss, int32_t *status, void *workspace, size_t workspace_bytes,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,8 +9,10 @@
 `foldin`   the exact block steps: one Newton solve per user with V fixed (mfcd_fold_in_users), one per item with U and
            the other items fixed (mfcd_item_step).
 `alternating` the two block steps alternated: monotone exact-block descent of the regularised BTL objective.
+`newton`   both tables at once: gradient and Hessian-vector product of the sampled objective (mfcd_triplet_rows) and a
+           trust-region Newton-CG fit on them.
 `population` the exact block steps of the ridge-regularised population risk: Newton-CG on mfcd_pair_hvp_rows.
 """
-from . import _lib, alternating, batching, engine, foldin, metrics, pairs, population, topk  # noqa: F401
+from . import _lib, alternating, batching, engine, foldin, metrics, newton, pairs, population, topk  # noqa: F401
 
-__all__ = ["_lib", "alternating", "batching", "engine", "foldin", "metrics", "pairs", "population", "topk"]
+__all__ = ["_lib", "alternating", "batching", "engine", "foldin", "metrics", "newton", "pairs", "population", "topk"]

@@ -118,6 +118,10 @@ SIGNATURES = {
     "mfcd_item_step_cg_workspace_bytes": (_sz, [_i32, _i32, _i64]),
     "mfcd_item_step_cg": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _dbl, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp,
                                  _vp, _sz, _vp]),
+    "mfcd_triplet_rows_segment": (_i32, []),
+    "mfcd_triplet_rows_workspace_bytes": (_sz, [_i32, _i32, _i64]),
+    "mfcd_triplet_rows": (_i32, [_i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _dbl,
+                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 TUNE_KEYS = {"resident_lookahead": 3, "resident_spin_limit": 5, "uvt_target_wgs": 9, "uvt_min_stages": 10,

@@ -5,7 +5,8 @@ fixed) and then `item_steps` simultaneous item steps at theta = 1/2: every item 
 minimiser against the current rows of the others.  Every loss term holds two item rows and the penalty one, so by
 convexity, term by term, F(V_new) <= F(V) - (1/2) sum_k (f_k(v_k) - f_k(v*_k)): F falls at every sub-step, without
 colouring the items and without any dependence on order.  F is invariant under a joint rescaling of U and V up to the
-penalty, so convergence is linear and slow at small l2, as for any alternating scheme."""
+penalty, so convergence is linear and slow at small l2, as for any alternating scheme; mfcd.newton.fit_newton moves both
+tables at once and certifies a stationary point."""
 import collections
 
 import torch

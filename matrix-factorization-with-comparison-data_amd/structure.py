@@ -24,6 +24,7 @@ from mfcd import alternating as _alternating
 from mfcd import engine as _engine
 from mfcd import foldin as _foldin
 from mfcd import metrics as _metrics
+from mfcd import newton as _newton
 from mfcd import pairs as _pairs
 from mfcd import population as _population
 from mfcd import sampling as _sampling
@@ -493,6 +494,23 @@ def refit_alternating(model, train_loader, weight_decay, sweeps=10, item_steps=2
     u, i, j, z = _comparisons(train_loader, U.shape[0], V.shape[0], V.device)
     result = _alternating.fit_alternating(U, V, u, i, j, z, float(weight_decay) * u.numel(), sweeps, item_steps)
     return result, result.objective_start
+
+
+def refit_newton(model, train_loader, weight_decay, max_iter=100):
+    """Extension (not in the reference): joint second-order descent of the regularised empirical objective from the
+    trained tables — mfcd.newton.fit_newton on the training comparisons with  l2 = weight_decay * N, so that
+    F = N x (mean BCE + (wd / 2)(|U|^2 + |V|^2)), N times what the reference's optimiser descends.  Both tables move at
+    once, by trust-region Newton-CG on the exact Hessian-vector product of F; status 0 certifies a stationary point
+    (|grad F|_inf <= 2^-26 l2 max|.|_inf).  Returns (result, F_at_model): the NewtonResult (tables, F and |grad F|_inf of
+    every outer iteration, CG iterations, status) and F at the model's tables; F_at_model - result.history[-1] is how
+    much of F the optimiser had left, and result.grad_inf[0] how far the model is from a stationary point of its own
+    training objective.  weight_decay must be > 0; d <= 256.  The model is not changed.  Not part of the result dict /
+    .pkl layout."""
+    _need_gpu(model.V.device)
+    U, V = model.U.data, model.V.data
+    u, i, j, z = _comparisons(train_loader, U.shape[0], V.shape[0], V.device)
+    result = _newton.fit_newton(U, V, u, i, j, z, float(weight_decay) * u.numel(), max_iter)
+    return result, result.history[0]
 
 
 def compute_ground_truth_metrics(test_loader, X, device):
