@@ -819,6 +819,39 @@ int mfcd_pair_hvp_multi_rows(const float *A, int64_t lda, const float *X, int64_
                              void *stream);
 
 /*
+ * Per column, the most informative admissible partner (no reference counterpart): the arg-max a D-optimal comparison
+ * design needs per iteration (mfcd/design.py).  For row r of A [rows][lda] and every column i < k,
+ *     best_val[r][i] = max over admissible j != i of  s_ij |g_i - g_j|^2,     s_ij = sigmoid'(a_i - a_j),
+ *     best_j[r][i]   = the j that attains it, the smallest j among equal scores,
+ * with g_j row j of the row's table G + r * g_row_stride, [k][ldg] fp32 with d columns; g_row_stride = 0 is one table
+ * for all rows.  The pair (i, j) is admissible when the weight of the mfcd_pair_law struct is > 0: the law gives the
+ * support only, its magnitude does not enter the score; law = NULL admits every pair.  X is read for the law's margin
+ * and the finiteness rule only and may be NULL when the law has no margin.  A column without an admissible partner
+ * (k = 1 included) gets the value +0 and the index -1.  A row with a non-finite entry in A, in X (when given) or in a row
+ * of its table — or whose table has a row whose squared norm overflows fp32 — is all NaN / -1; the other rows are
+ * untouched.  Columns >= k are not written.
+ * Kernel (csrc/pair_best.hip): one 256-thread workgroup per (row, tile of 128 columns i); the columns j stream through
+ * LDS in stages of 64, at most 128 columns of d at a time; the products g_i . g_j ride v_mfma_f32_32x32x2_f32 oriented so
+ * that the accumulator's column is i, and |g_i - g_j|^2 = max(n_i + n_j - 2 g_i . g_j, 0) with the squared norms n of a
+ * pre-pass (f64 sum in the order of the columns, rounded to fp32 once).  The table is NOT centred here: the caller
+ * subtracts the column mean, so that the cancellation is at the size of the table's spread.  s = e h h with
+ * e = exp(-|a_i - a_j|), h = 1 / (1 + e), as mfcd_pair_hvp_rows.  A lane owns one i and sixteen j per 32 x 32 block and
+ * keeps a running (max, arg) in registers; the two half-waves of a column are combined once, the tie to the smaller j.
+ * No atomics, every result has one owner: two calls are bit-equal, and a row's result does not depend on the other rows,
+ * on the leading dimensions or on its place in the call.  An odd d is padded with zero columns inside the kernel.
+ * Limits: rows >= 0 (0 = success, nothing launched), 1 <= k <= 1 048 576, 1 <= d <= 256, lda, ldv, ldj (ldx with X) >= k,
+ * ldg >= d, g_row_stride 0 or >= k * ldg, the outputs none of the inputs nor each other, the law rules of
+ * mfcd_pair_law_grad_rows for a law that is not NULL, and X not NULL under a law with a margin; MFCD_EINVAL outside them
+ * and MFCD_EWORKSPACE for a short workspace, before anything touches the device.  workspace: as the workspace_bytes
+ * entry says (4 k bytes per row of a block of rows of at most 64 MiB; 0 = sizes out of range), 256-byte aligned.  Long
+ * inputs go through in blocks of rows.  No allocation and no host wait.
+ */
+size_t mfcd_pair_best_workspace_bytes(int rows, int k, int d);
+int mfcd_pair_best_rows(const float *A, int64_t lda, const float *X, int64_t ldx, const float *G, int64_t g_row_stride,
+                        int64_t ldg, int d, int rows, int k, const mfcd_pair_law *law, float *best_val, int64_t ldv,
+                        int32_t *best_j, int64_t ldj, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * The exact user step of the BTL fit, "fold-in" (no reference counterpart: the reference only ever moves U and V
  * together, structure.py:845-852): with the item table V [m][d] held fixed, row r of U_out is the minimiser of
  *     f(u) = sum over t of  softplus(x_t) - z_t x_t  +  (l2 / 2) |u|^2,     x_t = u . delta_t,  delta_t = V[i_t] - V[j_t],

@@ -39,12 +39,7 @@ constexpr int kInfoSlices = 8;                         // interleaved slices of 
 constexpr size_t kInfoRowBytes = kInfoMaxD * sizeof(double) + (kInfoMaxD / 32) * sizeof(int);
 
 inline int info_tiles(int k) { return (k + kInfoTile - 1) / kInfoTile; }
-inline int info_chunk_rows(int rows, int T)
-{
-    int64_t R = kPairMaxBlocks / T;                    // >= 128
-    if (R > kInfoMaxRows) R = kInfoMaxRows;
-    return (int)(rows < R ? rows : R);
-}
+inline int info_chunk_rows(int rows, int T) { return pair_chunk_rows(rows, T, kInfoMaxRows); }
 
 struct InfoArgs {
     const float *A, *X, *B;

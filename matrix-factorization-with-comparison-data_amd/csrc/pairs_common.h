@@ -10,6 +10,15 @@ namespace {
 constexpr int kPairMaxCols = 1 << 20;
 constexpr int64_t kPairMaxBlocks = 1 << 20;            // (row, tile) workgroups per launch: bounds the workspace at 80 MiB
 
+// Rows per launch of a kernel with T (row, tile) workgroups per row: long inputs go through in blocks of rows of at most
+// kPairMaxBlocks workgroups and at most `cap` rows (what the kernel's per-row workspace allows).
+inline int pair_chunk_rows(int rows, int T, int64_t cap)
+{
+    int64_t R = kPairMaxBlocks / T;                    // >= 128
+    if (R > cap) R = cap;
+    return (int)(rows < R ? rows : R);
+}
+
 // Every unordered pair {i, j} of a row carries a weight
 //   w = (alpha_i beta_j + alpha_j beta_i   or 1)  *  [|x_i - x_j| <= margin]  *  [label_i != label_j],
 // each factor present or not (template flags HW, HM, HL: an absent factor costs no load and no instruction).

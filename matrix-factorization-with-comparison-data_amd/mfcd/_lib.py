@@ -102,6 +102,9 @@ SIGNATURES = {
     "mfcd_pair_hvp_multi_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "mfcd_pair_hvp_multi_rows": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp,
                                         _i64, _vp, _sz, _vp]),
+    "mfcd_pair_best_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "mfcd_pair_best_rows": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _sz,
+                                   _vp]),
     "mfcd_fold_in_max_d": (_i32, []),
     "mfcd_fold_in_chunk": (_i32, []),
     "mfcd_fold_in_workspace_bytes": (_sz, [_i32, _i32]),

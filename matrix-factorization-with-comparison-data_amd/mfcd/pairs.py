@@ -23,6 +23,10 @@ Hessian-vector product of `population_risk` / `law_risk`.  mfcd/population.py bu
 pass, `pair_info_rows` contracts the result to the d x d matrix H_r = B_r^T L(a_r) B_r the Laplacian induces on a user's
 row, and `user_information` forms it for the users of a model: the Hessian of a user's risk sum in u (at="model") or the
 Fisher information of the law's comparisons about the row (at="truth").
+
+`pair_best_rows` (mfcd_pair_best_rows) finds, per column, the admissible partner with the largest
+sigmoid'(a_i - a_j) |g_i - g_j|^2 on a table the caller centres: the arg-max mfcd/design.py builds the D-optimal
+comparison design of a user on.
 """
 import collections
 import copy
@@ -37,7 +41,9 @@ from .rows import RowBlocks
 TILE = 1024          # columns per workgroup tile of the kernel (csrc/pairs.hip: kPairTile)
 INFO_TILE = 128     # columns per workgroup tile of the multi-column kernel (csrc/pair_info.hip: kInfoTile)
 INFO_MAX_D = 256    # its widest item table (kInfoMaxD)
-_INFO_Z_BYTES = 256 << 20    # `pair_info_rows` takes rows in chunks whose Z stays under this
+BEST_TILE = 128     # columns per workgroup tile of the arg-max kernel (csrc/pair_best.hip: kBestTile)
+BEST_MAX_D = 256    # its widest table (kBestMaxD)
+_INFO_Z_BYTES = 256 << 20   # `pair_info_rows` takes rows in chunks whose Z stays under this
 _WHAT = {"counts": 1, "sums": 2, "both": 3}
 
 
@@ -325,6 +331,47 @@ def pair_hvp_multi_rows(A, B, X=None, law=None, index=None, deg=False):
                                               None if c is None else ctypes.byref(c), Z.data_ptr(), d, _lib.ptr(D), k,
                                               _lib.ptr(ws), ws.numel(), _lib.stream_ptr(A.device)))
     return (Z, D) if deg else Z
+
+
+def pair_best_rows(A, G, X=None, law=None):
+    """Per column the most informative admissible partner (mfcd_pair_best_rows): scores A [rows, k] and a table G, fp32
+    on the GPU, [rows, k, d] (one table per row) or [k, d] (one for all rows), d <= 256 →
+    (val fp32 [rows, k], j int32 [rows, k]),
+        val_i = max over admissible j != i of s_ij |g_i - g_j|^2,   s_ij = sigmoid'(a_i - a_j),
+    and j_i the smallest j that attains it.  A pair is admissible when the weight of `law` (on rows already restricted
+    to its columns; None: every pair) is > 0; the weight's size does not enter.  X [rows, k] enters through the law's
+    margin and the finiteness rule only; it may be None unless the law has a margin.  The kernel forms |g_i - g_j|^2
+    from squared norms and fp32 matrix products: the caller centres the table.  A column without an admissible partner
+    has (+0, -1); a row with a non-finite entry in A, X or its table is all (NaN, -1).  Deterministic, and a row does
+    not depend on its neighbours."""
+    who = "pair_best_rows"
+    if X is None:
+        A, _, rows, k, lda, _ = _lib.row_pair(A, A, who)
+        ldx = 0
+    else:
+        A, X, rows, k, lda, ldx = _lib.row_pair(A, X, who)
+    if not torch.is_tensor(G) or G.dtype != torch.float32 or not G.is_cuda or G.dim() not in (2, 3):
+        raise _lib.MfcdError(f"{who} needs the table as a float32 GPU tensor [k, d] or [rows, k, d] (no CPU fallback)")
+    if G.shape[-2] != k or (G.dim() == 3 and G.shape[0] != rows):
+        raise ValueError(f"the table must be [{k}, d] or [{rows}, {k}, d], got {tuple(G.shape)}")
+    G = G.contiguous()
+    d = G.shape[-1]
+    c = None if law is None else law._c(rows, k)
+    if law is not None and law.margin is not None and X is None:
+        raise ValueError("a law with a margin needs X")
+    L = _lib.load()
+    val = torch.empty((rows, k), dtype=torch.float32, device=A.device)
+    arg = torch.empty((rows, k), dtype=torch.int32, device=A.device)
+    if rows:
+        _range_check(k)
+        if not 1 <= d <= BEST_MAX_D:
+            raise _lib.MfcdError(f"a table of {d} columns is outside the kernel's range [1, {BEST_MAX_D}]")
+        ws = _lib.workspace(L.mfcd_pair_best_workspace_bytes(rows, k, d), A.device)
+        _lib.check(L.mfcd_pair_best_rows(A.data_ptr(), lda, None if X is None else X.data_ptr(), ldx, G.data_ptr(),
+                                         k * d if G.dim() == 3 else 0, d, d, rows, k,
+                                         None if c is None else ctypes.byref(c), val.data_ptr(), k, arg.data_ptr(), k,
+                                         _lib.ptr(ws), ws.numel(), _lib.stream_ptr(A.device)))
+    return val, arg
 
 
 def pair_info_rows(A, B, X=None, law=None, index=None):

@@ -21,6 +21,7 @@ from torch.utils.data import DataLoader, Dataset
 from generation_data import *  # noqa: F401,F403  (ref:17 re-exports every sampler/generator name)
 import generation_data as _gd
 from mfcd import alternating as _alternating
+from mfcd import design as _design
 from mfcd import engine as _engine
 from mfcd import foldin as _foldin
 from mfcd import metrics as _metrics
@@ -364,6 +365,71 @@ def strategy_information(model_or_V, X, s, num_triplets, strategies=("random", "
         eig = torch.linalg.eigvalsh(torch.where(good[:, None, None], per, eye))
         out[strategy] = torch.where(good[:, None], eig, torch.full_like(eig, float("nan"))).cpu().numpy()
     return out
+
+
+def _truth_tables(model_or_V, X):
+    """(U, V) fp32 on V's device for the calls that read no scores of U (at="truth")."""
+    V = model_or_V.V.data if hasattr(model_or_V, "V") else model_or_V
+    _need_gpu(V.device)
+    V = V.detach().float()
+    if hasattr(model_or_V, "U"):
+        return model_or_V.U.data.detach().float(), V
+    return torch.zeros((X.shape[0], V.shape[1]), dtype=torch.float32, device=V.device), V
+
+
+def optimal_design(model_or_V, X, s, law=None, users=None, at="truth", prior=None):
+    """Extension (not in the reference): the D-optimal comparison design of every user — the probability measure on the
+    user's item pairs that maximises log det(prior + sum_p xi_p sigmoid'(a_i - a_j)(v_i - v_j)(v_i - v_j)^T), the upper
+    bound `strategy_information` lacks — by pairwise Frank-Wolfe on the device (mfcd.design.user_design; include/mfcd.h
+    mfcd_pair_best_rows finds the most informative pair of every user per iteration) → mfcd.design.UserDesign with the
+    support `pairs`, its `weights`, the mass `rest` left on the start measure, `info`, `logdet`, and the certificate
+    `gap` >= log det at the optimum - `logdet`.  model_or_V: a model, or V [m, d] (at="truth" reads no scores of U).
+    law: a `sampling_law` restricts the pairs to its support and is the start measure (None: every pair).  prior: None,
+    a scalar tau (tau I) or [k, d, d].  fp32 models only.  Not part of the result dict / .pkl layout."""
+    U, V = _truth_tables(model_or_V, X)
+    if at != "truth" and not hasattr(model_or_V, "U"):
+        raise ValueError("at='model' needs a model, not a bare V")
+    return _design.user_design(U, V, X, s, law, users, at, prior)
+
+
+def strategy_efficiency(model_or_V, X, s, num_triplets, strategies=("random", "margin", "popularity", "variance", "top_k",
+                                                                     "proximity", "cluster"), users=None, prior=None):
+    """Extension (not in the reference): how far each sampling strategy's comparisons are from the most informative ones
+    possible, per user → dict strategy → f64 numpy [k]: the D-efficiency exp((Phi_strategy - Phi*) / d) with
+    Phi = log det(prior + per-comparison Fisher information at the truth) — Phi_strategy of the strategy's law
+    (`strategy_information`'s matrix), Phi* of `optimal_design` over ALL pairs — plus the key "gap": the design's
+    certificate per user.  Phi* is taken from the design found, which is at most `gap` below the optimum: the true
+    efficiency lies within a factor exp(gap / d) of the reported one (reported >= true >= reported exp(-gap / d)), and
+    no reported value exceeds exp(gap / d).  NaN marks a user without weight under the strategy, or an information matrix that is not positive
+    definite (add a prior).  Not part of the result dict / .pkl layout."""
+    U, V = _truth_tables(model_or_V, X)
+    d = V.shape[1]
+    best = _design.user_design(U, V, X, s, None, users, "truth", prior)
+    M0 = _design._prior(prior, best.info.shape[0], d, V.device)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=V.device)
+    out = {}
+    for strategy in strategies:
+        law = sampling_law(X, num_triplets, strategy, device=V.device)
+        res = _pairs.user_information(U, V, X, s, law, users, "truth")
+        if res.info.shape[0] != best.info.shape[0]:
+            raise ValueError(f"the law of {strategy} names its own users: give `users`")
+        chol, bad = torch.linalg.cholesky_ex(M0 + res.info / res.weight[:, None, None])
+        phi = torch.where(bad == 0, 2.0 * chol.diagonal(dim1=1, dim2=2).log().sum(1), nan)
+        out[strategy] = torch.exp((phi - best.logdet) / d).cpu().numpy()
+    out["gap"] = best.gap.cpu().numpy()
+    return out
+
+
+def informative_pairs(model, X, k, s=1.0, law=None, users=None, prior=None):
+    """Extension (not in the reference): for every user the k comparisons worth asking next — at the model's scores
+    a = U[u] V^T and P = (prior + H_u)^-1, with H_u the user's information under `law` (`user_information`), the k
+    anchor items i with the largest  max over j of sigmoid'(a_i - a_j)(v_i - v_j)^T P (v_i - v_j)  and each one's best
+    partner j (include/mfcd.h mfcd_pair_best_rows, then mfcd_topk_rows over its values) → (i int32 [users, k],
+    j int32 [users, k], score fp32 [users, k]) on the model's device, positions in the law's columns.  prior: None, a
+    scalar or [users, d, d]; a user whose prior + H_u is not positive definite gets -1 / -1 / NaN.  Not part of the
+    result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _design.informative_pairs(model.U.data, model.V.data, X, k, s, law, users, prior)
 
 
 def _comparisons(data, n, m, device):

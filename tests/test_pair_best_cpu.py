@@ -1,0 +1,204 @@
+"""CPU-only checks of the pair arg-max entry and of the design built on it (include/mfcd.h: mfcd_pair_best_rows;
+mfcd/pairs.py: pair_best_rows; mfcd/design.py: user_design, informative_pairs; the structure.py names): the entry is
+declared and bound under the unchanged ABI version, every limit is refused before the device is touched, there is no CPU
+fallback, the public signatures are what the documents say, the kernel's model (tests/pair_best_model.py) is the
+definition, and the design's model (tests/design_model.py) reaches its certificate."""
+import ctypes
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import design_model as DM
+import pair_best_model as BM
+import pair_law_model as LM
+from conftest import ROOT
+
+
+def test_best_entry_is_declared_and_bound():
+    from mfcd import _lib, pairs
+    header = open(os.path.join(ROOT, "include", "mfcd.h")).read()
+    for name, nargs, res in (("mfcd_pair_best_rows", 18, "int"), ("mfcd_pair_best_workspace_bytes", 3, "size_t")):
+        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == nargs, name
+        decl = re.search(r"\b%s %s\(([^)]*)\)" % (res, name), header).group(1)
+        assert len(decl.split(",")) == nargs, name
+    declared = set(re.findall(r"\b(mfcd_[a-z_0-9]+)\s*\(", header)) - {"mfcd_sample"}
+    assert declared == set(_lib.SIGNATURES)
+    assert re.search(r"#define MFCD_ABI_VERSION 4\b", header)
+    L = _lib.load()
+    assert L.mfcd_abi_version() == 4 and L.mfcd_pair_best_rows
+    W = L.mfcd_pair_best_workspace_bytes
+    assert W(0, 8, 3) > 0 and W(5, 8, 3) % 256 == 0 and W(5, 8, 3) >= 5 * 8 * 4 and W(5, 1000, 256) >= 5 * 1000 * 4
+    assert W(-1, 8, 3) == 0 and W(5, 0, 3) == 0 and W(5, 1048577, 3) == 0 and W(5, 8, 0) == 0 and W(5, 8, 257) == 0
+    assert W(10 ** 6, 4096, 64) == W(4096, 4096, 64) <= 64 << 20      # long inputs go through in blocks of rows
+    assert W(10 ** 6, 1048576, 256) <= 64 << 20
+    assert pairs.BEST_TILE == 128 and pairs.BEST_MAX_D == 256
+    src = open(os.path.join(ROOT, "matrix-factorization-with-comparison-data_amd", "csrc", "pair_best.hip")).read()
+    assert re.search(r"kBestTile = %d\b" % pairs.BEST_TILE, src) and '#include "pairs_common.h"' in src
+    assert "law_weight<" in src and "law_dispatch<" in src and "pair_chunk_rows(" in src     # shared, not copied
+
+
+def test_best_bad_arguments_are_refused_before_the_device():
+    from mfcd import _lib
+    L = _lib.load()
+    A_, X_, G_, V_, J_, W_, P = (4096 * q for q in range(1, 8))       # non-null addresses that are never dereferenced
+
+    def law(alpha=None, beta=None, labels=None, stride=0, use_margin=0, margin=0.0):
+        c = _lib.PairLawC()
+        c.alpha, c.beta, c.labels, c.label_stride, c.use_margin, c.margin = alpha, beta, labels, stride, use_margin, margin
+        return c
+
+    def call(rows=2, k=8, d=3, A=A_, X=X_, G=G_, gstride=24, val=V_, arg=J_, lda=8, ldx=8, ldg=3, ldv=8, ldj=8, c=None, ws=W_,
+             nbytes=1 << 20):
+        return L.mfcd_pair_best_rows(A, lda, X, ldx, G, gstride, ldg, d, rows, k, None if c is None else ctypes.byref(c),
+                                     val, ldv, arg, ldj, ws, nbytes, None)
+
+    big = 1 << 21
+    assert call(rows=0) == 0 and call(rows=0, X=None, ldx=0) == 0 and call(rows=0, gstride=0) == 0
+    assert call(rows=0, ws=None, nbytes=0) == 0                                     # nothing to do, nothing launched
+    assert call(rows=0, c=law()) == 0 and call(rows=0, k=1, gstride=3) == 0
+    assert call(rows=-1) == -1 and call(k=0) == -1
+    assert call(k=1048577, lda=big, ldx=big, ldv=big, ldj=big, gstride=0) == -1
+    assert call(d=0, ldg=0) == -1 and call(d=257, ldg=257, gstride=0) == -1
+    assert call(rows=0, d=256, ldg=256, gstride=0) == 0 and call(rows=0, k=1048576, lda=big, ldx=big, ldv=big, ldj=big, gstride=0) == 0
+    assert call(A=None) == -1 and call(G=None) == -1 and call(val=None) == -1 and call(arg=None) == -1
+    assert call(lda=7) == -1 and call(ldx=7) == -1 and call(ldv=7) == -1 and call(ldj=7) == -1 and call(ldg=2) == -1
+    for bad in (1, 23, -24):                                                        # a table stride in (0, k ldg), or negative
+        assert call(gstride=bad) == -1
+    assert call(ldg=4, gstride=31) == -1 and call(rows=0, ldg=4, gstride=32) == 0
+    for other in (A_, X_, G_, J_):                                                  # an output aliases an input or the other
+        assert call(val=other) == -1
+    for other in (A_, X_, G_):
+        assert call(arg=other) == -1
+    assert call(rows=0, val=A_) == -1                                               # a bad call stays bad with no rows
+    assert call(ws=None) == -1 and call(nbytes=63) == -2                            # MFCD_EWORKSPACE
+    assert call(c=law(alpha=P)) == -1 and call(c=law(beta=P)) == -1
+    assert call(c=law(use_margin=1, margin=-1e-30)) == -1 and call(c=law(use_margin=1, margin=float("nan"))) == -1
+    assert call(c=law(labels=P, stride=7)) == -1 and call(c=law(labels=P, stride=-8)) == -1
+    assert call(c=law(use_margin=1, margin=0.5), X=None) == -1                      # a margin needs X
+    assert call(rows=0, c=law(use_margin=1, margin=0.5)) == 0 and call(rows=0, c=law(margin=-1.0), X=None) == 0
+    assert call(rows=0, c=law(alpha=P, beta=P, labels=P, stride=8, use_margin=1, margin=float("inf"))) == 0
+
+
+def test_no_cpu_fallback_and_public_signatures():
+    import structure as S
+    from mfcd import _lib, design, pairs
+    A, G = torch.randn(3, 9), torch.randn(9, 2)
+    for call in (lambda: pairs.pair_best_rows(A, G), lambda: pairs.pair_best_rows(A, torch.randn(3, 9, 2), A, pairs.PairLaw(margin=1.0))):
+        with pytest.raises(_lib.MfcdError):
+            call()
+    model = S.MatrixFactorization(3, 9, 2)
+    U, V = model.U.data, model.V.data
+    for call in (lambda: design.user_design(U, V, A), lambda: design.informative_pairs(U, V, A, 2)):
+        with pytest.raises(_lib.MfcdError):
+            call()
+    for call in (lambda: S.optimal_design(model, A, 1.0), lambda: S.strategy_efficiency(model, A, 1.0, 100),
+                 lambda: S.informative_pairs(model, A, 2)):
+        with pytest.raises(RuntimeError):
+            call()
+    for call in (lambda: design.user_design(U, V, A, at="elsewhere"), lambda: design.user_design(U, V, A, gtol=0.0),
+                 lambda: design.user_design(U, V, A, max_iter=-1)):
+        with pytest.raises(ValueError):
+            call()
+    p = inspect.signature(pairs.pair_best_rows).parameters
+    assert list(p) == ["A", "G", "X", "law"] and p["X"].default is None and p["law"].default is None
+    p = inspect.signature(design.user_design).parameters
+    assert list(p) == ["U", "V", "X", "s", "law", "users", "at", "prior", "gtol", "max_iter", "row_block"]
+    assert p["s"].default == 1.0 and p["at"].default == "truth" and p["gtol"].default == 1e-3
+    assert all(p[k].default is None for k in ("law", "users", "prior", "max_iter", "row_block"))
+    assert design.UserDesign._fields == ("pairs", "weights", "rest", "info", "logdet", "logdet_start", "gap", "iters", "status")
+    p = inspect.signature(S.optimal_design).parameters
+    assert list(p) == ["model_or_V", "X", "s", "law", "users", "at", "prior"] and p["at"].default == "truth"
+    p = inspect.signature(S.strategy_efficiency).parameters
+    assert list(p) == ["model_or_V", "X", "s", "num_triplets", "strategies", "users", "prior"]
+    assert p["strategies"].default == inspect.signature(S.strategy_information).parameters["strategies"].default
+    p = inspect.signature(S.informative_pairs).parameters
+    assert list(p) == ["model", "X", "k", "s", "law", "users", "prior"] and p["s"].default == 1.0
+    for fn in (S.optimal_design, S.strategy_efficiency, S.informative_pairs):
+        assert fn.__doc__.startswith("Extension (not in the reference)") and "Not part of the result dict" in " ".join(fn.__doc__.split())
+    assert not any("design" in k or "efficiency" in k for k in S._RESULT_KEYS)
+
+
+def test_kernel_model_is_the_definition():
+    """S64 by the broadcast equals the pair-by-pair loop; E dominates the f64 difference between the difference form and
+    the Gram form by orders of magnitude; `best` takes the smallest j among equal scores, skips inadmissible pairs and
+    marks columns without a partner."""
+    rng = np.random.default_rng(11)
+    k, d = 23, 5
+    a, G = 1.5 * rng.standard_normal(k), rng.standard_normal((k, d))
+    x = rng.uniform(-3, 3, k).astype(np.float32)
+    w = LM.weights(x, margin=1.0, labels=rng.integers(0, 3, k))
+    w[:, 4] = w[4, :] = 0.0                                           # a column without a partner
+    S64, E, adm = BM.scores(a, G, w, x)
+    for i, j in ((0, 1), (7, 3), (22, 5)):
+        p = 1.0 / (1.0 + np.exp(-(a[i] - a[j])))
+        np.testing.assert_allclose(S64[i, j], p * (1 - p) * ((G[i] - G[j]) ** 2).sum(), rtol=1e-13)
+    n = (G * G).sum(1)
+    gram = BM.HM.dsigmoid(a[:, None] - a[None, :]) * np.maximum(n[:, None] + n[None, :] - 2 * G @ G.T, 0.0)
+    assert (np.abs(gram - S64) <= 1e-8 * E).all() and (E > 0).all() and (E == E.T).all()
+    assert (adm == adm.T).all() and not adm.diagonal().any() and not adm[4].any()
+    val, j = BM.best(S64, adm)
+    assert j[4] == -1 and val[4] == 0.0 and (j[np.arange(k) != 4] >= 0).all()
+    for i in range(k):
+        if j[i] >= 0:
+            assert adm[i, j[i]] and val[i] == S64[i, j[i]] and val[i] == S64[i][adm[i]].max()
+    Gt = np.array([[0.0], [1.0], [-1.0], [1.0], [0.0]])               # column 0: |g_0 - g_j|^2 = 1 for j = 1, 2, 3
+    St, _, admt = BM.scores(np.zeros(5), Gt)
+    vt, jt = BM.best(St, admt)
+    assert vt.tolist() == [0.25, 1.0, 1.0, 1.0, 0.25] and jt.tolist() == [1, 2, 1, 2, 1]
+    one = BM.best(*BM.scores([1.0], [[2.0, 3.0]])[::2])
+    assert one[0].tolist() == [0.0] and one[1].tolist() == [-1]
+    bad = BM.scores([1.0, np.inf], [[0.0], [1.0]])
+    assert np.isnan(bad[0]).all() and np.isnan(BM.best(bad[0], bad[2])[0]).all() and (BM.best(bad[0], bad[2])[1] == -1).all()
+    assert np.isnan(BM.scores([1.0, 0.5], [[0.0], [np.nan]])[0]).all()
+    assert np.isnan(BM.scores([1.0, 0.5], [[0.0], [1.0]], None, [0.0, -np.inf])[0]).all()
+
+
+@pytest.mark.parametrize("m,d", [(40, 3), (65, 8)])
+def test_design_model_reaches_its_certificate(m, d):
+    """Within 300 iterations gap <= 1e-3 d; the weights are a probability measure, info is the measure's matrix, the
+    log-determinant did not decrease, the certificate is the brute-force KKT gap, and the uniform law is far from the
+    optimum (why the quantity is worth reporting)."""
+    rng = np.random.default_rng(5)
+    V = rng.standard_normal((m, d))
+    a = 1.5 * rng.standard_normal(m)
+    res = DM.design_row(a, V, None, None, 1e-3, 300)
+    eff = DM.uniform_efficiency(a, V, res)
+    print(f"m={m} d={d}: iters {res['iters']}, gap {res['gap']:.3e}, atoms {len(res['pairs'])}, rest {res['rest']:.3e}, "
+          f"uniform D-efficiency {eff:.3f}")
+    assert res["status"] == 0 and res["gap"] <= 1e-3 * d and res["iters"] <= 300
+    w = np.array(res["weights"])
+    assert (w > 0).all() and res["rest"] >= 0 and abs(w.sum() + res["rest"] - 1.0) <= 1e-12
+    S, D, adm, start = DM.pair_terms(a, V)
+    info = res["rest"] * start + sum(wq * S[p] * np.outer(D[p], D[p]) for p, wq in zip(res["pairs"], w))
+    np.testing.assert_allclose(res["info"], info, rtol=0, atol=1e-12 * np.abs(info).max())
+    assert all(i < j for i, j in res["pairs"]) and len(set(res["pairs"])) == len(res["pairs"])
+    assert res["logdet"] >= res["logdet_start"]
+    g, tr = DM.kkt(a, V, res["info"])
+    assert abs((g - tr) - res["gap"]) <= 1e-10 and abs(tr - d) <= 1e-9      # no prior: tr(P M) = d
+    assert 0.05 < eff < 0.5
+    assert len(res["pairs"]) <= d * (d + 1) // 2 + 8                        # a near-optimal design is sparse
+
+
+def test_design_model_edges():
+    rng = np.random.default_rng(9)
+    V = rng.standard_normal((12, 1))
+    a = rng.standard_normal(12)
+    res = DM.design_row(a, V, None, None, 1e-3, 5)                    # d = 1: all mass on the best single pair, at once
+    S, D, adm, _ = DM.pair_terms(a, V)
+    g = np.where(adm, S * D[:, :, 0] ** 2, -1.0)
+    i, j = np.unravel_index(g.argmax(), g.shape)
+    assert res["pairs"] == [(min(i, j), max(i, j))] and res["weights"] == [1.0] and res["rest"] == 0.0 and res["iters"] == 1
+    flat = np.concatenate([rng.standard_normal((12, 2)), np.zeros((12, 1))], axis=1)      # rank-deficient V
+    assert DM.design_row(a, flat)["status"] == 2 and np.isnan(DM.design_row(a, flat)["info"]).all()
+    ok = DM.design_row(a, flat, None, 0.1, 1e-3, 300)
+    assert ok["status"] == 0 and ok["gap"] <= 3e-3
+    w = LM.weights(rng.uniform(-3, 3, 12).astype(np.float32), margin=1.5)
+    res = DM.design_row(a, V, w, None, 1e-3, 50)
+    assert res["status"] == 0 and all(w[p] > 0 for p in res["pairs"])
+    assert DM.design_row(a, V, np.zeros((12, 12)))["status"] == 2     # a law without weight
+    stop = DM.design_row(a, rng.standard_normal((12, 3)), None, None, 1e-9, 2)
+    assert stop["status"] == 1 and stop["iters"] == 2 and stop["gap"] > 0
