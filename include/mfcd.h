@@ -1039,6 +1039,100 @@ int mfcd_triplet_rows(int side, int pass, int gauss_newton, const double *U, int
                       double *diag, double *loss, int32_t *status, void *workspace, size_t workspace_bytes,
                       void *stream);
 
+/*
+ * The statistics of mfcd_pair_stats_rows over ragged rows (no reference counterpart: the reference's Draft/ loads a
+ * ratings table, 20 to 737 ratings per user, and never scores a model on it; this is the exact BTL risk and the exact
+ * Kendall counts of a model on the ratings a user gave).  CSR layout: row r owns entries [row_off[r], row_off[r + 1]) of
+ * x [entries] (the observed values) and of a [entries] (the model's scores of the same entries), fp32; row_off is int64
+ * [rows + 1].  Everything is over the n0 = L (L - 1) / 2 unordered pairs among a row's L entries; no pair is formed in
+ * memory.
+ *   counts, sums, what, scale   per row, exactly as mfcd_pair_stats_rows defines them with m replaced by L: the same
+ *            comparison rules, the same per-pair functions (csrc/pairs_common.h), fp32 runs of at most 64 terms widened
+ *            to f64; a NaN in the row gives counts -1, any non-finite entry NaN sums.  A row of 0 or 1 entries gives zero
+ *            counts and +0 sums.
+ *   flags    bit 0, MFCD_RAGGED_SKIP_TIES: pairs with x_k == x_l (compared as values: -0.0 equals +0.0) leave the four
+ *            sums, as a ratings table's ties carry no preference; the row's support is then n0 - Tx.  The counts are
+ *            not affected.
+ *   status   [rows] int32: 0, or 2 for a row that fails validation; such a row has counts -1 and NaN sums.
+ * Tiles.  A row is cut into tiles of TILE = mfcd_pair_ragged_tile() = 256 entries.  The caller passes tile_off
+ * [rows + 1], the prefix sum of ceil(L_r / TILE), and its total n_tiles (the host cannot see row_off, and the entry has
+ * no host wait).  A first kernel validates every row before any entry of it is read: 0 <= row_off[r] <= row_off[r + 1]
+ * <= entries, L <= 1 048 576, tile_off[r + 1] - tile_off[r] = ceil(L / TILE) inside [0, n_tiles], and every tile of the
+ * row found by the binary search over tile_off.  Then one 256-thread workgroup per tile, one entry per thread, finds its
+ * row by that search and visits its tile's pairs with itself and with every later tile of the row, read from LDS as a
+ * broadcast; it writes one fixed-size partial, and a finishing kernel (one wave per row) adds a row's partials in a
+ * fixed order.  No address is formed from the offsets of a row that failed.  No floating-point atomics: two calls are
+ * bit-equal, what = 1 / what = 2 are bit-equal to the matching half of what = 3, and a row's outputs do not depend on
+ * the other rows of the call or on its position in it.
+ * Limits: rows >= 0 (0 = success, nothing launched), entries >= 0, n_tiles >= 0, what in {1, 2, 3} with its outputs
+ * present, flags in {0, 1}, scale finite (as a float too), a and x where entries > 0, row_off, tile_off and status;
+ * MFCD_EINVAL outside them and MFCD_EWORKSPACE for a short workspace, before anything touches the device.  workspace:
+ * mfcd_pair_ragged_workspace_bytes(rows, n_tiles), 80 bytes per tile (less than a twenty-fifth of the tiles' own
+ * entries; 0 = sizes out of range), 256-byte aligned; launches are cut to 2^20 workgroups.  No allocation and no host
+ * wait.
+ */
+#define MFCD_RAGGED_SKIP_TIES 1
+int mfcd_pair_ragged_tile(void);
+size_t mfcd_pair_ragged_workspace_bytes(int rows, int64_t n_tiles);
+int mfcd_pair_ragged_stats(const float *a, const float *x, int64_t entries, const int64_t *row_off, int rows,
+                           const int64_t *tile_off, int64_t n_tiles, double scale, int flags, int what, int64_t *counts,
+                           double *sums, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The gradient of the `risk` sum above with respect to the scores, on the same layout (no reference counterpart).  Entry
+ * e of g [entries] receives
+ *     g_e = sum over the other entries l of e's row of  w_el (sigmoid(a_e - a_l) - sigmoid(scale (x_e - x_l))),
+ * w_el = 1, or under MFCD_RAGGED_SKIP_TIES [x_e != x_l]; the arithmetic is mfcd_pair_grad_rows' (csrc/pairs_common.h),
+ * rounded to fp32 once.  The same validation kernel runs first; then one workgroup per tile visits its tile's pairs with
+ * EVERY tile of the row, so each thread owns its sum and stores it itself: no workspace, no finishing kernel, no atomic.
+ * A row that fails validation gets status 2 and none of its entries of g is written; a row with a non-finite entry gets
+ * an all-NaN slice (status 0) and the other rows are untouched; a row of one entry gets exactly +0.  Two calls are
+ * bit-equal and a row's slice does not depend on the other rows or on its position.
+ * Limits: those above, g where entries > 0, g neither a nor x; MFCD_EINVAL outside them, before anything touches the
+ * device.  No allocation and no host wait.
+ */
+int mfcd_pair_ragged_grad(const float *a, const float *x, int64_t entries, const int64_t *row_off, int rows,
+                          const int64_t *tile_off, int64_t n_tiles, double scale, int flags, float *g, int32_t *status,
+                          void *stream);
+
+/*
+ * The scores of a ratings table's entries (no reference counterpart): a_e = R[r] . C[idx_e] for the entries of row r,
+ * R [n_r][d] and C [n_c][d] fp32 factor tables, idx int32 [entries] (the item of an entry).  One 256-thread workgroup
+ * per row; fp32 products, each rounded, added in ascending column order.  Before any gather the row's offsets
+ * (0 <= row_off[r] <= row_off[r + 1] <= entries) and every idx of the row (in [0, n_c)) are checked: an invalid row gets
+ * status 2 and, where its offsets are valid, an all-NaN slice of a.
+ * Limits: 1 <= d <= 256, 0 <= rows <= n_r, n_c >= 1, entries >= 0, idx and a where entries > 0, a neither R nor C;
+ * MFCD_EINVAL outside them, before anything touches the device.  No allocation and no host wait.
+ */
+int mfcd_ragged_dot(const float *R, int n_r, const float *C, int n_c, int d, int64_t entries, const int64_t *row_off,
+                    int rows, const int32_t *idx, float *a, int32_t *status, void *stream);
+
+/*
+ * The carry of a per-entry coefficient to a factor table (no reference counterpart):
+ *     out[r] = sum over the entries e of row r of  coef[perm ? perm[e] : e] * T[idx_e],
+ * T [t_rows][d] fp32, out [rows][d] fp32.  With coef the gradient of mfcd_pair_ragged_grad it is called once by user
+ * (T = V, idx the entries' items) and once by item on the transposed layout (T = U, idx the entries' users, perm [entries]
+ * int64 mapping a transposed position to its CSR entry).
+ * Segments, as mfcd_triplet_rows: a row is cut into segments of S = mfcd_ragged_segment() = 256 entries, the caller
+ * passes seg_off [rows + 1], the prefix sum of ceil(L_r / S), and n_seg.  One wave per segment adds coef * T in f64
+ * (the product of two fp32 values is exact there) and writes the segment's d sums to the workspace; a second kernel
+ * gives every output element one owner, which adds the row's segments in ascending order and rounds to fp32 once: an
+ * item with a hundred thousand ratings is spread over hundreds of waves.  No floating-point atomics: two calls are
+ * bit-equal and a row depends only on its own entries.
+ * Validation, before any gather: the row's offsets and segment range (as above), every idx in [0, t_rows), every perm
+ * in [0, entries).  A row that fails gets status 2 and an all-NaN row of out.  A row without entries gets +0.
+ * Limits: 1 <= d <= 256, rows >= 0 (0 = success, nothing launched), 0 <= n_seg <= 2^31, t_rows >= 1, idx and coef where
+ * n_seg > 0, out neither T nor coef; MFCD_EINVAL outside them and MFCD_EWORKSPACE for a workspace below
+ * mfcd_ragged_gather_sum_workspace_bytes(rows, d, n_seg) (256 + d doubles and one int32 per segment, each region rounded
+ * up to 256; 0 = sizes out of range), before anything touches the device.  No allocation and no host wait.
+ */
+int mfcd_ragged_segment(void);
+size_t mfcd_ragged_gather_sum_workspace_bytes(int rows, int d, int64_t n_seg);
+int mfcd_ragged_gather_sum(const float *T, int t_rows, int d, int64_t entries, const int64_t *row_off, int rows,
+                           const int32_t *idx, const float *coef, const int64_t *perm, const int64_t *seg_off,
+                           int64_t n_seg, float *out, int32_t *status, void *workspace, size_t workspace_bytes,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,17 @@ __device__ __forceinline__ unsigned sortable_key(float f)
 // inf or NaN: the exponent bits are all set
 __device__ __forceinline__ bool is_nonfinite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
+// The row that holds segment (or tile) s: the largest r with seg_off[r] <= s.  Reads seg_off[0 .. rows] only, whatever it holds.
+__device__ __forceinline__ int trip_find_row(const int64_t *__restrict__ seg_off, int rows, int64_t s)
+{
+    int lo = 0, hi = rows;            // seg_off[lo] <= s is assumed, the answer lies in [lo, hi)
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (seg_off[mid] <= s) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 // acc[reg] of a 32x32 fp32 MFMA tile:  row = (reg&3) + 8*(reg>>2) + 4*half,  col = lane&31   (gfx950 C/D map)
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ int tile_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }

@@ -1,5 +1,6 @@
-// What the pair kernels of pairs.hip and pair_info.hip share: the limits of a call, the pair law's kernel arguments, its
-// weight, its argument check and the dispatch over its three flags.
+// What the pair kernels of pairs.hip, pair_info.hip, pair_best.hip and pair_ragged.hip share: the limits of a call, the
+// pair law's kernel arguments, its weight, its argument check and the dispatch over its three flags, and the per-pair
+// arithmetic of the statistics and gradient kernels (DESIGN sections 3.10, 3.13).
 #pragma once
 #include <cmath>
 
@@ -74,6 +75,51 @@ void law_dispatch(bool hw, bool hm, bool hl, Args... args)
     case 6: F<false, true, true>::go(args...); break;
     default: F<true, true, true>::go(args...); break;
     }
+}
+
+// ---- the per-pair arithmetic of the statistics and gradient kernels (pairs.hip, pair_ragged.hip) ----
+// One pair.  f: the run's fp32 accumulators — log2(1 + e) and the linear part of the two risks apart (ln 2 is applied
+// once, in f64), exp_acc, bayes_acc.
+template <int WHAT, bool MASKED>
+__device__ __forceinline__ void pair_term(float ai, float xi, float aj, float xj, bool valid, float scale,
+                                          unsigned (&cnt)[4], float (&f)[6])
+{
+    const bool la = ai < aj, ga = ai > aj, lx = xi < xj, gx = xi > xj;
+    const bool v = !MASKED || valid;
+    if (WHAT & 1) {                                    // comparison masks combine on the scalar unit
+        cnt[0] += (unsigned)(v && ((la && lx) || (ga && gx)));
+        cnt[1] += (unsigned)(v && ((la && gx) || (ga && lx)));
+        cnt[2] += (unsigned)(v && (la || ga));         // strictly ordered in a: Ta = n0 - this, in the finishing kernel
+        cnt[3] += (unsigned)(v && (lx || gx));         // (a row with a NaN is voided there)
+    }
+    if (WHAT & 2) {
+        const float da = ai - aj, t = scale * (xi - xj);
+        const float ada = v ? fabsf(da) : 0.0f, at = v ? fabsf(t) : 0.0f;
+        const float ea = __builtin_amdgcn_exp2f(-1.4426950408889634f * ada);       // exp(-|da|): v_exp_f32
+        const float et = __builtin_amdgcn_exp2f(-1.4426950408889634f * at);
+        const float l2a = __builtin_amdgcn_logf(1.0f + ea), l2t = __builtin_amdgcn_logf(1.0f + et);   // v_log_f32: log2
+        const float qhi = __builtin_amdgcn_rcpf(1.0f + et), qlo = et * qhi;       // sigmoid(|t|), sigmoid(-|t|)
+        // the scores order the pair against the side the label law leans to: then 1 - q (for da > 0) or q (da < 0) is
+        // q_hi and the pair is right with probability q_lo; otherwise the other way round
+        const bool against = ga != (t >= 0.0f);
+        const float miss = against ? qhi : qlo, hit = against ? qlo : qhi;
+        const float eacc = (ga || la) ? hit : 0.5f;
+        f[0] += v ? l2a : 0.0f;
+        f[1] = fmaf(ada, miss, f[1]);
+        f[2] += v ? l2t : 0.0f;
+        f[3] = fmaf(at, qlo, f[3]);
+        f[4] += v ? eacc : 0.0f;
+        f[5] += v ? qhi : 0.0f;
+    }
+}
+
+// sigmoid(v) from exp of a non-positive argument only: sigmoid(|v|) = 1 / (1 + e), sigmoid(-|v|) = e / (1 + e), selected
+// by the sign, never formed as 1 - sigmoid.  v = +-0 gives the same value for either sign.
+__device__ __forceinline__ float pair_sigmoid(float v)
+{
+    const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * fabsf(v));       // exp(-|v|) <= 1: v_exp_f32
+    const float hi = __builtin_amdgcn_rcpf(1.0f + e);
+    return v >= 0.0f ? hi : e * hi;
 }
 
 }  // namespace

@@ -103,17 +103,6 @@ struct TripGather<1> {
     static __device__ __forceinline__ const double *own_direction(const TripArgs &a) { return a.Q; }
 };
 
-// The row that holds segment s: the largest r with seg_off[r] <= s.  Reads seg_off[0 .. rows] only, whatever it holds.
-__device__ __forceinline__ int trip_find_row(const int64_t *__restrict__ seg_off, int rows, int64_t s)
-{
-    int lo = 0, hi = rows;            // seg_off[lo] <= s is assumed, the answer lies in [lo, hi)
-    while (hi - lo > 1) {
-        const int mid = lo + (hi - lo) / 2;
-        if (seg_off[mid] <= s) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // One wave per segment.  L lanes per record, E elements per lane (column g + e L of lane g of the group).
 template <int SIDE, int PASS, int L, int E>
 __global__ __launch_bounds__(kTripWaves * MFCD_WAVE) void triplet_rows_segments(const TripArgs a)

@@ -12,9 +12,11 @@
 `newton`   both tables at once: gradient and Hessian-vector product of the sampled objective (mfcd_triplet_rows) and a
            trust-region Newton-CG fit on them.
 `population` the exact block steps of the ridge-regularised population risk: Newton-CG on mfcd_pair_hvp_rows.
+`ratings`  the all-pairs risk, gradient and metrics on observed ratings: ragged rows (mfcd_pair_ragged_stats, _grad).
 `design`   the D-optimal comparison design of every user: pairwise Frank-Wolfe on the arg-max of mfcd_pair_best_rows.
 """
-from . import _lib, alternating, batching, design, engine, foldin, metrics, newton, pairs, population, topk  # noqa: F401
+from . import (_lib, alternating, batching, design, engine, foldin, metrics, newton, pairs, population, ratings,  # noqa: F401
+               topk)
 
 __all__ = ["_lib", "alternating", "batching", "design", "engine", "foldin", "metrics", "newton", "pairs", "population",
-           "topk"]
+           "ratings", "topk"]

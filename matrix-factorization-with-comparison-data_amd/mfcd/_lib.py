@@ -125,6 +125,14 @@ SIGNATURES = {
     "mfcd_triplet_rows_workspace_bytes": (_sz, [_i32, _i32, _i64]),
     "mfcd_triplet_rows": (_i32, [_i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _dbl,
                                  _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mfcd_pair_ragged_tile": (_i32, []),
+    "mfcd_pair_ragged_workspace_bytes": (_sz, [_i32, _i64]),
+    "mfcd_pair_ragged_stats": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i64, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mfcd_pair_ragged_grad": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i64, _dbl, _i32, _vp, _vp, _vp]),
+    "mfcd_ragged_dot": (_i32, [_vp, _i32, _vp, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "mfcd_ragged_segment": (_i32, []),
+    "mfcd_ragged_gather_sum_workspace_bytes": (_sz, [_i32, _i32, _i64]),
+    "mfcd_ragged_gather_sum": (_i32, [_vp, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
 }
 
 TUNE_KEYS = {"resident_lookahead": 3, "resident_spin_limit": 5, "uvt_target_wgs": 9, "uvt_min_stages": 10,

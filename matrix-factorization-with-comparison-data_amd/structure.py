@@ -28,6 +28,7 @@ from mfcd import metrics as _metrics
 from mfcd import newton as _newton
 from mfcd import pairs as _pairs
 from mfcd import population as _population
+from mfcd import ratings as _ratings
 from mfcd import sampling as _sampling
 from mfcd import topk as _topk
 
@@ -279,6 +280,93 @@ def train_model_law(model, X, s, optimizer, device, law, num_steps=1000, log_eve
         out = (at, torch.stack(seen).double().cpu().tolist() if seen else [])
     model.eval()
     return out
+
+
+def observe_ratings(X, p, levels=None, seed=0):
+    """Extension (not in the reference): a ratings table from a dense X — every entry is kept with probability p, drawn
+    from a private CPU torch.Generator(seed) (the global torch and numpy RNG states are not touched, so the host
+    pipeline's draw order stays what it is).  levels=k replaces the kept values by the ratings 1..k, cut at the global
+    k-quantiles of the kept values.  Returns an mfcd.ratings.RatingsData on X's device: what `ratings_risk`,
+    `train_model_ratings` and `compute_ratings_metrics` take, to ask how reconstruction degrades with p and k.  Not part
+    of the result dict / .pkl layout."""
+    if not torch.is_tensor(X) or X.dim() != 2:
+        raise ValueError("observe_ratings takes a dense [n, m] tensor")
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError("p must lie in [0, 1]")
+    gen = torch.Generator(device="cpu").manual_seed(int(seed))
+    keep = torch.rand(X.shape, generator=gen) < float(p)
+    users, items = keep.nonzero(as_tuple=True)
+    values = X.detach().cpu().float()[keep].numpy()
+    if levels is not None:
+        k = int(levels)
+        if k < 1:
+            raise ValueError("levels must be >= 1")
+        edges = np.quantile(values.astype(np.float64), np.arange(1, k) / k) if values.size else np.zeros(k - 1)
+        values = 1.0 + np.searchsorted(edges, values.astype(np.float64), side="right")
+    return _ratings.RatingsData(users.numpy(), items.numpy(), values, X.shape[0], X.shape[1]).to(X.device)
+
+
+def load_ratings(path, sep=None):
+    """Extension (not in the reference): reads a text file of `user item value [ignored columns]` lines (sep=None: any
+    white space, the layout of MovieLens' u.data) with numpy; the user and item ids are mapped to 0..n-1 and 0..m-1 in
+    the order of their sorted unique values.  Returns (data, user_ids, item_ids): an mfcd.ratings.RatingsData on the CPU
+    (`.to(device)` moves it) and the id of every row and column.  Not part of the result dict / .pkl layout."""
+    table = np.loadtxt(path, delimiter=sep, usecols=(0, 1, 2), ndmin=2, dtype=np.float64)
+    user_ids, users = np.unique(table[:, 0], return_inverse=True)
+    item_ids, items = np.unique(table[:, 1], return_inverse=True)
+    if (user_ids == np.round(user_ids)).all() and (item_ids == np.round(item_ids)).all():
+        user_ids, item_ids = user_ids.astype(np.int64), item_ids.astype(np.int64)
+    data = _ratings.RatingsData(users.reshape(-1), items.reshape(-1), table[:, 2], user_ids.size, item_ids.size)
+    return data, user_ids, item_ids
+
+
+def ratings_risk(model, data, s=1.0, skip_ties=False):
+    """Extension (not in the reference): the exact BTL risk of the model on a ratings table as a differentiable scalar —
+    over every user and ALL pairs of items that user rated, the BCE of p = sigmoid(a_k - a_l) under the label law
+    q = sigmoid(s (x_k - x_l)), divided by the number of such pairs of all users (skip_ties: pairs with equal ratings
+    carry no preference and stay out).  Returns a 0-dim fp32 tensor on the model's device; `.backward()` fills
+    `model.U.grad` / `model.V.grad` (include/mfcd.h mfcd_pair_ragged_grad, mfcd_ragged_gather_sum).  fp32 models only;
+    data: an mfcd.ratings.RatingsData on the model's device.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _ratings.ratings_risk(model.U, model.V, data, s, skip_ties)
+
+
+def train_model_ratings(model, data, s, optimizer, device, num_steps=1000, log_every=100, skip_ties=False):
+    """Extension (not in the reference): `train_model_population` on `ratings_risk(model, data, s)` — full-batch optimiser
+    steps on the exact risk of the observed ratings.  Returns (steps, risks) as `train_model_population` does.
+    torch.optim.Adam takes the fused loop (mfcd.ratings.fit_ratings), any other optimiser zero_grad / ratings_risk /
+    backward / step.  Not part of the result dict / .pkl layout."""
+    _need_gpu(device)
+    model.train()
+    if _engine.fused_step_applies(model, optimizer):
+        out = _ratings.fit_ratings(_engine.AdamBinding(model, optimizer), data, s, num_steps, log_every, skip_ties)
+    else:
+        at, seen = [], []
+        for t in range(int(num_steps)):
+            optimizer.zero_grad()
+            loss = ratings_risk(model, data, s, skip_ties)
+            loss.backward()
+            optimizer.step()
+            if log_every > 0 and t % log_every == 0:
+                at.append(t)
+                seen.append(loss.detach())
+        if log_every > 0:
+            with torch.no_grad():
+                at.append(int(num_steps))
+                seen.append(ratings_risk(model, data, s, skip_ties))
+        out = (at, torch.stack(seen).double().cpu().tolist() if seen else [])
+    model.eval()
+    return out
+
+
+def compute_ratings_metrics(model, data, s=1.0, skip_ties=False):
+    """Extension (not in the reference): `compute_pairwise_metrics` on a ratings table, typically a held-out split
+    (`data.split`): the same keys and `_per_user` arrays, every user's values over the pairs among the items that user
+    rated (include/mfcd.h mfcd_pair_ragged_stats); a user without a pair is NaN and stays out of the means.  skip_ties:
+    the likelihood and accuracy keys over the pairs with different ratings only.  Not part of the result dict / .pkl
+    layout."""
+    _need_gpu(model.U.device)
+    return _ratings.ratings_metrics(model.U.data, model.V.data, data, s, skip_ties)
 
 
 def population_hvp(model, X, dU, dV, s=1.0, law=None, users=None, row_block=2048, gauss_newton=False):
