@@ -1096,6 +1096,30 @@ int mfcd_pair_ragged_grad(const float *a, const float *x, int64_t entries, const
                           void *stream);
 
 /*
+ * The Hessian of the `risk` sum above with respect to the scores, applied to a vector y [entries], on the same layout
+ * (no reference counterpart): mfcd_pair_hvp_rows over ragged rows.  Entry e receives
+ *     q_e   = sum over the other entries l of e's row of  w_el s_el (y_e - y_l),   s_el = sigmoid'(a_e - a_l),
+ *     deg_e = sum over the other entries l of e's row of  w_el s_el                (deg may be NULL: not computed),
+ * w_el = 1, or under MFCD_RAGGED_SKIP_TIES [x_e != x_l]: the row Laplacian L(a) applied to y, and its diagonal.  Neither
+ * the scale nor the label law enters a second derivative, so there is no `scale`; x is read under the skip flag only (it
+ * may be NULL without it).  The arithmetic is mfcd_pair_hvp_rows' (csrc/pairs_common.h: pair_curvature, the difference
+ * of y formed first, one fma), in fp32 runs of at most 64 columns counted from the row's start, widened to f64 and
+ * rounded to fp32 once: on rows of one length q and deg are bit-equal to mfcd_pair_hvp_rows'.  The decomposition is
+ * mfcd_pair_ragged_grad's: the same validation kernel, one workgroup per tile against EVERY tile of the row, no
+ * workspace, no finishing kernel, no atomic.  An entry's own column adds exactly 0 to q and is masked out of deg.
+ * A row that fails validation gets status 2 and none of its entries of q or deg is written; a row with a non-finite a or
+ * y (or x under the skip flag) gets all-NaN slices (status 0) and the other rows are untouched; a row of one entry and
+ * a y constant over the row give exactly +0 in q.  Two calls are bit-equal, q does not depend on whether deg is asked
+ * for, and a row's slices do not depend on the other rows or on its position.
+ * Limits: those of mfcd_pair_ragged_grad without x and scale; a, y, q and under the skip flag x where entries > 0; q
+ * and deg distinct from the inputs and from each other; MFCD_EINVAL outside them, before anything touches the device.
+ * No allocation and no host wait.
+ */
+int mfcd_pair_ragged_hvp(const float *a, const float *x, const float *y, int64_t entries, const int64_t *row_off, int rows,
+                         const int64_t *tile_off, int64_t n_tiles, int flags, float *q, float *deg, int32_t *status,
+                         void *stream);
+
+/*
  * The scores of a ratings table's entries (no reference counterpart): a_e = R[r] . C[idx_e] for the entries of row r,
  * R [n_r][d] and C [n_c][d] fp32 factor tables, idx int32 [entries] (the item of an entry).  One 256-thread workgroup
  * per row; fp32 products, each rounded, added in ascending column order.  Before any gather the row's offsets

@@ -1,5 +1,5 @@
-// pair_ragged.hip — the all-pairs statistics and gradient of pairs.hip over ragged rows (include/mfcd.h:
-// mfcd_pair_ragged_stats, mfcd_pair_ragged_grad).  A row is a CSR slice: entries [row_off[r], row_off[r+1])
+// pair_ragged.hip — the all-pairs statistics, gradient and Hessian-vector product of pairs.hip over ragged rows
+// (include/mfcd.h: mfcd_pair_ragged_stats, mfcd_pair_ragged_grad, mfcd_pair_ragged_hvp).  A row is a CSR slice: entries [row_off[r], row_off[r+1])
 // of the value array x and of the score array a; all L (L - 1) / 2 pairs among a row's entries are visited, per row, and
 // no pair is ever materialised.  The per-pair arithmetic is pairs_common.h's, the functions pairs.hip runs.
 //
@@ -11,6 +11,7 @@
 //   statistics  tile I against the tiles J >= I (each unordered pair once; the diagonal tile masked to i < j); one
 //               fixed-size partial per tile; a one-wave finishing kernel per row adds the row's partials in order.
 //   gradient    tile I against EVERY tile J, so a thread owns its sum and stores it itself (no finishing kernel).
+//   Hessian     times a vector y, and its diagonal: the gradient's decomposition, (a, y) in LDS, x beside it under SKIP.
 // A first kernel (one wave per row) validates every row before any entry of it is read and writes status[r]: 0, or 2 for
 //   not (0 <= row_off[r] <= row_off[r+1] <= entries),  a length above 2^20,  a tile range that is not
 //   ceil(L / 256) tiles inside [0, n_tiles),  or a tile of the range that the search does not lead back to the row.
@@ -259,6 +260,86 @@ __global__ __launch_bounds__(kRagTile) void ragged_grad_kernel(const RagArgs g, 
     if (p < w.len) G[w.b + p] = bad ? __uint_as_float(0x7fc00000u) : (float)acc;   // rounded to fp32 once
 }
 
+// q_e = sum over the other entries l of e's row of w_el s_el (y_e - y_l), s_el = sigmoid'(a_e - a_l), and with DEG
+// deg_e = sum over l != e of w_el s_el: the row Laplacian L(a) of the ragged risk applied to y, and its diagonal.  The
+// decomposition is ragged_grad_kernel's, the pair is pairs.hip's hvp_run's (pair_curvature, the difference of y formed
+// first, then one fma).  Columns [0, jn) of the LDS tile against this thread's entry.  OWN: the tile is the thread's own;
+// its own column (column tid) adds exactly 0 to q but 1/4 to deg, so with DEG s is zeroed there — a compare the other
+// tiles do not carry.  SKIP: a pair tied in x has w = 0.
+template <bool DEG, bool SKIP, bool OWN>
+__device__ __forceinline__ void ragged_hvp_run(const float2 *tile, const float *tx, int jn, float ai, float yi, float xi,
+                                               int tid, double &acc, double &dacc)
+{
+    for (int jb = 0; jb < jn; jb += kRagFlush) {
+        const int je = jb + kRagFlush < jn ? jb + kRagFlush : jn;
+        float f = 0.0f, d = 0.0f;                      // at most kRagFlush terms each
+#pragma unroll 4
+        for (int j = jb; j < je; ++j) {
+            const float2 v = tile[j];
+            float s = pair_curvature(ai - v.x);
+            if (SKIP) {
+                const float xj = tx[j];
+                s = (xi < xj || xi > xj) ? s : 0.0f;
+            }
+            if (DEG && OWN) s = j == tid ? 0.0f : s;
+            f = fmaf(s, yi - v.y, f);
+            if (DEG) d += s;
+        }
+        acc += (double)f;
+        if (DEG) dacc += (double)d;
+    }
+}
+
+template <bool DEG, bool SKIP>
+__global__ __launch_bounds__(kRagTile) void ragged_hvp_kernel(const RagArgs g, const float *__restrict__ Y, int64_t t0,
+                                                              float *__restrict__ Q, float *__restrict__ Dg)
+{
+    __shared__ float2 tile[kRagTile];                  // (a, y)
+    __shared__ float tx[SKIP ? kRagTile : 1];
+    const int tid = threadIdx.x;
+    RagTile w;
+    if (!ragged_tile(g, t0 + blockIdx.x, &w)) return;  // uniform over the workgroup
+    const float *a = g.a + w.b, *y = Y + w.b, *x = SKIP ? g.x + w.b : nullptr;
+
+    const int p = w.I * kRagTile + tid;
+    const bool in = p < w.len;                         // past the end: computed, never stored
+    const float ai = in ? a[p] : 0.0f, yi = in ? y[p] : 0.0f, xi = SKIP && in ? x[p] : 0.0f;
+    const bool wave_live = w.I * kRagTile + (tid & ~63) < w.len;           // as in the statistics kernel
+    int bad = 0;                                       // the workgroup stages the whole row: it sees every entry
+    double acc = 0.0, dacc = 0.0;
+    for (int J = 0; J < w.T; ++J) {
+        __syncthreads();                               // the previous tile's readers are done
+        const int pj = J * kRagTile + tid;
+        const bool inj = pj < w.len;
+        const float2 v = inj ? make_float2(a[pj], y[pj]) : make_float2(0.0f, 0.0f);
+        bad |= (int)(is_nonfinite_bits(v.x) || is_nonfinite_bits(v.y));
+        tile[tid] = v;
+        if (SKIP) {
+            const float vx = inj ? x[pj] : 0.0f;
+            bad |= (int)is_nonfinite_bits(vx);
+            tx[tid] = vx;
+        }
+        __syncthreads();
+        const int jn = w.len - J * kRagTile < kRagTile ? w.len - J * kRagTile : kRagTile;   // pad columns stay out
+        if (!wave_live) continue;                      // the wave only helps to stage the tiles
+        if (J != w.I) ragged_hvp_run<DEG, SKIP, false>(tile, tx, jn, ai, yi, xi, tid, acc, dacc);
+        else ragged_hvp_run<DEG, SKIP, true>(tile, tx, jn, ai, yi, xi, tid, acc, dacc);
+    }
+    bad = __syncthreads_or(bad);
+    if (in) {                                          // rounded to fp32 once
+        Q[w.b + p] = bad ? __uint_as_float(0x7fc00000u) : (float)acc;
+        if (DEG) Dg[w.b + p] = bad ? __uint_as_float(0x7fc00000u) : (float)dacc;
+    }
+}
+
+template <bool DEG>
+void ragged_hvp_launch(bool skip, unsigned blocks, hipStream_t st, const RagArgs &g, const float *y, int64_t t0, float *q,
+                       float *deg)
+{
+    if (skip) hipLaunchKernelGGL((ragged_hvp_kernel<DEG, true>), dim3(blocks), dim3(kRagTile), 0, st, g, y, t0, q, deg);
+    else hipLaunchKernelGGL((ragged_hvp_kernel<DEG, false>), dim3(blocks), dim3(kRagTile), 0, st, g, y, t0, q, deg);
+}
+
 template <int WHAT>
 void ragged_tiles_launch(bool skip, unsigned blocks, hipStream_t st, const RagArgs &g, int64_t t0, RagPartial *part)
 {
@@ -343,6 +424,31 @@ extern "C" int mfcd_pair_ragged_grad(const float *a, const float *x, int64_t ent
         const unsigned nb = (unsigned)(n_tiles - t0 < kPairMaxBlocks ? n_tiles - t0 : kPairMaxBlocks);
         if (skip) hipLaunchKernelGGL(ragged_grad_kernel<true>, dim3(nb), dim3(kRagTile), 0, st, g, t0, g_out);
         else hipLaunchKernelGGL(ragged_grad_kernel<false>, dim3(nb), dim3(kRagTile), 0, st, g, t0, g_out);
+        MFCD_HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int mfcd_pair_ragged_hvp(const float *a, const float *x, const float *y, int64_t entries, const int64_t *row_off,
+                                    int rows, const int64_t *tile_off, int64_t n_tiles, int flags, float *q, float *deg,
+                                    int32_t *status, void *stream)
+{
+    if (rows < 0 || entries < 0 || n_tiles < 0 || !row_off || !tile_off || !status) return MFCD_EINVAL;
+    if (entries > 0 && (!a || !y || !q)) return MFCD_EINVAL;
+    if (flags & ~MFCD_RAGGED_SKIP_TIES) return MFCD_EINVAL;
+    const bool skip = (flags & MFCD_RAGGED_SKIP_TIES) != 0;
+    if (skip && entries > 0 && !x) return MFCD_EINVAL;   // x is read under the skip flag only
+    if (q && (q == a || q == y || q == x || q == deg)) return MFCD_EINVAL;
+    if (deg && (deg == a || deg == y || deg == x)) return MFCD_EINVAL;
+    if (n_tiles > (int64_t)1 << 40) return MFCD_EINVAL;
+    if (rows == 0) return 0;
+    const RagArgs g{a, x, entries, row_off, tile_off, rows, n_tiles, 0.0f, status};   // no scale in a second derivative
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = ragged_status_launch(g, st)) return rc;
+    for (int64_t t0 = 0; t0 < n_tiles; t0 += kPairMaxBlocks) {
+        const unsigned nb = (unsigned)(n_tiles - t0 < kPairMaxBlocks ? n_tiles - t0 : kPairMaxBlocks);
+        if (deg) ragged_hvp_launch<true>(skip, nb, st, g, y, t0, q, deg);
+        else ragged_hvp_launch<false>(skip, nb, st, g, y, t0, q, deg);
         MFCD_HIP_TRY(hipGetLastError());
     }
     return 0;

@@ -588,9 +588,7 @@ __device__ __forceinline__ void hvp_run(const float2 *tile, const float *tx, con
             const int lj = HL ? lab[j] : 0;
 #pragma unroll
             for (int k = 0; k < kPairIpt; ++k) {
-                const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * fabsf(ai[k] - v.x));   // exp(-|da|) <= 1
-                const float h = __builtin_amdgcn_rcpf(1.0f + e);
-                float s = e * h * h;
+                float s = pair_curvature(ai[k] - v.x);
                 if (HW || HM || HL)
                     s = __fmul_rn(law_weight<HW, HM, HL>(HM ? xi[k] - xj : 0.0f, ali[k], bei[k], li[k], alj, bej, lj, mg), s);
                 if (DEG && k == KMASK) s = j - j0 == tid ? 0.0f : s;

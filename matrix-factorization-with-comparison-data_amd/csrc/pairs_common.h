@@ -1,6 +1,6 @@
 // What the pair kernels of pairs.hip, pair_info.hip, pair_best.hip and pair_ragged.hip share: the limits of a call, the
 // pair law's kernel arguments, its weight, its argument check and the dispatch over its three flags, and the per-pair
-// arithmetic of the statistics and gradient kernels (DESIGN sections 3.10, 3.13).
+// arithmetic of the statistics, gradient and Hessian-vector kernels (DESIGN sections 3.10, 3.13, 3.14).
 #pragma once
 #include <cmath>
 
@@ -120,6 +120,15 @@ __device__ __forceinline__ float pair_sigmoid(float v)
     const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * fabsf(v));       // exp(-|v|) <= 1: v_exp_f32
     const float hi = __builtin_amdgcn_rcpf(1.0f + e);
     return v >= 0.0f ? hi : e * hi;
+}
+
+// sigmoid'(da) = e h h with e = exp(-|da|), h = 1 / (1 + e): symmetric in the sign of da, so nothing is selected and
+// nothing cancels; one exp and one reciprocal.  The Hessian-vector kernels' pair (pairs.hip, pair_ragged.hip).
+__device__ __forceinline__ float pair_curvature(float da)
+{
+    const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * fabsf(da));   // exp(-|da|) <= 1
+    const float h = __builtin_amdgcn_rcpf(1.0f + e);
+    return e * h * h;
 }
 
 }  // namespace

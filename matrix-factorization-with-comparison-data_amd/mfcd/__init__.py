@@ -13,10 +13,11 @@
            trust-region Newton-CG fit on them.
 `population` the exact block steps of the ridge-regularised population risk: Newton-CG on mfcd_pair_hvp_rows.
 `ratings`  the all-pairs risk, gradient and metrics on observed ratings: ragged rows (mfcd_pair_ragged_stats, _grad).
+`ratings_exact` the exact block steps of the ridge-regularised ratings risk: Newton-CG on mfcd_pair_ragged_hvp.
 `design`   the D-optimal comparison design of every user: pairwise Frank-Wolfe on the arg-max of mfcd_pair_best_rows.
 """
 from . import (_lib, alternating, batching, design, engine, foldin, metrics, newton, pairs, population, ratings,  # noqa: F401
-               topk)
+               ratings_exact, topk)
 
 __all__ = ["_lib", "alternating", "batching", "design", "engine", "foldin", "metrics", "newton", "pairs", "population",
-           "ratings", "topk"]
+           "ratings", "ratings_exact", "topk"]

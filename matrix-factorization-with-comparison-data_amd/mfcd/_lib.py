@@ -129,6 +129,7 @@ SIGNATURES = {
     "mfcd_pair_ragged_workspace_bytes": (_sz, [_i32, _i64]),
     "mfcd_pair_ragged_stats": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i64, _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mfcd_pair_ragged_grad": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _i64, _dbl, _i32, _vp, _vp, _vp]),
+    "mfcd_pair_ragged_hvp": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "mfcd_ragged_dot": (_i32, [_vp, _i32, _vp, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "mfcd_ragged_segment": (_i32, []),
     "mfcd_ragged_gather_sum_workspace_bytes": (_sz, [_i32, _i32, _i64]),

@@ -6,7 +6,9 @@ the L_u (L_u - 1) / 2 pairs among the items that user rated, exactly and without
 and segment offsets the entries need; every host read happens there, once per dataset.  `ragged_scores`,
 `pair_ragged_stats`, `pair_ragged_grad` and `ragged_gather_sum` are the kernel calls.  `ratings_risk` is the exact BTL
 risk of a model on the table as a differentiable scalar, `ratings_metrics` the exact held-out metrics, `fit_ratings` the
-fused loop of scores, gradient, two gather-sums and one dense Adam step.  There is no CPU form of any of it."""
+fused loop of scores, gradient, two gather-sums and one dense Adam step.  `pair_ragged_hvp` (mfcd_pair_ragged_hvp) is the
+curvature of the same risk in score space and `ratings_hvp` its product with a direction of both tables; the exact block
+steps built on it are mfcd/ratings_exact.py's.  There is no CPU form of any of it."""
 import numpy as np
 import torch
 
@@ -41,7 +43,8 @@ class RatingsData:
                                             by-(item, user) order is CSR entry col_perm[p], of user col_user[p]
       col_seg_off int64 [m + 1], col_n_seg  the items' segments
     Python ints: entries, pairs = sum of L_u (L_u - 1) / 2, tied_pairs = those of them with equal values (-0.0 equals
-    +0.0).  lengths: the users' L_u as a host int64 array."""
+    +0.0).  lengths: the users' L_u as a host int64 array; user_pairs, user_tied_pairs: the two counts per user, host
+    int64 [n] (`user_support`)."""
 
     _TENSORS = ("row_off", "item", "user", "value", "tile_off", "seg_off", "col_off", "col_user", "col_perm", "col_seg_off")
 
@@ -77,6 +80,12 @@ class RatingsData:
         start = np.flatnonzero(np.concatenate(([True], (su[1:] != su[:-1]) | (sv[1:] != sv[:-1])))) if u.size else su
         runs = np.diff(np.concatenate((start, [u.size]))).astype(np.int64)
         self.tied_pairs = int((runs * (runs - 1) // 2).sum())
+        self.user_pairs = lengths * (lengths - 1) // 2
+        self.user_tied_pairs = np.bincount(su[start], weights=runs * (runs - 1) // 2, minlength=n).astype(np.int64)
+
+    def user_support(self, skip_ties=False):
+        """`support` per user: host int64 [n].  A user whose support is 0 has a risk that is identically 0."""
+        return self.user_pairs - self.user_tied_pairs if skip_ties else self.user_pairs
 
     @property
     def device(self):
@@ -184,6 +193,27 @@ def pair_ragged_grad(a, data, scale=1.0, skip_ties=False):
     return g, status
 
 
+def pair_ragged_hvp(a, y, data, skip_ties=False, deg=False):
+    """Scores a and a score-space vector y, fp32 [entries] on the GPU → (q fp32 [entries], status int32 [n]), or with
+    deg=True (q, deg, status): the Hessian of the users' `risk` sums of `pair_ragged_stats` with respect to the scores,
+    applied to y, and its diagonal — every user's row Laplacian, `pairs.pair_hvp_rows` over the user's own entries
+    (mfcd_pair_ragged_hvp).  Neither the scale nor the values enter, except that skip_ties drops the pairs with equal
+    values.  Deterministic."""
+    a = _need(a, torch.float32, "pair_ragged_hvp", "the scores")
+    y = _need(y, torch.float32, "pair_ragged_hvp", "the vector")
+    _need_data(data, "pair_ragged_hvp")
+    if a.numel() != data.entries or y.numel() != data.entries:
+        raise ValueError(f"{a.numel()} scores and a vector of {y.numel()} for {data.entries} ratings")
+    q = torch.empty_like(a)
+    d = torch.empty_like(a) if deg else None
+    status = torch.zeros(data.n, dtype=torch.int32, device=a.device)
+    _lib.check(_lib.load().mfcd_pair_ragged_hvp(_lib.ptr(a), _lib.ptr(data.value), _lib.ptr(y), data.entries,
+                                                _lib.ptr(data.row_off), data.n, _lib.ptr(data.tile_off), data.n_tiles,
+                                                int(bool(skip_ties)), _lib.ptr(q), _lib.ptr(d), _lib.ptr(status),
+                                                _lib.stream_ptr(a.device)))
+    return (q, d, status) if deg else (q, status)
+
+
 def ragged_gather_sum(coef, data, table, side):
     """coef fp32 [entries] (in CSR order) and an fp32 GPU table → (out fp32, status int32) (mfcd_ragged_gather_sum):
     side="user": table is V [m, d], out[u] = sum over u's entries of coef_e V[item_e], [n, d];
@@ -253,6 +283,31 @@ def ratings_risk(U, V, data, s=1.0, skip_ties=False):
         _need(t, torch.float32, "the ratings risk", name)
     _need_data(data, "the ratings risk")
     return _RatingsRisk.apply(U, V, data, float(s), bool(skip_ties), _support(data, skip_ties))
+
+
+def ratings_hvp(U, V, dU, dV, data, s=1.0, skip_ties=False, gauss_newton=False):
+    """The Hessian of `ratings_risk` with respect to both tables, applied to a direction (dU, dV) of their shapes → (HU,
+    HV) fp32, as `pairs.population_hvp` on a ratings table: with dA = dU[user] . V[item] + U[user] . dV[item] over the
+    entries, q = `pair_ragged_hvp`(a, dA), g = `pair_ragged_grad`(a) and c = 1 / data.support(skip_ties),
+        HU = c [gather_sum(q, V) + gather_sum(g, dV)] by user,   HV = c [gather_sum(q, U) + gather_sum(g, dU)] by item.
+    gauss_newton=True drops the two g terms: the positive semi-definite part.  fp32 GPU tensors; nothing is modified."""
+    tables = [_need(t, torch.float32, "the ratings Hessian-vector product", name)
+              for name, t in (("U", U), ("V", V), ("dU", dU), ("dV", dV))]
+    _need_data(data, "the ratings Hessian-vector product")
+    U, V, dU, dV = (t.detach() for t in tables)
+    if dU.shape != U.shape or dV.shape != V.shape:
+        raise ValueError(f"a direction of shapes {tuple(dU.shape)}, {tuple(dV.shape)} for tables {tuple(U.shape)}, "
+                         f"{tuple(V.shape)}")
+    c = 1.0 / _support(data, skip_ties)
+    a = ragged_scores(U, V, data)[0]
+    dA = ragged_scores(dU, V, data)[0].add_(ragged_scores(U, dV, data)[0])
+    q = pair_ragged_hvp(a, dA, data, skip_ties)[0]
+    HU, HV = _table_grads(q, data, U, V)
+    if not gauss_newton:
+        g = pair_ragged_grad(a, data, s, skip_ties)[0]
+        gU, gV = _table_grads(g, data, dU, dV)
+        HU, HV = HU.add_(gU), HV.add_(gV)
+    return HU.mul_(c), HV.mul_(c)
 
 
 def ratings_metrics(U, V, data, s=1.0, skip_ties=False):

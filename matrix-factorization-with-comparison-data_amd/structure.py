@@ -29,6 +29,7 @@ from mfcd import newton as _newton
 from mfcd import pairs as _pairs
 from mfcd import population as _population
 from mfcd import ratings as _ratings
+from mfcd import ratings_exact as _ratings_exact
 from mfcd import sampling as _sampling
 from mfcd import topk as _topk
 
@@ -367,6 +368,67 @@ def compute_ratings_metrics(model, data, s=1.0, skip_ties=False):
     layout."""
     _need_gpu(model.U.device)
     return _ratings.ratings_metrics(model.U.data, model.V.data, data, s, skip_ties)
+
+
+def ratings_hvp(model, data, dU, dV, s=1.0, skip_ties=False, gauss_newton=False):
+    """Extension (not in the reference): `population_hvp` on a ratings table — the Hessian of `ratings_risk(model, data,
+    s, skip_ties)` with respect to the factor tables, applied to the direction (dU [n, d], dV [m, d]) → (HU, HV) fp32 on
+    the model's device (include/mfcd.h mfcd_pair_ragged_hvp, the Laplacian of every user's pair risk over the items that
+    user rated, carried to the tables by mfcd_ragged_dot and mfcd_ragged_gather_sum).  gauss_newton=True drops the terms
+    that hold the risk's gradient: the product is then positive semidefinite.  fp32 models only.  Not part of the result
+    dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _ratings.ratings_hvp(model.U.data, model.V.data, dU, dV, data, s, skip_ties, gauss_newton)
+
+
+def fit_users_ratings(V_or_model, data, weight_decay, s=1.0, skip_ties=False, coef=None):
+    """Extension (not in the reference): fold-in on ratings — with the item table held fixed, the vectors of the users
+    of `data` from their ratings alone: for every user the minimiser of  c * (the user's all-pairs BTL risk sum) +
+    (wd / 2) |u|^2,  started at zero (mfcd.ratings_exact.ratings_user_step: Newton-CG on mfcd_pair_ragged_hvp).  The
+    users need not have been in training; data.m must be the number of rows of V.  V_or_model: a model or a bare fp32 V
+    [m, d] on the GPU.  c = 1 / data.support(skip_ties), or `coef`: pass the training table's 1 / support so that the
+    ridge weighs as it did in training.  Returns the PopulationStepResult (rows [data.n, d], status 0 certified / 1
+    stopped / 2 invalid, newton_iters, cg_iters, objective_before, objective_after, grad_ratio); a user without a pair
+    gets the zero row.  weight_decay must be > 0.  Not part of the result dict / .pkl layout."""
+    V = V_or_model.V.data if hasattr(V_or_model, "V") and hasattr(V_or_model, "U") else V_or_model
+    if not torch.is_tensor(V):
+        raise TypeError("fit_users_ratings takes a model or its V table")
+    _need_gpu(V.device)
+    return _ratings_exact.ratings_user_step(None, V, data, s, float(weight_decay), skip_ties, coef)
+
+
+def refit_users_ratings(model, data, s, weight_decay, skip_ties=False):
+    """Extension (not in the reference): `refit_users_population` on a ratings table — for the model's own V, the best
+    response of every user's row on  F = ratings_risk + (wd / 2)(|U|^2 + |V|^2),  the objective whose stationary points
+    `train_model_ratings` approaches under Adam's coupled weight decay, by mfcd.ratings_exact.ratings_user_step started
+    at `model.U`.  Returns (result, gain): the PopulationStepResult and, per user, gain = objective_before -
+    objective_after >= 0: what the trained row still had to gain in F with V fixed.  weight_decay must be > 0.  The
+    model is not changed.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    result = _ratings_exact.ratings_user_step(model.U.data, model.V.data, data, s, float(weight_decay), skip_ties)
+    return result, result.objective_before - result.objective_after
+
+
+def refit_items_ratings(model, data, s, weight_decay, skip_ties=False):
+    """Extension (not in the reference): the mirror of `refit_users_ratings` — for the model's own U, the minimiser over
+    all of V of F (one problem: a user's pairs couple the items), by mfcd.ratings_exact.ratings_item_step started at
+    `model.V`.  Returns (result, gain) with result.rows the best-response V [m, d] and gain the 0-dim decrease of F.
+    weight_decay must be > 0.  The model is not changed.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.V.device)
+    result = _ratings_exact.ratings_item_step(model.U.data, model.V.data, data, s, float(weight_decay), skip_ties)
+    return result, result.objective_before - result.objective_after
+
+
+def train_model_ratings_exact(model, data, s, weight_decay, sweeps=10, skip_ties=False):
+    """Extension (not in the reference): `train_model_ratings` by exact block steps instead of Adam — `sweeps` sweeps of
+    one exact user step and one exact item step of  F = ratings_risk + (wd / 2)(|U|^2 + |V|^2)
+    (mfcd.ratings_exact.fit_ratings_exact), each a Newton-CG solve on the ragged pair Hessian, in place on the model's
+    tables.  Returns F after every sub-step as a list of [after the user step, after the item step] per sweep; it does
+    not increase.  fp32 models only; weight_decay must be > 0.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    result = _ratings_exact.fit_ratings_exact(model.U.data, model.V.data, data, s, float(weight_decay), sweeps, skip_ties)
+    model.eval()
+    return result.history.cpu().tolist()
 
 
 def population_hvp(model, X, dU, dV, s=1.0, law=None, users=None, row_block=2048, gauss_newton=False):
