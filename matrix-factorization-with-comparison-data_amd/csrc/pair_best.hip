@@ -193,18 +193,6 @@ __global__ __launch_bounds__(kBestThreads) void pair_best_kernel(BestArgs g)
     }
 }
 
-template <bool HW, bool HM, bool HL> struct BestLaunch {
-    static void go(int d, dim3 grid, hipStream_t st, BestArgs g)
-    {
-        const dim3 block(kBestThreads);
-        if (d <= 4) hipLaunchKernelGGL((pair_best_kernel<4, 1, HW, HM, HL>), grid, block, 0, st, g);
-        else if (d <= 32) hipLaunchKernelGGL((pair_best_kernel<32, 1, HW, HM, HL>), grid, block, 0, st, g);
-        else if (d <= 64) hipLaunchKernelGGL((pair_best_kernel<64, 1, HW, HM, HL>), grid, block, 0, st, g);
-        else if (d <= 128) hipLaunchKernelGGL((pair_best_kernel<128, 1, HW, HM, HL>), grid, block, 0, st, g);
-        else hipLaunchKernelGGL((pair_best_kernel<128, 2, HW, HM, HL>), grid, block, 0, st, g);
-    }
-};
-
 }  // namespace
 
 extern "C" size_t mfcd_pair_best_workspace_bytes(int rows, int k, int d)
@@ -237,8 +225,8 @@ extern "C" int mfcd_pair_best_rows(const float *A, int64_t lda, const float *X, 
     const bool per_row = g_row_stride != 0;
     float *nrm = (float *)workspace;
     hipStream_t st = (hipStream_t)stream;
-    for (int r0 = 0; r0 < rows; r0 += R) {             // stream order keeps one block's norms apart from the next's
-        const int nr = rows - r0 < R ? rows - r0 : R;
+    // stream order keeps one block's norms apart from the next's
+    return pair_chunks(rows, R, [&](int r0, int nr) {
         const float *tbl = G + (int64_t)r0 * g_row_stride;
         if (per_row || r0 == 0) {
             hipLaunchKernelGGL(best_norm_kernel, dim3((unsigned)((k + kBestThreads - 1) / kBestThreads), (unsigned)(per_row ? nr : 1)),
@@ -253,8 +241,7 @@ extern "C" int mfcd_pair_best_rows(const float *A, int64_t lda, const float *X, 
         g.ldx = ldx;
         g.g_row_stride = g_row_stride;
         g.ldg = ldg;
-        g.law = la;
-        if (g.law.labels) g.law.labels += (int64_t)r0 * g.law.label_stride;
+        g.law = law_rows(la, r0);
         g.k = k;
         g.d = d;
         g.T = T;
@@ -264,9 +251,14 @@ extern "C" int mfcd_pair_best_rows(const float *A, int64_t lda, const float *X, 
         g.arg = best_j + (int64_t)r0 * ldj;
         g.ldv = ldv;
         g.ldj = ldj;
-        law_dispatch<BestLaunch>(la.alpha != nullptr, law && law->use_margin != 0, la.labels != nullptr, d,
-                                 dim3((unsigned)((int64_t)nr * T)), st, g);
-        MFCD_HIP_TRY(hipGetLastError());
-    }
-    return 0;
+        const dim3 grid((unsigned)((int64_t)nr * T)), block(kBestThreads);
+        law_dispatch(la, law && law->use_margin != 0, [&](auto hw, auto hm, auto hl) {
+            if (d <= 4) hipLaunchKernelGGL((pair_best_kernel<4, 1, hw(), hm(), hl()>), grid, block, 0, st, g);
+            else if (d <= 32) hipLaunchKernelGGL((pair_best_kernel<32, 1, hw(), hm(), hl()>), grid, block, 0, st, g);
+            else if (d <= 64) hipLaunchKernelGGL((pair_best_kernel<64, 1, hw(), hm(), hl()>), grid, block, 0, st, g);
+            else if (d <= 128) hipLaunchKernelGGL((pair_best_kernel<128, 1, hw(), hm(), hl()>), grid, block, 0, st, g);
+            else hipLaunchKernelGGL((pair_best_kernel<128, 2, hw(), hm(), hl()>), grid, block, 0, st, g);
+        });
+        return (int)hipGetLastError();
+    });
 }

@@ -220,16 +220,6 @@ __global__ __launch_bounds__(kInfoThreads) void pair_info_kernel(InfoArgs g)
     }
 }
 
-template <bool HW, bool HM, bool HL> struct InfoLaunch {
-    static void go(int nd, dim3 grid, hipStream_t st, InfoArgs g)
-    {
-        const dim3 block(kInfoThreads);
-        if (nd == 1) hipLaunchKernelGGL((pair_info_kernel<1, HW, HM, HL>), grid, block, 0, st, g);
-        else if (nd == 2) hipLaunchKernelGGL((pair_info_kernel<2, HW, HM, HL>), grid, block, 0, st, g);
-        else hipLaunchKernelGGL((pair_info_kernel<4, HW, HM, HL>), grid, block, 0, st, g);
-    }
-};
-
 }  // namespace
 
 extern "C" size_t mfcd_pair_hvp_multi_workspace_bytes(int rows, int k, int d)
@@ -262,9 +252,8 @@ extern "C" int mfcd_pair_hvp_multi_rows(const float *A, int64_t lda, const float
     double *ctr = (double *)workspace;
     int *flag = (int *)((char *)workspace + (size_t)R * kInfoMaxD * sizeof(double));
     hipStream_t st = (hipStream_t)stream;
-    const int nd = d <= 32 ? 1 : d <= 64 ? 2 : 4;
-    for (int r0 = 0; r0 < rows; r0 += R) {             // stream order keeps one chunk's centres apart from the next's
-        const int nr = rows - r0 < R ? rows - r0 : R;
+    // stream order keeps one chunk's centres apart from the next's
+    return pair_chunks(rows, R, [&](int r0, int nr) {
         const int32_t *ix = index ? index + (int64_t)r0 * index_stride : nullptr;
         if (per_row || r0 == 0) {
             hipLaunchKernelGGL(info_centre_kernel, dim3((unsigned)(per_row ? nr : 1), (unsigned)((d + 31) / 32)),
@@ -280,8 +269,7 @@ extern "C" int mfcd_pair_hvp_multi_rows(const float *A, int64_t lda, const float
         g.ldb = ldb;
         g.index = ix;
         g.index_stride = index_stride;
-        g.law = la;
-        if (g.law.labels) g.law.labels += (int64_t)r0 * g.law.label_stride;
+        g.law = law_rows(la, r0);
         g.k = k;
         g.d = d;
         g.T = T;
@@ -292,9 +280,12 @@ extern "C" int mfcd_pair_hvp_multi_rows(const float *A, int64_t lda, const float
         g.deg = deg ? deg + (int64_t)r0 * ldd : nullptr;
         g.ldz = ldz;
         g.ldd = ldd;
-        const dim3 grid((unsigned)((int64_t)nr * T), (unsigned)((d + kInfoChunkD - 1) / kInfoChunkD));
-        law_dispatch<InfoLaunch>(la.alpha != nullptr, law && law->use_margin != 0, la.labels != nullptr, nd, grid, st, g);
-        MFCD_HIP_TRY(hipGetLastError());
-    }
-    return 0;
+        const dim3 grid((unsigned)((int64_t)nr * T), (unsigned)((d + kInfoChunkD - 1) / kInfoChunkD)), block(kInfoThreads);
+        law_dispatch(la, law && law->use_margin != 0, [&](auto hw, auto hm, auto hl) {
+            if (d <= 32) hipLaunchKernelGGL((pair_info_kernel<1, hw(), hm(), hl()>), grid, block, 0, st, g);
+            else if (d <= 64) hipLaunchKernelGGL((pair_info_kernel<2, hw(), hm(), hl()>), grid, block, 0, st, g);
+            else hipLaunchKernelGGL((pair_info_kernel<4, hw(), hm(), hl()>), grid, block, 0, st, g);
+        });
+        return (int)hipGetLastError();
+    });
 }

@@ -28,13 +28,6 @@ namespace {
 constexpr int kRagTile = 256;                          // entries per tile = threads per workgroup (mfcd_pair_ragged_tile)
 constexpr int kRagFlush = 64;                          // columns, = terms per accumulator, between two widenings to f64
 
-struct RagPartial {
-    long long c[4];     // C, D, pairs strictly ordered in a, in x, of this tile
-    long long bad[2];   // NaN entries, non-finite entries (NaN included) among the tile's own entries
-    double s[4];        // risk, bayes_risk, exp_acc, bayes_acc
-};
-static_assert(sizeof(RagPartial) == 80, "workspace layout");
-
 struct RagArgs {
     const float *a, *x;
     int64_t entries;
@@ -109,11 +102,9 @@ __device__ __forceinline__ void ragged_run(const float2 *tile, int jn, float ai,
 }
 
 template <int WHAT, bool SKIP>
-__global__ __launch_bounds__(kRagTile) void ragged_tiles_kernel(const RagArgs g, int64_t t0, RagPartial *__restrict__ part)
+__global__ __launch_bounds__(kRagTile) void ragged_tiles_kernel(const RagArgs g, int64_t t0, PairPartial *__restrict__ part)
 {
     __shared__ float2 tile[kRagTile];
-    __shared__ long long red_c[kRagTile / 64][6];
-    __shared__ double red_s[kRagTile / 64][6];
     const int tid = threadIdx.x;
     const int64_t t = t0 + blockIdx.x;
     RagTile w;
@@ -150,39 +141,22 @@ __global__ __launch_bounds__(kRagTile) void ragged_tiles_kernel(const RagArgs g,
 
     long long c6[6] = {(long long)cnt[0], (long long)cnt[1], (long long)cnt[2], (long long)cnt[3], (long long)n_nan,
                        (long long)n_inf};
-#pragma unroll
-    for (int q = 0; q < 6; ++q) c6[q] = wave_sum_xor(c6[q]);
-#pragma unroll
-    for (int q = 0; q < 6; ++q) acc[q] = wave_sum_xor(acc[q]);
-    if ((tid & 63) == 0) {
-        for (int q = 0; q < 6; ++q) red_c[tid >> 6][q] = c6[q];
-        for (int q = 0; q < 6; ++q) red_s[tid >> 6][q] = acc[q];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        RagPartial out;
-        for (int q = 0; q < 6; ++q) {
-            long long v = 0;
-            for (int k = 0; k < kRagTile / 64; ++k) v += red_c[k][q];
-            if (q < 4) out.c[q] = v;
-            else out.bad[q - 4] = v;
-        }
-        double s6[6];
-        for (int q = 0; q < 6; ++q) {
-            s6[q] = 0.0;
-            for (int k = 0; k < kRagTile / 64; ++k) s6[q] += red_s[k][q];       // fixed order
-        }
-        out.s[0] = 0.6931471805599453 * s6[0] + s6[1];
-        out.s[1] = 0.6931471805599453 * s6[2] + s6[3];
-        out.s[2] = s6[4];
-        out.s[3] = s6[5];
+    pair_block_sum<kRagTile / 64>(tid, c6, acc, [&](const long long(&c)[6], const double(&s)[6]) {
+        PairPartial out;
+        for (int q = 0; q < 4; ++q) out.c[q] = c[q];
+        out.bad[0] = c[4];
+        out.bad[1] = c[5];
+        out.s[0] = 0.6931471805599453 * s[0] + s[1];
+        out.s[1] = 0.6931471805599453 * s[2] + s[3];
+        out.s[2] = s[4];
+        out.s[3] = s[5];
         part[t] = out;
-    }
+    });
 }
 
 // One wave per row: lane l adds the partials of the row's tiles l, l + 64, ... in order, then the lanes are added in a
 // fixed tree; or the outputs of a row that failed validation.
-__global__ __launch_bounds__(256) void ragged_finish_kernel(const RagArgs g, const RagPartial *__restrict__ part, int what,
+__global__ __launch_bounds__(256) void ragged_finish_kernel(const RagArgs g, const PairPartial *__restrict__ part, int what,
                                                             int64_t *__restrict__ counts, double *__restrict__ sums)
 {
     const int lane = threadIdx.x & (MFCD_WAVE - 1);
@@ -201,7 +175,7 @@ __global__ __launch_bounds__(256) void ragged_finish_kernel(const RagArgs g, con
     long long c6[6] = {0, 0, 0, 0, 0, 0};
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     for (int64_t t = s0 + lane; t < s1; t += MFCD_WAVE) {
-        const RagPartial &p = part[t];
+        const PairPartial &p = part[t];
         for (int q = 0; q < 4; ++q) c6[q] += p.c[q];
         c6[4] += p.bad[0];
         c6[5] += p.bad[1];
@@ -332,39 +306,29 @@ __global__ __launch_bounds__(kRagTile) void ragged_hvp_kernel(const RagArgs g, c
     }
 }
 
-template <bool DEG>
-void ragged_hvp_launch(bool skip, unsigned blocks, hipStream_t st, const RagArgs &g, const float *y, int64_t t0, float *q,
-                       float *deg)
-{
-    if (skip) hipLaunchKernelGGL((ragged_hvp_kernel<DEG, true>), dim3(blocks), dim3(kRagTile), 0, st, g, y, t0, q, deg);
-    else hipLaunchKernelGGL((ragged_hvp_kernel<DEG, false>), dim3(blocks), dim3(kRagTile), 0, st, g, y, t0, q, deg);
-}
-
-template <int WHAT>
-void ragged_tiles_launch(bool skip, unsigned blocks, hipStream_t st, const RagArgs &g, int64_t t0, RagPartial *part)
-{
-    if (skip) hipLaunchKernelGGL((ragged_tiles_kernel<WHAT, true>), dim3(blocks), dim3(kRagTile), 0, st, g, t0, part);
-    else hipLaunchKernelGGL((ragged_tiles_kernel<WHAT, false>), dim3(blocks), dim3(kRagTile), 0, st, g, t0, part);
-}
-
-// The checks the two entries share → 0, or MFCD_EINVAL; fills the kernels' arguments.
-inline int ragged_args(const float *a, const float *x, int64_t entries, const int64_t *row_off, int rows,
+// The checks the three entries share → 0, or MFCD_EINVAL; fills the kernels' arguments.  need_x: whether x is read (the
+// Hessian reads it under the skip flag only, and has no scale: it passes 0).
+inline int ragged_args(const float *a, const float *x, bool need_x, int64_t entries, const int64_t *row_off, int rows,
                        const int64_t *tile_off, int64_t n_tiles, double scale, int flags, int32_t *status, RagArgs *out)
 {
     if (rows < 0 || entries < 0 || n_tiles < 0 || !row_off || !tile_off || !status) return MFCD_EINVAL;
-    if (entries > 0 && (!a || !x)) return MFCD_EINVAL;
+    if (entries > 0 && (!a || (need_x && !x))) return MFCD_EINVAL;
     if (flags & ~MFCD_RAGGED_SKIP_TIES) return MFCD_EINVAL;
     if (!std::isfinite(scale) || !std::isfinite((float)scale)) return MFCD_EINVAL;
     *out = RagArgs{a, x, entries, row_off, tile_off, rows, n_tiles, (float)scale, status};
     return 0;
 }
 
-inline int ragged_status_launch(const RagArgs &g, hipStream_t st)
+// What every entry launches: the validation of the rows, then launch(t0, grid) over the tiles in blocks of kPairMaxBlocks.
+template <class F>
+int ragged_launch(const RagArgs &g, hipStream_t st, F launch)
 {
-    const unsigned blocks = (unsigned)(((int64_t)g.rows + 3) / 4);
-    hipLaunchKernelGGL(ragged_status_kernel, dim3(blocks), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(ragged_status_kernel, dim3((unsigned)(((int64_t)g.rows + 3) / 4)), dim3(256), 0, st, g);
     MFCD_HIP_TRY(hipGetLastError());
-    return 0;
+    return pair_chunks(g.n_tiles, kPairMaxBlocks, [&](int64_t t0, int64_t nb) {
+        launch(t0, dim3((unsigned)nb));
+        return (int)hipGetLastError();
+    });
 }
 
 }  // namespace
@@ -374,7 +338,7 @@ extern "C" int mfcd_pair_ragged_tile(void) { return kRagTile; }
 extern "C" size_t mfcd_pair_ragged_workspace_bytes(int rows, int64_t n_tiles)
 {
     if (rows < 0 || n_tiles < 0 || n_tiles > (int64_t)1 << 40) return 0;
-    return align_up((size_t)(n_tiles > 0 ? n_tiles : 1) * sizeof(RagPartial));
+    return align_up((size_t)(n_tiles > 0 ? n_tiles : 1) * sizeof(PairPartial));
 }
 
 extern "C" int mfcd_pair_ragged_stats(const float *a, const float *x, int64_t entries, const int64_t *row_off, int rows,
@@ -383,28 +347,26 @@ extern "C" int mfcd_pair_ragged_stats(const float *a, const float *x, int64_t en
                                       size_t workspace_bytes, void *stream)
 {
     RagArgs g;
-    if (ragged_args(a, x, entries, row_off, rows, tile_off, n_tiles, scale, flags, status, &g)) return MFCD_EINVAL;
+    if (ragged_args(a, x, true, entries, row_off, rows, tile_off, n_tiles, scale, flags, status, &g)) return MFCD_EINVAL;
     if (what < 1 || what > 3 || ((what & 1) && !counts) || ((what & 2) && !sums)) return MFCD_EINVAL;
     if (rows == 0) return 0;
     if (!workspace) return MFCD_EINVAL;
     const size_t need = mfcd_pair_ragged_workspace_bytes(rows, n_tiles);
     if (need == 0) return MFCD_EINVAL;
     if (workspace_bytes < need) return MFCD_EWORKSPACE;
-    RagPartial *part = (RagPartial *)workspace;
+    PairPartial *part = (PairPartial *)workspace;
     hipStream_t st = (hipStream_t)stream;
-    const bool skip = (flags & MFCD_RAGGED_SKIP_TIES) != 0;
-    if (int rc = ragged_status_launch(g, st)) return rc;
-    for (int64_t t0 = 0; t0 < n_tiles; t0 += kPairMaxBlocks) {
-        const unsigned nb = (unsigned)(n_tiles - t0 < kPairMaxBlocks ? n_tiles - t0 : kPairMaxBlocks);
-        if (what == 1) ragged_tiles_launch<1>(skip, nb, st, g, t0, part);
-        else if (what == 2) ragged_tiles_launch<2>(skip, nb, st, g, t0, part);
-        else ragged_tiles_launch<3>(skip, nb, st, g, t0, part);
-        MFCD_HIP_TRY(hipGetLastError());
-    }
+    void (*const kernels[2][3])(RagArgs, int64_t, PairPartial *) = {
+        {ragged_tiles_kernel<1, false>, ragged_tiles_kernel<2, false>, ragged_tiles_kernel<3, false>},
+        {ragged_tiles_kernel<1, true>, ragged_tiles_kernel<2, true>, ragged_tiles_kernel<3, true>}};
+    const auto tiles = kernels[(flags & MFCD_RAGGED_SKIP_TIES) != 0][what - 1];
+    if (int rc = ragged_launch(g, st, [&](int64_t t0, dim3 grid) {
+            hipLaunchKernelGGL(tiles, grid, dim3(kRagTile), 0, st, g, t0, part);
+        }))
+        return rc;
     hipLaunchKernelGGL(ragged_finish_kernel, dim3((unsigned)(((int64_t)rows + 3) / 4)), dim3(256), 0, st, g, part, what,
                        counts, sums);
-    MFCD_HIP_TRY(hipGetLastError());
-    return 0;
+    return (int)hipGetLastError();
 }
 
 extern "C" int mfcd_pair_ragged_grad(const float *a, const float *x, int64_t entries, const int64_t *row_off, int rows,
@@ -412,44 +374,34 @@ extern "C" int mfcd_pair_ragged_grad(const float *a, const float *x, int64_t ent
                                      int32_t *status, void *stream)
 {
     RagArgs g;
-    if (ragged_args(a, x, entries, row_off, rows, tile_off, n_tiles, scale, flags, status, &g)) return MFCD_EINVAL;
+    if (ragged_args(a, x, true, entries, row_off, rows, tile_off, n_tiles, scale, flags, status, &g)) return MFCD_EINVAL;
     if (entries > 0 && !g_out) return MFCD_EINVAL;
     if (g_out && (g_out == a || g_out == x)) return MFCD_EINVAL;
     if (n_tiles > (int64_t)1 << 40) return MFCD_EINVAL;
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const bool skip = (flags & MFCD_RAGGED_SKIP_TIES) != 0;
-    if (int rc = ragged_status_launch(g, st)) return rc;
-    for (int64_t t0 = 0; t0 < n_tiles; t0 += kPairMaxBlocks) {
-        const unsigned nb = (unsigned)(n_tiles - t0 < kPairMaxBlocks ? n_tiles - t0 : kPairMaxBlocks);
-        if (skip) hipLaunchKernelGGL(ragged_grad_kernel<true>, dim3(nb), dim3(kRagTile), 0, st, g, t0, g_out);
-        else hipLaunchKernelGGL(ragged_grad_kernel<false>, dim3(nb), dim3(kRagTile), 0, st, g, t0, g_out);
-        MFCD_HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    const auto kernel = flags & MFCD_RAGGED_SKIP_TIES ? ragged_grad_kernel<true> : ragged_grad_kernel<false>;
+    return ragged_launch(g, st, [&](int64_t t0, dim3 grid) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kRagTile), 0, st, g, t0, g_out);
+    });
 }
 
 extern "C" int mfcd_pair_ragged_hvp(const float *a, const float *x, const float *y, int64_t entries, const int64_t *row_off,
                                     int rows, const int64_t *tile_off, int64_t n_tiles, int flags, float *q, float *deg,
                                     int32_t *status, void *stream)
 {
-    if (rows < 0 || entries < 0 || n_tiles < 0 || !row_off || !tile_off || !status) return MFCD_EINVAL;
-    if (entries > 0 && (!a || !y || !q)) return MFCD_EINVAL;
-    if (flags & ~MFCD_RAGGED_SKIP_TIES) return MFCD_EINVAL;
-    const bool skip = (flags & MFCD_RAGGED_SKIP_TIES) != 0;
-    if (skip && entries > 0 && !x) return MFCD_EINVAL;   // x is read under the skip flag only
+    const bool skip = (flags & MFCD_RAGGED_SKIP_TIES) != 0;   // x is read under the skip flag only
+    RagArgs g;
+    if (ragged_args(a, x, skip, entries, row_off, rows, tile_off, n_tiles, 0.0, flags, status, &g)) return MFCD_EINVAL;
+    if (entries > 0 && (!y || !q)) return MFCD_EINVAL;
     if (q && (q == a || q == y || q == x || q == deg)) return MFCD_EINVAL;
     if (deg && (deg == a || deg == y || deg == x)) return MFCD_EINVAL;
     if (n_tiles > (int64_t)1 << 40) return MFCD_EINVAL;
     if (rows == 0) return 0;
-    const RagArgs g{a, x, entries, row_off, tile_off, rows, n_tiles, 0.0f, status};   // no scale in a second derivative
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = ragged_status_launch(g, st)) return rc;
-    for (int64_t t0 = 0; t0 < n_tiles; t0 += kPairMaxBlocks) {
-        const unsigned nb = (unsigned)(n_tiles - t0 < kPairMaxBlocks ? n_tiles - t0 : kPairMaxBlocks);
-        if (deg) ragged_hvp_launch<true>(skip, nb, st, g, y, t0, q, deg);
-        else ragged_hvp_launch<false>(skip, nb, st, g, y, t0, q, deg);
-        MFCD_HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    const auto kernel = deg ? (skip ? ragged_hvp_kernel<true, true> : ragged_hvp_kernel<true, false>)
+                            : (skip ? ragged_hvp_kernel<false, true> : ragged_hvp_kernel<false, false>);
+    return ragged_launch(g, st, [&](int64_t t0, dim3 grid) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kRagTile), 0, st, g, y, t0, q, deg);
+    });
 }

@@ -44,19 +44,7 @@ constexpr int kPairIpt = 4;                            // elements of tile I per
 constexpr int kPairTile = kPairThreads * kPairIpt;     // 1024 columns (mfcd/pairs.py: TILE)
 constexpr int kPairFlush = 16;                         // columns between two widenings of the fp32 sums to f64
 
-struct PairPartial {
-    long long c[4];     // C, D, pairs strictly ordered in a, in x, of this (row, tile I)
-    long long bad[2];   // NaN entries, non-finite entries (NaN included) among tile I's elements
-    double s[4];        // risk, bayes_risk, exp_acc, bayes_acc
-};
-static_assert(sizeof(PairPartial) == 80, "workspace layout");
-
 inline int pair_tiles(int m) { return (m + kPairTile - 1) / kPairTile; }
-inline int pair_chunk_rows(int rows, int T)
-{
-    const int64_t R = kPairMaxBlocks / T;              // >= 1024
-    return (int)(rows < R ? rows : R);
-}
 
 // Columns [j0, j1) of the LDS tile against this thread's elements: k < KFULL unmasked, k == KMASK (the run of the
 // diagonal tile that holds element k itself, first column j0) only where the element's column is below j.
@@ -90,8 +78,6 @@ __global__ __launch_bounds__(kPairThreads) void pair_tiles_kernel(const float *_
                                                                   float scale, PairPartial *__restrict__ part)
 {
     __shared__ float2 tile[kPairTile];
-    __shared__ long long red_c[kPairThreads / 64][6];
-    __shared__ double red_s[kPairThreads / 64][6];
     const int tid = threadIdx.x;
     const int64_t r = blockIdx.x / T;
     const int I = (int)(blockIdx.x - r * T);
@@ -140,34 +126,17 @@ __global__ __launch_bounds__(kPairThreads) void pair_tiles_kernel(const float *_
 
     long long c6[6] = {(long long)cnt[0], (long long)cnt[1], (long long)cnt[2], (long long)cnt[3], (long long)n_nan,
                        (long long)n_inf};
-#pragma unroll
-    for (int q = 0; q < 6; ++q) c6[q] = wave_sum_xor(c6[q]);
-#pragma unroll
-    for (int q = 0; q < 6; ++q) acc[q] = wave_sum_xor(acc[q]);
-    if ((tid & 63) == 0) {
-        for (int q = 0; q < 6; ++q) red_c[tid >> 6][q] = c6[q];
-        for (int q = 0; q < 6; ++q) red_s[tid >> 6][q] = acc[q];
-    }
-    __syncthreads();
-    if (tid == 0) {
+    pair_block_sum<kPairThreads / 64>(tid, c6, acc, [&](const long long(&c)[6], const double(&s)[6]) {
         PairPartial out;
-        for (int q = 0; q < 6; ++q) {
-            long long v = 0;
-            for (int w = 0; w < kPairThreads / 64; ++w) v += red_c[w][q];
-            if (q < 4) out.c[q] = v;
-            else out.bad[q - 4] = v;
-        }
-        double s6[6];
-        for (int q = 0; q < 6; ++q) {
-            s6[q] = 0.0;
-            for (int w = 0; w < kPairThreads / 64; ++w) s6[q] += red_s[w][q];   // fixed order
-        }
-        out.s[0] = 0.6931471805599453 * s6[0] + s6[1];
-        out.s[1] = 0.6931471805599453 * s6[2] + s6[3];
-        out.s[2] = s6[4];
-        out.s[3] = s6[5];
+        for (int q = 0; q < 4; ++q) out.c[q] = c[q];
+        out.bad[0] = c[4];
+        out.bad[1] = c[5];
+        out.s[0] = 0.6931471805599453 * s[0] + s[1];
+        out.s[1] = 0.6931471805599453 * s[2] + s[3];
+        out.s[2] = s[4];
+        out.s[3] = s[5];
         part[blockIdx.x] = out;
-    }
+    });
 }
 
 // One wave per row: lane l adds the partials of tiles l, l + 64, ... in order, then the lanes are added in a fixed tree.
@@ -196,81 +165,7 @@ __global__ __launch_bounds__(64) void pair_finish_kernel(const PairPartial *__re
     }
 }
 
-template <int WHAT>
-void pair_launch(const float *A, int64_t lda, const float *X, int64_t ldx, int nr, int m, int T, float scale,
-                 PairPartial *part, hipStream_t st)
-{
-    hipLaunchKernelGGL(pair_tiles_kernel<WHAT>, dim3((unsigned)((int64_t)nr * T)), dim3(kPairThreads), 0, st, A, lda, X,
-                       ldx, m, T, scale, part);
-}
-
-// ---- the gradient of a row's risk sum (DESIGN section 3.10, follow-on) ----
-// g_i = sum over j != i of sigmoid(a_i - a_j) - sigmoid(scale (x_i - x_j)): the derivative of the `risk` sum above with
-// respect to a_i.  Same decomposition as pair_tiles_kernel — one workgroup per (row, tile I), four elements per thread
-// in registers, tiles streamed through LDS and read as a broadcast — but EVERY tile J is visited, so a thread owns its
-// four sums completely and stores them itself: no scatter to the j side, no workspace, no finishing kernel, no atomics,
-// at the price of visiting each unordered pair twice.
-constexpr int kGradFlush = 64;                         // columns, = terms per accumulator, between two widenings to f64
-
-__global__ __launch_bounds__(kPairThreads) void pair_grad_kernel(const float *__restrict__ A, int64_t lda,
-                                                                 const float *__restrict__ X, int64_t ldx, int m, int T,
-                                                                 float scale, float *__restrict__ G, int64_t ldg)
-{
-    __shared__ float2 tile[kPairTile];
-    const int tid = threadIdx.x;
-    const int64_t r = blockIdx.x / T;
-    const int I = (int)(blockIdx.x - r * T);
-    const float *a = A + r * lda, *x = X + r * ldx;
-
-    float ai[kPairIpt], xi[kPairIpt];
-#pragma unroll
-    for (int k = 0; k < kPairIpt; ++k) {
-        const int p = I * kPairTile + k * kPairThreads + tid;
-        ai[k] = p < m ? a[p] : 0.0f;                   // an element past m is computed and never stored
-        xi[k] = p < m ? x[p] : 0.0f;
-    }
-
-    int bad = 0;                                       // the workgroup stages the whole row: it sees every entry
-    double acc[kPairIpt] = {0.0, 0.0, 0.0, 0.0};
-    for (int J = 0; J < T; ++J) {
-        __syncthreads();                               // the previous tile's readers are done
-#pragma unroll
-        for (int k = 0; k < kPairIpt; ++k) {
-            const int e = k * kPairThreads + tid, p = J * kPairTile + e;
-            const float2 v = p < m ? make_float2(a[p], x[p]) : make_float2(0.0f, 0.0f);
-            bad |= (int)(is_nonfinite_bits(v.x) || is_nonfinite_bits(v.y));
-            tile[e] = v;
-        }
-        __syncthreads();
-        // columns of tile J that exist: a zero-filled pad column would be a real term here.  The column j == i needs no
-        // mask: both differences are +-0 there, both sigmoids run the same instructions on the same e, and the term is
-        // exactly 0.
-        const int jn = m - J * kPairTile < kPairTile ? m - J * kPairTile : kPairTile;
-        for (int jb = 0; jb < jn; jb += kGradFlush) {
-            const int je = jb + kGradFlush < jn ? jb + kGradFlush : jn;
-            float f[kPairIpt] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 4
-            for (int j = jb; j < je; ++j) {
-                const float2 v = tile[j];
-#pragma unroll
-                for (int k = 0; k < kPairIpt; ++k)
-                    f[k] += pair_sigmoid(ai[k] - v.x) - pair_sigmoid(scale * (xi[k] - v.y));
-            }
-#pragma unroll
-            for (int k = 0; k < kPairIpt; ++k) acc[k] += (double)f[k];
-        }
-    }
-
-    bad = __syncthreads_or(bad);
-    float *g = G + r * ldg;
-#pragma unroll
-    for (int k = 0; k < kPairIpt; ++k) {
-        const int p = I * kPairTile + k * kPairThreads + tid;
-        if (p < m) g[p] = bad ? __uint_as_float(0x7fc00000u) : (float)acc[k];     // rounded to fp32 once
-    }
-}
-
-// ---- the same two kernels under a pair law (second follow-on) ----
+// ---- the statistics under a pair law (second follow-on) ----
 // Every unordered pair {i, j} of a row carries a weight
 //   w = (alpha_i beta_j + alpha_j beta_i   or 1)  *  [|x_i - x_j| <= margin]  *  [label_i != label_j],
 // each factor present or not (template flags HW, HM, HL: an absent factor costs no load and no instruction).  The sums
@@ -365,8 +260,6 @@ __global__ __launch_bounds__(kPairThreads) void pair_law_tiles_kernel(const floa
 {
     __shared__ typename LawElem<HW>::type tile[kPairTile];
     __shared__ int lab[HL ? kPairTile : 1];
-    __shared__ long long red_c[kPairThreads / 64][2];
-    __shared__ double red_s[kPairThreads / 64][7];
     const int tid = threadIdx.x;
     const int64_t r = blockIdx.x / T;
     const int I = (int)(blockIdx.x - r * T);
@@ -426,34 +319,17 @@ __global__ __launch_bounds__(kPairThreads) void pair_law_tiles_kernel(const floa
     }
 
     long long c2[2] = {(long long)support, (long long)n_inf};
-#pragma unroll
-    for (int q = 0; q < 2; ++q) c2[q] = wave_sum_xor(c2[q]);
-#pragma unroll
-    for (int q = 0; q < 7; ++q) acc[q] = wave_sum_xor(acc[q]);
-    if ((tid & 63) == 0) {
-        for (int q = 0; q < 2; ++q) red_c[tid >> 6][q] = c2[q];
-        for (int q = 0; q < 7; ++q) red_s[tid >> 6][q] = acc[q];
-    }
-    __syncthreads();
-    if (tid == 0) {
+    pair_block_sum<kPairThreads / 64>(tid, c2, acc, [&](const long long(&c)[2], const double(&s)[7]) {
         LawPartial out;
-        out.support = out.bad = 0;
-        for (int w = 0; w < kPairThreads / 64; ++w) {
-            out.support += red_c[w][0];
-            out.bad += red_c[w][1];
-        }
-        double s7[7];
-        for (int q = 0; q < 7; ++q) {
-            s7[q] = 0.0;
-            for (int w = 0; w < kPairThreads / 64; ++w) s7[q] += red_s[w][q];   // fixed order
-        }
-        out.s[0] = HW ? s7[6] : (double)out.support;
-        out.s[1] = 0.6931471805599453 * s7[0] + s7[1];
-        out.s[2] = 0.6931471805599453 * s7[2] + s7[3];
-        out.s[3] = s7[4];
-        out.s[4] = s7[5];
+        out.support = c[0];
+        out.bad = c[1];
+        out.s[0] = HW ? s[6] : (double)out.support;
+        out.s[1] = 0.6931471805599453 * s[0] + s[1];
+        out.s[2] = 0.6931471805599453 * s[2] + s[3];
+        out.s[3] = s[4];
+        out.s[4] = s[5];
         part[blockIdx.x] = out;
-    }
+    });
 }
 
 // One wave per row, as pair_finish_kernel: a fixed order over the tiles, then a fixed tree over the lanes.
@@ -479,13 +355,21 @@ __global__ __launch_bounds__(64) void pair_law_finish_kernel(const LawPartial *_
     }
 }
 
-// g_i = sum over j != i of w_ij (sigmoid(a_i - a_j) - sigmoid(scale (x_i - x_j))): pair_grad_kernel under the law.  The
-// column j == i still needs no mask: its term is exactly +0 whatever its weight.
+// ---- the gradient of a row's risk sum (DESIGN section 3.10, follow-on) ----
+// g_i = sum over j != i of w_ij (sigmoid(a_i - a_j) - sigmoid(scale (x_i - x_j))): the derivative of the `risk` sum above
+// with respect to a_i.  Same decomposition as the statistics — one workgroup per (row, tile I), four elements per thread
+// in registers, tiles streamed through LDS and read as a broadcast — but EVERY tile J is visited, so a thread owns its
+// four sums completely and stores them itself: no scatter to the j side, no workspace, no finishing kernel, no atomics,
+// at the price of visiting each unordered pair twice.  One template serves the plain entry (no flag, an empty LawArgs:
+// w = 1, the accumulation a plain add) and the law entry.  The column j == i needs no mask: both differences are +-0
+// there, both sigmoids run the same instructions on the same e, and the term is exactly +0 whatever its weight.
+constexpr int kGradFlush = 64;                         // columns, = terms per accumulator, between two widenings to f64
+
 template <bool HW, bool HM, bool HL>
-__global__ __launch_bounds__(kPairThreads) void pair_law_grad_kernel(const float *__restrict__ A, int64_t lda,
-                                                                     const float *__restrict__ X, int64_t ldx, LawArgs law,
-                                                                     int m, int T, float scale, float *__restrict__ G,
-                                                                     int64_t ldg)
+__global__ __launch_bounds__(kPairThreads) void pair_grad_kernel(const float *__restrict__ A, int64_t lda,
+                                                                 const float *__restrict__ X, int64_t ldx, LawArgs law,
+                                                                 int m, int T, float scale, float *__restrict__ G,
+                                                                 int64_t ldg)
 {
     __shared__ typename LawElem<HW>::type tile[kPairTile];
     __shared__ int lab[HL ? kPairTile : 1];
@@ -523,7 +407,8 @@ __global__ __launch_bounds__(kPairThreads) void pair_law_grad_kernel(const float
             if (HL) lab[e] = in ? lb[p] : 0;
         }
         __syncthreads();
-        const int jn = m - J * kPairTile < kPairTile ? m - J * kPairTile : kPairTile;   // pad columns stay out
+        // columns of tile J that exist: a zero-filled pad column would be a real term here
+        const int jn = m - J * kPairTile < kPairTile ? m - J * kPairTile : kPairTile;
         for (int jb = 0; jb < jn; jb += kGradFlush) {
             const int je = jb + kGradFlush < jn ? jb + kGradFlush : jn;
             float f[kPairIpt] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -539,8 +424,10 @@ __global__ __launch_bounds__(kPairThreads) void pair_law_grad_kernel(const float
 #pragma unroll
                 for (int k = 0; k < kPairIpt; ++k) {
                     const float dx = xi[k] - v.y;
-                    const float w = law_weight<HW, HM, HL>(dx, ali[k], bei[k], li[k], alj, bej, lj, mg);
-                    f[k] = fmaf(w, pair_sigmoid(ai[k] - v.x) - pair_sigmoid(scale * dx), f[k]);
+                    const float term = pair_sigmoid(ai[k] - v.x) - pair_sigmoid(scale * dx);
+                    if constexpr (HW || HM || HL)
+                        f[k] = fmaf(law_weight<HW, HM, HL>(dx, ali[k], bei[k], li[k], alj, bej, lj, mg), term, f[k]);
+                    else f[k] += term;
                 }
             }
 #pragma unroll
@@ -561,7 +448,7 @@ __global__ __launch_bounds__(kPairThreads) void pair_law_grad_kernel(const float
 // q_i = sum over j != i of w_ij s_ij (y_i - y_j),  s_ij = sigmoid'(a_i - a_j),  and optionally deg_i = sum over j != i of
 // w_ij s_ij: the weighted graph Laplacian L(a) applied to y, and its diagonal.  The decomposition is pair_grad_kernel's
 // (every tile J visited, a thread owns its four sums and stores them itself); one template serves the plain entry
-// (LAW = false: no x, w = 1) and the law entry, whose flags are pair_law_grad_kernel's.
+// (LAW = false: no x, w = 1) and the law entry, whose flags are pair_grad_kernel's.
 //   s = e h h with e = exp(-|v|), h = 1 / (1 + e): symmetric in the sign of v, so nothing is selected and nothing
 //   cancels; one exp and one reciprocal per ordered pair.  The term is s (y_i - y_j), the difference formed first.
 // The column j == i adds exactly 0 to q (its difference is +0) but s = 1/4 to deg: with DEG the element that can meet its
@@ -675,56 +562,15 @@ __global__ __launch_bounds__(kPairThreads) void pair_hvp_kernel(const float *__r
     }
 }
 
-template <bool HW, bool HM, bool HL> struct LawTilesLaunch {
-    static void go(const float *A, int64_t lda, const float *X, int64_t ldx, LawArgs law, int nr, int m, int T, float scale,
-                   LawPartial *part, hipStream_t st)
-    {
-        hipLaunchKernelGGL((pair_law_tiles_kernel<HW, HM, HL>), dim3((unsigned)((int64_t)nr * T)), dim3(kPairThreads), 0, st,
-                           A, lda, X, ldx, law, m, T, scale, part);
-    }
-};
-
-template <bool HW, bool HM, bool HL> struct LawGradLaunch {
-    static void go(const float *A, int64_t lda, const float *X, int64_t ldx, LawArgs law, int nr, int m, int T, float scale,
-                   float *G, int64_t ldg, hipStream_t st)
-    {
-        hipLaunchKernelGGL((pair_law_grad_kernel<HW, HM, HL>), dim3((unsigned)((int64_t)nr * T)), dim3(kPairThreads), 0, st,
-                           A, lda, X, ldx, law, m, T, scale, G, ldg);
-    }
-};
-
-template <bool LAW, bool HW, bool HM, bool HL>
-void hvp_launch(const float *A, int64_t lda, const float *X, int64_t ldx, const float *Y, int64_t ldy, LawArgs law, int nr,
-                int m, int T, float *Q, int64_t ldq, float *deg, int64_t ldd, hipStream_t st)
+// The rest of the two Hessian-vector entries' argument check, after pair_args (X = nullptr: the plain entry).
+inline int hvp_args(const float *A, const float *X, const float *Y, const float *Q, const float *deg)
 {
-    const dim3 grid((unsigned)((int64_t)nr * T)), block(kPairThreads);
-    if (deg)
-        hipLaunchKernelGGL((pair_hvp_kernel<LAW, HW, HM, HL, true>), grid, block, 0, st, A, lda, X, ldx, Y, ldy, law, m, T, Q,
-                           ldq, deg, ldd);
-    else
-        hipLaunchKernelGGL((pair_hvp_kernel<LAW, HW, HM, HL, false>), grid, block, 0, st, A, lda, X, ldx, Y, ldy, law, m, T, Q,
-                           ldq, deg, ldd);
-}
-
-template <bool HW, bool HM, bool HL> struct LawHvpLaunch {
-    static void go(const float *A, int64_t lda, const float *X, int64_t ldx, const float *Y, int64_t ldy, LawArgs law, int nr,
-                   int m, int T, float *Q, int64_t ldq, float *deg, int64_t ldd, hipStream_t st)
-    {
-        hvp_launch<true, HW, HM, HL>(A, lda, X, ldx, Y, ldy, law, nr, m, T, Q, ldq, deg, ldd, st);
-    }
-};
-
-// The shared argument check of the two Hessian-vector entries → 0, or MFCD_EINVAL (X = nullptr: the plain entry).
-inline int hvp_args(const float *A, int64_t lda, const float *X, int64_t ldx, const float *Y, int64_t ldy, int rows, int m,
-                    const float *Q, int64_t ldq, const float *deg, int64_t ldd)
-{
-    if (!A || !Y || !Q || rows < 0 || m < 1 || m > kPairMaxCols || lda < m || ldy < m || ldq < m) return MFCD_EINVAL;
-    if (X && ldx < m) return MFCD_EINVAL;
-    if (deg && ldd < m) return MFCD_EINVAL;
-    if (Q == A || Q == Y || Q == X || Q == deg) return MFCD_EINVAL;
+    if (!Q || Q == A || Q == Y || Q == X || Q == deg) return MFCD_EINVAL;
     if (deg && (deg == A || deg == Y || deg == X)) return MFCD_EINVAL;
     return 0;
 }
+
+inline dim3 pair_grid(int nr, int T) { return dim3((unsigned)((int64_t)nr * T)); }
 
 }  // namespace
 
@@ -739,46 +585,37 @@ extern "C" int mfcd_pair_stats_rows(const float *A, int64_t lda, const float *X,
                                     double scale, int what, int64_t *counts, double *sums, void *workspace,
                                     size_t workspace_bytes, void *stream)
 {
-    if (!A || !X || rows < 0 || m < 1 || m > kPairMaxCols || lda < m || ldx < m) return MFCD_EINVAL;
+    if (pair_args(A, X, rows, m, scale, {lda, ldx})) return MFCD_EINVAL;
     if (what < 1 || what > 3 || ((what & 1) && !counts) || ((what & 2) && !sums)) return MFCD_EINVAL;
-    if (!std::isfinite(scale) || !std::isfinite((float)scale)) return MFCD_EINVAL;
     if (rows == 0) return 0;
     if (!workspace) return MFCD_EINVAL;
     if (workspace_bytes < mfcd_pair_stats_workspace_bytes(rows, m)) return MFCD_EWORKSPACE;
-    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
+    const int T = pair_tiles(m);
     PairPartial *part = (PairPartial *)workspace;
     hipStream_t st = (hipStream_t)stream;
-    for (int r0 = 0; r0 < rows; r0 += R) {             // stream order keeps one chunk's partials apart from the next's
-        const int nr = rows - r0 < R ? rows - r0 : R;
-        const float *a = A + (int64_t)r0 * lda, *x = X + (int64_t)r0 * ldx;
-        if (what == 1) pair_launch<1>(a, lda, x, ldx, nr, m, T, (float)scale, part, st);
-        else if (what == 2) pair_launch<2>(a, lda, x, ldx, nr, m, T, (float)scale, part, st);
-        else pair_launch<3>(a, lda, x, ldx, nr, m, T, (float)scale, part, st);
+    const auto tiles = what == 1 ? pair_tiles_kernel<1> : what == 2 ? pair_tiles_kernel<2> : pair_tiles_kernel<3>;
+    // stream order keeps one chunk's partials apart from the next's
+    return pair_chunks(rows, pair_chunk_rows(rows, T), [&](int r0, int nr) {
+        hipLaunchKernelGGL(tiles, pair_grid(nr, T), dim3(kPairThreads), 0, st, A + (int64_t)r0 * lda, lda,
+                           X + (int64_t)r0 * ldx, ldx, m, T, (float)scale, part);
         MFCD_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(pair_finish_kernel, dim3((unsigned)nr), dim3(64), 0, st, part, T,
-                           (long long)m * (m - 1) / 2, what,
+        hipLaunchKernelGGL(pair_finish_kernel, dim3((unsigned)nr), dim3(64), 0, st, part, T, (long long)m * (m - 1) / 2, what,
                            counts ? counts + (int64_t)r0 * 4 : nullptr, sums ? sums + (int64_t)r0 * 4 : nullptr);
-        MFCD_HIP_TRY(hipGetLastError());
-    }
-    return 0;
+        return (int)hipGetLastError();
+    });
 }
 
 extern "C" int mfcd_pair_grad_rows(const float *A, int64_t lda, const float *X, int64_t ldx, int rows, int m, double scale,
                                    float *G, int64_t ldg, void *stream)
 {
-    if (!A || !X || !G || rows < 0 || m < 1 || m > kPairMaxCols || lda < m || ldx < m || ldg < m) return MFCD_EINVAL;
-    if (G == A || G == X) return MFCD_EINVAL;
-    if (!std::isfinite(scale) || !std::isfinite((float)scale)) return MFCD_EINVAL;
-    if (rows == 0) return 0;
-    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
-    for (int r0 = 0; r0 < rows; r0 += R) {
-        const int nr = rows - r0 < R ? rows - r0 : R;
-        hipLaunchKernelGGL(pair_grad_kernel, dim3((unsigned)((int64_t)nr * T)), dim3(kPairThreads), 0, (hipStream_t)stream,
-                           A + (int64_t)r0 * lda, lda, X + (int64_t)r0 * ldx, ldx, m, T, (float)scale,
-                           G + (int64_t)r0 * ldg, ldg);
-        MFCD_HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    if (pair_args(A, X, rows, m, scale, {lda, ldx, ldg}) || !G || G == A || G == X) return MFCD_EINVAL;
+    const int T = pair_tiles(m);
+    return pair_chunks(rows, pair_chunk_rows(rows, T), [&](int r0, int nr) {
+        hipLaunchKernelGGL((pair_grad_kernel<false, false, false>), pair_grid(nr, T), dim3(kPairThreads), 0,
+                           (hipStream_t)stream, A + (int64_t)r0 * lda, lda, X + (int64_t)r0 * ldx, ldx, LawArgs{}, m, T,
+                           (float)scale, G + (int64_t)r0 * ldg, ldg);
+        return (int)hipGetLastError();
+    });
 }
 
 extern "C" size_t mfcd_pair_law_stats_workspace_bytes(int rows, int m)
@@ -792,87 +629,74 @@ extern "C" int mfcd_pair_law_stats_rows(const float *A, int64_t lda, const float
                                         double scale, const mfcd_pair_law *law, int64_t *support, double *sums,
                                         void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!A || !X || rows < 0 || m < 1 || m > kPairMaxCols || lda < m || ldx < m || !support || !sums) return MFCD_EINVAL;
-    if (!std::isfinite(scale) || !std::isfinite((float)scale)) return MFCD_EINVAL;
     LawArgs la;
-    if (law_args(law, m, &la)) return MFCD_EINVAL;
+    if (pair_args(A, X, rows, m, scale, {lda, ldx}) || !support || !sums || law_args(law, m, &la)) return MFCD_EINVAL;
     if (rows == 0) return 0;
     if (!workspace) return MFCD_EINVAL;
     if (workspace_bytes < mfcd_pair_law_stats_workspace_bytes(rows, m)) return MFCD_EWORKSPACE;
-    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
+    const int T = pair_tiles(m);
     LawPartial *part = (LawPartial *)workspace;
     hipStream_t st = (hipStream_t)stream;
-    for (int r0 = 0; r0 < rows; r0 += R) {             // stream order keeps one chunk's partials apart from the next's
-        const int nr = rows - r0 < R ? rows - r0 : R;
-        LawArgs lr = la;
-        if (lr.labels) lr.labels += (int64_t)r0 * lr.label_stride;
-        law_dispatch<LawTilesLaunch>(la.alpha != nullptr, law->use_margin != 0, la.labels != nullptr,
-                                     A + (int64_t)r0 * lda, lda, X + (int64_t)r0 * ldx, ldx, lr, nr, m, T, (float)scale, part,
-                                     st);
+    // stream order keeps one chunk's partials apart from the next's
+    return pair_chunks(rows, pair_chunk_rows(rows, T), [&](int r0, int nr) {
+        law_dispatch(la, law->use_margin != 0, [&](auto hw, auto hm, auto hl) {
+            hipLaunchKernelGGL((pair_law_tiles_kernel<hw(), hm(), hl()>), pair_grid(nr, T), dim3(kPairThreads), 0, st,
+                               A + (int64_t)r0 * lda, lda, X + (int64_t)r0 * ldx, ldx, law_rows(la, r0), m, T, (float)scale,
+                               part);
+        });
         MFCD_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(pair_law_finish_kernel, dim3((unsigned)nr), dim3(64), 0, st, part, T, support + r0,
                            sums + (int64_t)r0 * 5);
-        MFCD_HIP_TRY(hipGetLastError());
-    }
-    return 0;
+        return (int)hipGetLastError();
+    });
 }
 
 extern "C" int mfcd_pair_law_grad_rows(const float *A, int64_t lda, const float *X, int64_t ldx, int rows, int m,
                                        double scale, const mfcd_pair_law *law, float *G, int64_t ldg, void *stream)
 {
-    if (!A || !X || !G || rows < 0 || m < 1 || m > kPairMaxCols || lda < m || ldx < m || ldg < m) return MFCD_EINVAL;
-    if (G == A || G == X) return MFCD_EINVAL;
-    if (!std::isfinite(scale) || !std::isfinite((float)scale)) return MFCD_EINVAL;
     LawArgs la;
-    if (law_args(law, m, &la)) return MFCD_EINVAL;
-    if (rows == 0) return 0;
-    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
-    for (int r0 = 0; r0 < rows; r0 += R) {
-        const int nr = rows - r0 < R ? rows - r0 : R;
-        LawArgs lr = la;
-        if (lr.labels) lr.labels += (int64_t)r0 * lr.label_stride;
-        law_dispatch<LawGradLaunch>(la.alpha != nullptr, law->use_margin != 0, la.labels != nullptr,
-                                    A + (int64_t)r0 * lda, lda, X + (int64_t)r0 * ldx, ldx, lr, nr, m, T, (float)scale,
-                                    G + (int64_t)r0 * ldg, ldg, (hipStream_t)stream);
-        MFCD_HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    if (pair_args(A, X, rows, m, scale, {lda, ldx, ldg}) || !G || G == A || G == X || law_args(law, m, &la)) return MFCD_EINVAL;
+    const int T = pair_tiles(m);
+    return pair_chunks(rows, pair_chunk_rows(rows, T), [&](int r0, int nr) {
+        law_dispatch(la, law->use_margin != 0, [&](auto hw, auto hm, auto hl) {
+            hipLaunchKernelGGL((pair_grad_kernel<hw(), hm(), hl()>), pair_grid(nr, T), dim3(kPairThreads), 0,
+                               (hipStream_t)stream, A + (int64_t)r0 * lda, lda, X + (int64_t)r0 * ldx, ldx, law_rows(la, r0), m,
+                               T, (float)scale, G + (int64_t)r0 * ldg, ldg);
+        });
+        return (int)hipGetLastError();
+    });
 }
 
 extern "C" int mfcd_pair_hvp_rows(const float *A, int64_t lda, const float *Y, int64_t ldy, int rows, int m, float *Q,
                                   int64_t ldq, float *deg, int64_t ldd, void *stream)
 {
-    if (hvp_args(A, lda, nullptr, 0, Y, ldy, rows, m, Q, ldq, deg, ldd)) return MFCD_EINVAL;
-    if (rows == 0) return 0;
-    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
-    for (int r0 = 0; r0 < rows; r0 += R) {
-        const int nr = rows - r0 < R ? rows - r0 : R;
-        hvp_launch<false, false, false, false>(A + (int64_t)r0 * lda, lda, nullptr, 0, Y + (int64_t)r0 * ldy, ldy, LawArgs{}, nr,
-                                               m, T, Q + (int64_t)r0 * ldq, ldq, deg ? deg + (int64_t)r0 * ldd : nullptr, ldd,
-                                               (hipStream_t)stream);
-        MFCD_HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    if (pair_args(A, Y, rows, m, 0.0, {lda, ldy, ldq, deg ? ldd : m}) || hvp_args(A, nullptr, Y, Q, deg)) return MFCD_EINVAL;
+    const int T = pair_tiles(m);
+    const auto kernel = deg ? pair_hvp_kernel<false, false, false, false, true> : pair_hvp_kernel<false, false, false, false, false>;
+    return pair_chunks(rows, pair_chunk_rows(rows, T), [&](int r0, int nr) {
+        hipLaunchKernelGGL(kernel, pair_grid(nr, T), dim3(kPairThreads), 0, (hipStream_t)stream, A + (int64_t)r0 * lda, lda,
+                           (const float *)nullptr, (int64_t)0, Y + (int64_t)r0 * ldy, ldy, LawArgs{}, m, T,
+                           Q + (int64_t)r0 * ldq, ldq, deg ? deg + (int64_t)r0 * ldd : nullptr, ldd);
+        return (int)hipGetLastError();
+    });
 }
 
 extern "C" int mfcd_pair_law_hvp_rows(const float *A, int64_t lda, const float *X, int64_t ldx, const float *Y, int64_t ldy,
                                       int rows, int m, const mfcd_pair_law *law, float *Q, int64_t ldq, float *deg,
                                       int64_t ldd, void *stream)
 {
-    if (!X || hvp_args(A, lda, X, ldx, Y, ldy, rows, m, Q, ldq, deg, ldd)) return MFCD_EINVAL;
     LawArgs la;
-    if (law_args(law, m, &la)) return MFCD_EINVAL;
-    if (rows == 0) return 0;
-    const int T = pair_tiles(m), R = pair_chunk_rows(rows, T);
-    for (int r0 = 0; r0 < rows; r0 += R) {
-        const int nr = rows - r0 < R ? rows - r0 : R;
-        LawArgs lr = la;
-        if (lr.labels) lr.labels += (int64_t)r0 * lr.label_stride;
-        law_dispatch<LawHvpLaunch>(la.alpha != nullptr, law->use_margin != 0, la.labels != nullptr, A + (int64_t)r0 * lda, lda,
-                                   X + (int64_t)r0 * ldx, ldx, Y + (int64_t)r0 * ldy, ldy, lr, nr, m, T,
-                                   Q + (int64_t)r0 * ldq, ldq, deg ? deg + (int64_t)r0 * ldd : nullptr, ldd,
-                                   (hipStream_t)stream);
-        MFCD_HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    if (pair_args(A, Y, rows, m, 0.0, {lda, ldx, ldy, ldq, deg ? ldd : m}) || !X || hvp_args(A, X, Y, Q, deg) ||
+        law_args(law, m, &la))
+        return MFCD_EINVAL;
+    const int T = pair_tiles(m);
+    return pair_chunks(rows, pair_chunk_rows(rows, T), [&](int r0, int nr) {
+        law_dispatch(la, law->use_margin != 0, [&](auto hw, auto hm, auto hl) {
+            const auto kernel = deg ? pair_hvp_kernel<true, hw(), hm(), hl(), true> : pair_hvp_kernel<true, hw(), hm(), hl(), false>;
+            hipLaunchKernelGGL(kernel, pair_grid(nr, T), dim3(kPairThreads), 0, (hipStream_t)stream, A + (int64_t)r0 * lda, lda,
+                               X + (int64_t)r0 * ldx, ldx, Y + (int64_t)r0 * ldy, ldy, law_rows(la, r0), m, T,
+                               Q + (int64_t)r0 * ldq, ldq, deg ? deg + (int64_t)r0 * ldd : nullptr, ldd);
+        });
+        return (int)hipGetLastError();
+    });
 }

@@ -1,8 +1,11 @@
-// What the pair kernels of pairs.hip, pair_info.hip, pair_best.hip and pair_ragged.hip share: the limits of a call, the
-// pair law's kernel arguments, its weight, its argument check and the dispatch over its three flags, and the per-pair
-// arithmetic of the statistics, gradient and Hessian-vector kernels (DESIGN sections 3.10, 3.13, 3.14).
+// What the pair kernels of pairs.hip, pair_info.hip, pair_best.hip and pair_ragged.hip share: the limits of a call and the
+// host loop over its launches, the opening argument check, the pair law's kernel arguments, its weight, its argument
+// check and the dispatch over its three flags, the per-pair arithmetic of the statistics, gradient and Hessian-vector
+// kernels, and the statistics' workgroup reduction and partial (DESIGN sections 3.10, 3.13, 3.14).
 #pragma once
 #include <cmath>
+#include <initializer_list>
+#include <type_traits>
 
 #include "common.h"
 
@@ -13,11 +16,31 @@ constexpr int64_t kPairMaxBlocks = 1 << 20;            // (row, tile) workgroups
 
 // Rows per launch of a kernel with T (row, tile) workgroups per row: long inputs go through in blocks of rows of at most
 // kPairMaxBlocks workgroups and at most `cap` rows (what the kernel's per-row workspace allows).
-inline int pair_chunk_rows(int rows, int T, int64_t cap)
+inline int pair_chunk_rows(int rows, int T, int64_t cap = kPairMaxBlocks)
 {
     int64_t R = kPairMaxBlocks / T;                    // >= 128
     if (R > cap) R = cap;
     return (int)(rows < R ? rows : R);
+}
+
+// The host loop of every entry: [0, n) in blocks of at most `step`, launch(i0, count) per block in stream order → the
+// first non-zero status.  Rows (r0, nr) for the dense entries, tiles (t0, nb) for the ragged ones.
+template <class I, class F>
+int pair_chunks(I n, I step, F launch)
+{
+    for (I i0 = 0; i0 < n; i0 += step)
+        if (int rc = launch(i0, n - i0 < step ? n - i0 : step)) return rc;
+    return 0;
+}
+
+// The opening check of the dense entries → 0, or MFCD_EINVAL: the two inputs, the call's size, every leading dimension
+// (those of absent arrays are passed as m), a scale that is finite in fp32 (entries without a scale pass 0).
+inline int pair_args(const void *A, const void *B, int rows, int m, double scale, std::initializer_list<int64_t> lds)
+{
+    if (!A || !B || rows < 0 || m < 1 || m > kPairMaxCols) return MFCD_EINVAL;
+    for (int64_t ld : lds)
+        if (ld < m) return MFCD_EINVAL;
+    return std::isfinite(scale) && std::isfinite((float)scale) ? 0 : MFCD_EINVAL;
 }
 
 // Every unordered pair {i, j} of a row carries a weight
@@ -61,19 +84,29 @@ inline int law_args(const mfcd_pair_law *law, int m, LawArgs *out)
     return 0;
 }
 
-// F: a functor template over the three flags; picks the instantiation the law needs.
-template <template <bool, bool, bool> class F, class... Args>
-void law_dispatch(bool hw, bool hm, bool hl, Args... args)
+// The law of rows r0, r0 + 1, ... of a call: the labels move with the rows.
+inline LawArgs law_rows(LawArgs la, int64_t r0)
 {
-    switch ((hw ? 1 : 0) | (hm ? 2 : 0) | (hl ? 4 : 0)) {
-    case 0: F<false, false, false>::go(args...); break;
-    case 1: F<true, false, false>::go(args...); break;
-    case 2: F<false, true, false>::go(args...); break;
-    case 3: F<true, true, false>::go(args...); break;
-    case 4: F<false, false, true>::go(args...); break;
-    case 5: F<true, false, true>::go(args...); break;
-    case 6: F<false, true, true>::go(args...); break;
-    default: F<true, true, true>::go(args...); break;
+    if (la.labels) la.labels += r0 * la.label_stride;
+    return la;
+}
+
+// f: a generic lambda that receives the law's three flags (alpha / beta, margin, labels) as std::bool_constant tags and
+// launches the instantiation they name: hw() is a constant expression inside it.
+template <class F>
+void law_dispatch(const LawArgs &la, bool use_margin, F f)
+{
+    constexpr std::true_type y{};
+    constexpr std::false_type n{};
+    switch ((la.alpha ? 1 : 0) | (use_margin ? 2 : 0) | (la.labels ? 4 : 0)) {
+    case 0: f(n, n, n); break;
+    case 1: f(y, n, n); break;
+    case 2: f(n, y, n); break;
+    case 3: f(y, y, n); break;
+    case 4: f(n, n, y); break;
+    case 5: f(y, n, y); break;
+    case 6: f(n, y, y); break;
+    default: f(y, y, y); break;
     }
 }
 
@@ -130,5 +163,45 @@ __device__ __forceinline__ float pair_curvature(float da)
     const float h = __builtin_amdgcn_rcpf(1.0f + e);
     return e * h * h;
 }
+
+// ---- what the statistics kernels of pairs.hip and pair_ragged.hip share around the pair loops ----
+// The sums of NC 64-bit counters and NS f64 sums over a workgroup of WAVES waves: an xor tree within each wave, then
+// the waves in index order, by thread 0, which hands the totals to store(c, s).  Every thread of the workgroup calls it.
+template <int WAVES, int NC, int NS, class F>
+__device__ __forceinline__ void pair_block_sum(int tid, long long (&c)[NC], double (&s)[NS], F store)
+{
+    __shared__ long long red_c[WAVES][NC];
+    __shared__ double red_s[WAVES][NS];
+#pragma unroll
+    for (int q = 0; q < NC; ++q) c[q] = wave_sum_xor(c[q]);
+#pragma unroll
+    for (int q = 0; q < NS; ++q) s[q] = wave_sum_xor(s[q]);
+    if ((tid & 63) == 0) {
+        for (int q = 0; q < NC; ++q) red_c[tid >> 6][q] = c[q];
+        for (int q = 0; q < NS; ++q) red_s[tid >> 6][q] = s[q];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        long long ct[NC];
+        double st[NS];
+        for (int q = 0; q < NC; ++q) {
+            ct[q] = 0;
+            for (int w = 0; w < WAVES; ++w) ct[q] += red_c[w][q];
+        }
+        for (int q = 0; q < NS; ++q) {
+            st[q] = 0.0;
+            for (int w = 0; w < WAVES; ++w) st[q] += red_s[w][q];   // fixed order
+        }
+        store(ct, st);
+    }
+}
+
+// What one workgroup of a statistics kernel leaves in the workspace: one per (row, tile I), dense or ragged.
+struct PairPartial {
+    long long c[4];     // C, D, pairs strictly ordered in a, in x, of this tile
+    long long bad[2];   // NaN entries, non-finite entries (NaN included) among the tile's own elements
+    double s[4];        // risk, bayes_risk, exp_acc, bayes_acc
+};
+static_assert(sizeof(PairPartial) == 80, "workspace layout");
 
 }  // namespace

@@ -38,7 +38,7 @@ def test_best_entry_is_declared_and_bound():
     assert pairs.BEST_TILE == 128 and pairs.BEST_MAX_D == 256
     src = open(os.path.join(ROOT, "matrix-factorization-with-comparison-data_amd", "csrc", "pair_best.hip")).read()
     assert re.search(r"kBestTile = %d\b" % pairs.BEST_TILE, src) and '#include "pairs_common.h"' in src
-    assert "law_weight<" in src and "law_dispatch<" in src and "pair_chunk_rows(" in src     # shared, not copied
+    assert "law_weight<" in src and "law_dispatch(" in src and "pair_chunk_rows(" in src     # shared, not copied
 
 
 def test_best_bad_arguments_are_refused_before_the_device():

@@ -26,7 +26,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "matrix-factorization-with-comparison-d
 os.environ.setdefault("OMP_NUM_THREADS", "4")
 import torch  # noqa: E402
 
-from bench_pair_info import bench_lines, stretch, wall  # noqa: E402
+from pair_bench_common import bench_lines, stretch, wall  # noqa: E402
 from mfcd import design, pairs  # noqa: E402
 
 dev = torch.device("cuda:0")

@@ -17,36 +17,16 @@ import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "matrix-factorization-with-comparison-data_amd")]
-os.environ.setdefault("OMP_NUM_THREADS", "4")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
+
+from pair_bench_common import LANE_SLOTS_PER_S, ROOT, SECONDS, dev, stretch  # noqa: E402
 
 from mfcd import engine, pairs  # noqa: E402
 
-dev = torch.device("cuda:0")
-SECONDS = float(os.environ.get("PAIRS_BENCH_SECONDS", "0.5"))
 TORCH_SECONDS = float(os.environ.get("PAIRS_BENCH_TORCH_SECONDS", "1.0"))
 TEMP_ELEMS = (1 << 30) // (4 * 4)                 # four fp32 temporaries within 1 GiB
-LANE_SLOTS_PER_S = 1024 * 32 * 2.4e9              # VALU lanes x nominal clock
 CASES = (("notebooks 1000 x 1000 d=2", 1000, 1000, 2), ("C2 4096 x 4096 d=64", 4096, 4096, 64))
-
-
-def stretch(fn, seconds):
-    """Milliseconds per call over at least `seconds` of back-to-back calls (HIP events)."""
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    calls, total, per = 0, 0.0, 1
-    while total < seconds * 1e3:
-        t0.record()
-        for _ in range(per):
-            fn()
-        t1.record()
-        t1.synchronize()
-        ms = t0.elapsed_time(t1)
-        total += ms
-        calls += per
-        per = max(1, min(64, int(per * 0.05 * 1e3 / max(ms, 1e-3))))
-    return total / calls
 
 
 def torch_grad(A, X, scale, budget_s):

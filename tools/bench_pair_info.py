@@ -13,139 +13,28 @@ calls of the single-vector kernel on the same rows in the same run, the direct u
             turns, at 1000 x 1000 (d = 2, l2 = 1e-4) and C2 (d = 64, l2 = 1e-5) from the model's random start with
             X = U* V*^T as in bench_pair_hvp.py: wall ms (min of two), Newton and CG iterations, statuses, the largest
             distance between the two solvers' rows
-  identity  --parent-lib PATH (a libmfcd_hip.so built from the parent commit): the outputs of the six existing pair
-            entries on the three shapes, hashed in a child process per library and compared
+  identity  --parent-lib PATH (a libmfcd_hip.so built from the parent commit): the outputs of every pair entry
+            (pair_bench_common.py: digest), hashed in a child process per library and compared
   bench     --parent-tree DIR (a built checkout of the parent commit): bench.py --gpus 1 --steps 10490 --warmup 1049 in
             this tree and in DIR, taking turns, --bench-runs N runs each (default 3)
 
 Timing as DESIGN 3.4: HIP events around >= SECONDS of back-to-back calls after an untimed stretch, two rounds, the
 smaller one reported.  Usage: bench_pair_info.py [--out PATH] [--parent-lib PATH] [--parent-tree DIR] | --digest
 """
-import hashlib
-import json
 import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "matrix-factorization-with-comparison-data_amd")]
-os.environ.setdefault("OMP_NUM_THREADS", "4")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
+
+from pair_bench_common import (LANE_SLOTS_PER_S, ROOT, SECONDS, alternated, bench_lines, dev, digest, full_law,  # noqa: E402
+                               identity_lines, wall)
 
 from mfcd import pairs, population  # noqa: E402
 
-dev = torch.device("cuda:0")
-SECONDS = float(os.environ.get("PAIRS_BENCH_SECONDS", "0.5"))
-LANE_SLOTS_PER_S = 1024 * 32 * 2.4e9              # VALU lanes x nominal clock
 KERNELS = (("notebooks 1000 x 1000", 1000, 1000, 2), ("C2 4096 x 4096", 4096, 4096, 64),
            ("C5 width 256 x 20000", 256, 20000, 256))
 STEPS = (("notebooks 1000 x 1000 d=2", 1000, 1000, 2, 1e-4), ("C2 4096 x 4096 d=64", 4096, 4096, 64, 1e-5))
-
-
-def stretch(fn, seconds):
-    """Milliseconds per call over at least `seconds` of back-to-back calls (HIP events)."""
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    calls, total, per = 0, 0.0, 1
-    while total < seconds * 1e3:
-        t0.record()
-        for _ in range(per):
-            fn()
-        t1.record()
-        t1.synchronize()
-        ms = t0.elapsed_time(t1)
-        total += ms
-        calls += per
-        per = max(1, min(64, int(per * 0.05 * 1e3 / max(ms, 1e-3))))
-    return total / calls
-
-
-def alternated(fns):
-    """min over two rounds of every function's stretch, the functions taking turns within a round."""
-    found = [[] for _ in fns]
-    for _ in range(2):
-        for k, fn in enumerate(fns):
-            stretch(fn, SECONDS / 2)
-            found[k].append(stretch(fn, SECONDS))
-    return [min(t) for t in found]
-
-
-def full_law(m, g):
-    alpha, beta = (10.0 ** (-6.0 * torch.rand(m, generator=g)) for _ in range(2))
-    return pairs.PairLaw(alpha=alpha, beta=beta, margin=0.95, labels=torch.randint(0, 3, (m,), generator=g), device=dev)
-
-
-def wall(fn):
-    torch.cuda.synchronize()
-    start = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return out, (time.perf_counter() - start) * 1e3
-
-
-def digest():
-    """sha256 of the outputs of the six existing pair entries on the three shapes → one JSON line."""
-    import ctypes
-    from mfcd import _lib
-    lib = ctypes.CDLL(_lib.LIB_PATH)                    # a library of the parent commit lacks the entries added since
-    for name in [k for k in _lib.SIGNATURES if not hasattr(lib, k)]:
-        del _lib.SIGNATURES[name]
-    g = torch.Generator().manual_seed(1)
-    out = {}
-    for name, rows, m, _ in KERNELS:
-        A, X, Y = (torch.randn(rows, m, generator=g).to(dev) for _ in range(3))
-        law = full_law(m, g)
-        counts, sums = pairs.pair_stats_rows(A, X, 1.0, "both")
-        support, lsums = pairs.pair_law_stats_rows(A, X, law, 1.0)
-        parts = {"mfcd_pair_stats_rows": (counts, sums), "mfcd_pair_grad_rows": (pairs.pair_grad_rows(A, X, 1.0),),
-                 "mfcd_pair_law_stats_rows": (support, lsums),
-                 "mfcd_pair_law_grad_rows": (pairs.pair_law_grad_rows(A, X, law, 1.0),),
-                 "mfcd_pair_hvp_rows": pairs.pair_hvp_rows(A, Y, True) + (pairs.pair_hvp_rows(A, Y),),
-                 "mfcd_pair_law_hvp_rows": pairs.pair_law_hvp_rows(A, X, Y, law, True) + (pairs.pair_law_hvp_rows(A, X, Y, law),)}
-        for entry, ts in parts.items():
-            h = hashlib.sha256()
-            for t in ts:
-                h.update(t.cpu().numpy().tobytes())
-            out[f"{entry} @ {name}"] = h.hexdigest()
-    print(json.dumps(out))
-
-
-def identity_lines(parent_lib):
-    """The six entries under the library in use and under `parent_lib`, each hashed by a child process of its own."""
-    found = {}
-    for tag, lib in (("this build", None), ("parent build", os.path.abspath(parent_lib))):
-        env = dict(os.environ)
-        env.pop("MFCD_LIB", None)
-        if lib:
-            env["MFCD_LIB"] = lib
-        done = subprocess.run([sys.executable, os.path.abspath(__file__), "--digest"], env=env, capture_output=True,
-                              text=True, check=True)
-        found[tag] = json.loads(done.stdout.strip().splitlines()[-1])
-    lines = ["# identity: outputs of the six existing pair entries (the hvp entries with and without deg), this build against "
-             "a build of the parent commit (sha256 of every output tensor, first 12 digits)"]
-    for key in found["this build"]:
-        a, b = found["this build"][key], found["parent build"][key]
-        lines.append(f"#   {key:52s} {a[:12]} {b[:12]} {'bit-identical' if a == b else 'DIFFERENT'}")
-    return lines
-
-
-def bench_lines(parent_tree, runs):
-    """bench.py in this tree and in `parent_tree`, taking turns."""
-    found = {"this commit": [], "its parent": []}
-    for _ in range(runs):
-        for tag, tree in (("this commit", ROOT), ("its parent", os.path.abspath(parent_tree))):
-            env = dict(os.environ)
-            env.pop("MFCD_LIB", None)
-            done = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "10490", "--warmup", "1049"], cwd=tree,
-                                  env=env, capture_output=True, text=True, check=True)
-            found[tag].append(json.loads(done.stdout.strip().splitlines()[-1])["value"] / 1e6)
-    lines = [f"# bench.py --gpus 1 --steps 10490 --warmup 1049 in this tree and in a built checkout of the parent commit, {runs} "
-             "runs each, the commits taking turns on one GPU; M triplet-updates/s"]
-    for tag, vals in found.items():
-        med = sorted(vals)[len(vals) // 2]
-        lines.append(f"#   {tag:12s} " + " ".join(f"{v:8.2f}" for v in vals) + f"   median {med:8.2f}   spread "
-                     f"{100.0 * (max(vals) - min(vals)) / med:4.1f}%")
-    return lines
 
 
 def main():

@@ -25,7 +25,7 @@ os.environ.setdefault("OMP_NUM_THREADS", "4")
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from bench_pair_info import alternated, bench_lines, identity_lines, stretch, wall  # noqa: E402
+from pair_bench_common import alternated, bench_lines, identity_lines, stretch, wall  # noqa: E402
 from mfcd import engine, pairs, ratings  # noqa: E402
 import structure as S  # noqa: E402
 

@@ -22,7 +22,7 @@ os.environ.setdefault("OMP_NUM_THREADS", "4")
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from bench_pair_info import alternated, bench_lines, identity_lines, wall  # noqa: E402
+from pair_bench_common import alternated, bench_lines, identity_lines, wall  # noqa: E402
 from bench_pair_ragged import D, SECONDS, TORCH_BYTES, ml100k_shaped  # noqa: E402
 from mfcd import pairs, ratings, ratings_exact  # noqa: E402
 import structure as S  # noqa: E402
