@@ -1157,6 +1157,70 @@ int mfcd_ragged_gather_sum(const float *T, int t_rows, int d, int64_t entries, c
                            int64_t n_seg, float *out, int32_t *status, void *workspace, size_t workspace_bytes,
                            void *stream);
 
+/*
+ * The exact user step on a ratings table in one launch (no reference counterpart): what mfcd/ratings_exact.py's
+ * ratings_user_step computes with a chain of small launches per Newton iteration.  Row r owns entries
+ * [row_off[r], row_off[r+1]) of idx (int32, the entry's item: a row of V [m][d]) and x (its rating), L of them.  With V
+ * fixed, U_out[r] minimises
+ *     f(u) = coef * R_r(a) + (l2 / 2) |u|^2,   a_e = u . v_e,
+ *     R_r(a) = sum over the pairs e < l of the row of  w_el [softplus(a_e - a_l) - sigmoid(scale (x_e - x_l)) (a_e - a_l)],
+ * w_el = 1, or [x_e != x_l] under MFCD_RAGGED_SKIP_TIES: R_r is the `risk` sum of mfcd_pair_ragged_stats.  U_init = NULL
+ * starts every row at 0 (the fold-in of users who were not in training) and is bit-equal to a zero U_init.
+ * Algorithm (mfcd/population.py's _newton with solver "direct", per row; tests/ratings_foldin_model.py restates it):
+ *   1. u = U_init[r] or 0, t = 1, iterations = 0.
+ *   2. g = coef sum_e g_e v~_e + l2 u, g_e = sum over l != e of w_el (sigmoid(a_e - a_l) - sigmoid(scale (x_e - x_l))).
+ *      |g|_2 <= gtol l2 |u|_inf: status 0.  Otherwise iterations == max_newton: status 1.
+ *   3. If u moved since the direction was formed, or there is none yet:
+ *      H = coef sum_{e<l} w_el sigmoid'(a_e - a_l)(v~_e - v~_l)(v~_e - v~_l)^T + l2 I, p = -H^{-1} g by Cholesky in LDS; a
+ *      pivot that is not positive: p = -g / mean(diag H).
+ *   4. f_t = f(u + t p), iterations += 1.  f_t <= f + 1e-4 t (g . p) (a NaN f_t fails): u += t p, t = min(2 t, 1).
+ *      Otherwise t /= 2, the direction is kept, and t < 2^-12 ends the row with status 1.  Back to 2.
+ *      The inequality is evaluated twice and either evaluation accepts, as in mfcd_fold_in_users: on the two values of
+ *      f, and on the decrease f(u + t p) - f(u) summed pair by pair (softplus(a + h) - softplus(a) = log1p(sigmoid(a)
+ *      expm1(h)) for |h| < 1), which resolves decreases below the fp32 rounding of f itself.
+ * Precision: u, g, H, the solves, f and every dot product over d are f64.  v~_e is the gathered row minus the row's f64
+ * column mean, rounded to fp32 once (everything above depends on differences of the v_e only); a_e is an f64 chain over
+ * k rounded to fp32 once; the pair arithmetic is fp32, csrc/pairs_common.h's (pair_sigmoid, pair_curvature, the risk
+ * terms of pair_term), in runs of at most 64 terms widened to f64; Z = (D - C) V~ is formed per entry in fp32 runs of 64
+ * columns on the vector pipe, widened to f64 and rounded to fp32 once, and H = V~^T Z is added in f64.  U_out is the f64
+ * iterate rounded to fp32 once.
+ * Outputs: objective [rows][2] = {f at the start, f at the returned row}; grad_ratio [rows] = |g|_2 / (l2 |u|_inf) at
+ * the returned row; iters_status [rows][2] = {iterations, status}; info [rows][d][d] = sum_{e<l} w_el sigmoid'(a_e - a_l)
+ * (v~_e - v~_l)(v~_e - v~_l)^T at the returned row, without coef and ridge ([p][q] and [q][p] bit-equal; one more Hessian
+ * pass, taken only when info is not NULL; with max_newton = 0 the information at the start row).  objective, grad_ratio
+ * and info may be NULL, and a row's other outputs do not depend on it.
+ * Statuses: 0 certified; 1 stopped (iteration cap, or no Armijo decrease); 2 invalid data: offsets that are not
+ * 0 <= row_off[r] <= row_off[r+1] <= entries, an idx outside [0, m), a non-finite x, V row or U_init row — all checked
+ * before any gather, no address is formed from a bad index or offset — the row, its objective, grad_ratio and info
+ * are NaN, 0 iterations; 3: the row is longer than mfcd_ratings_fold_in_max_len(), outputs as for 2, nothing of the row
+ * is read.  A row without a supporting pair (L < 2; under the skip flag all x equal) is answered in closed form: row
+ * +0, status 0, 0 iterations, objective {(l2 / 2) |U_init[r]|^2, 0}, grad_ratio 0, info +0.
+ * One 256-thread workgroup owns a row from start to finish; no floating-point atomics, every sum has one owner and a
+ * fixed order that depends on the row alone: two calls are bit-equal and a row's outputs do not depend on the other
+ * rows or on its position.  No allocation and no host wait.
+ * mfcd_ratings_fold_in_max_len() = 3072: one workgroup takes a whole row, and a very long row would hold a compute unit
+ * for a long time.  Measured on one MI355X (profiles/ratings_fold_in.txt, one row of 1024 entries, d = 64): a Hessian
+ * pass runs at 0.34 G ordered pairs/s on its compute unit and a value-and-gradient pass at 0.52 G/s, 4.9 ns per ordered
+ * pair for an iteration of one pass each; a row of 3072 entries at max_newton = 20 then takes 3072^2 x 20 x 4.9 ns =
+ * 0.92 s, one of 4096 entries 1.6 s.  It is not a tuning knob.
+ * workspace: mfcd_ratings_fold_in_workspace_bytes(rows, d, entries) = 256 whatever the sizes (0 = sizes out of range):
+ * a row's state lives in its workgroup's LDS and nothing is staged in HBM; calls of more than 2^20 rows go through in
+ * launches of 2^20.
+ * Limits: 1 <= d <= mfcd_ratings_fold_in_max_d() = 64, m >= 1, rows >= 0 (0 = success, nothing launched), entries >= 0,
+ * flags 0 or MFCD_RAGGED_SKIP_TIES, scale finite as a float, coef and l2 finite and > 0, gtol finite and >= 0,
+ * 0 <= max_newton <= 1000, V, row_off, U_out and iters_status not NULL, idx and x where entries > 0, U_out and info
+ * overlapping none of V, idx, x, row_off, U_init nor each other; MFCD_EINVAL outside them and MFCD_EWORKSPACE for a short
+ * workspace, both before anything touches the device.
+ */
+int mfcd_ratings_fold_in_max_d(void);
+int mfcd_ratings_fold_in_max_len(void);
+size_t mfcd_ratings_fold_in_workspace_bytes(int rows, int d, int64_t entries);
+int mfcd_ratings_fold_in_users(const float *V, int m, int d, const int32_t *idx, const float *x, int64_t entries,
+                               const int64_t *row_off, int rows, double scale, int flags, double coef, double l2,
+                               const float *U_init, int max_newton, double gtol, float *U_out, double *objective,
+                               double *grad_ratio, int32_t *iters_status, double *info, void *workspace,
+                               size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

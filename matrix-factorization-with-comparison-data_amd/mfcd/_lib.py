@@ -134,6 +134,11 @@ SIGNATURES = {
     "mfcd_ragged_segment": (_i32, []),
     "mfcd_ragged_gather_sum_workspace_bytes": (_sz, [_i32, _i32, _i64]),
     "mfcd_ragged_gather_sum": (_i32, [_vp, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "mfcd_ratings_fold_in_max_d": (_i32, []),
+    "mfcd_ratings_fold_in_max_len": (_i32, []),
+    "mfcd_ratings_fold_in_workspace_bytes": (_sz, [_i32, _i32, _i64]),
+    "mfcd_ratings_fold_in_users": (_i32, [_vp, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _dbl, _i32, _dbl, _dbl, _vp, _i32, _dbl,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 TUNE_KEYS = {"resident_lookahead": 3, "resident_spin_limit": 5, "uvt_target_wgs": 9, "uvt_min_stages": 10,

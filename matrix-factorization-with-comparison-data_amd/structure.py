@@ -30,6 +30,7 @@ from mfcd import pairs as _pairs
 from mfcd import population as _population
 from mfcd import ratings as _ratings
 from mfcd import ratings_exact as _ratings_exact
+from mfcd import ratings_foldin as _ratings_foldin
 from mfcd import sampling as _sampling
 from mfcd import topk as _topk
 
@@ -407,6 +408,39 @@ def refit_users_ratings(model, data, s, weight_decay, skip_ties=False):
     _need_gpu(model.U.device)
     result = _ratings_exact.ratings_user_step(model.U.data, model.V.data, data, s, float(weight_decay), skip_ties)
     return result, result.objective_before - result.objective_after
+
+
+def fold_in_users_ratings(V_or_model, data, weight_decay, s=1.0, skip_ties=False, coef=None):
+    """Extension (not in the reference): `fit_users_ratings` in one launch — the same problem, start (zero), normaliser
+    and PopulationStepResult, solved by mfcd.ratings_foldin.ratings_fold_in_users: one workgroup per user runs the whole
+    damped Newton iteration with the user's d x d Hessian in LDS (include/mfcd.h mfcd_ratings_fold_in_users), d <= 64;
+    `cg_iters` is all zeros, and a user with more ratings than mfcd_ratings_fold_in_max_len() gets status 3 and a NaN
+    row (`fit_users_ratings` takes any length).  weight_decay must be > 0.  Not part of the result dict / .pkl layout."""
+    V = V_or_model.V.data if hasattr(V_or_model, "V") and hasattr(V_or_model, "U") else V_or_model
+    if not torch.is_tensor(V):
+        raise TypeError("fold_in_users_ratings takes a model or its V table")
+    _need_gpu(V.device)
+    return _ratings_foldin.ratings_fold_in_users(None, V, data, s, float(weight_decay), skip_ties, coef)
+
+
+def refit_users_ratings_kernel(model, data, s, weight_decay, skip_ties=False):
+    """Extension (not in the reference): `refit_users_ratings` in one launch — (result, gain) with the same meaning, the
+    users' best responses started at `model.U`, by mfcd.ratings_foldin.ratings_fold_in_users (d <= 64).  weight_decay
+    must be > 0.  The model is not changed.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    result = _ratings_foldin.ratings_fold_in_users(model.U.data, model.V.data, data, s, float(weight_decay), skip_ties)
+    return result, result.objective_before - result.objective_after
+
+
+def ratings_user_information(model, data, s=1.0, skip_ties=False):
+    """Extension (not in the reference): `user_information` on a ratings table — for every user of `data` the d x d
+    Hessian of the user's all-pairs risk sum in the user's row at the model's tables, H_u = sum over the pairs of the
+    user's items of w sigmoid'(a_e - a_l) (v_e - v_l)(v_e - v_l)^T → mfcd.pairs.UserInformation (info f64 [n, d, d],
+    weight f64 [n] the user's support, status int32 [n]) on the model's device (one call of
+    mfcd_ratings_fold_in_users without a Newton iteration; d <= 64).  fp32 models only.  Not part of the result dict /
+    .pkl layout."""
+    _need_gpu(model.U.device)
+    return _ratings_foldin.ratings_user_information(model.U.data, model.V.data, data, s, skip_ties)
 
 
 def refit_items_ratings(model, data, s, weight_decay, skip_ties=False):
