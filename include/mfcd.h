@@ -1221,6 +1221,51 @@ int mfcd_ratings_fold_in_users(const float *V, int m, int d, const int32_t *idx,
                                double *grad_ratio, int32_t *iters_status, double *info, void *workspace,
                                size_t workspace_bytes, void *stream);
 
+/*
+ * Where given columns of a row stand among the row's admissible columns (no reference counterpart): the rank of every
+ * held-out entry in the user's full ordered list of items, training items barred — what recall@k, hit rate, NDCG@k, MRR
+ * and AUC over the whole catalogue are computed from (mfcd/ranking.py).  Nothing is sorted and nothing n x m is formed.
+ * Scores as mfcd_topk_rows takes them: X [n][ldx] fp32, or (X == NULL) A [n][d] . B [m][d], 1 <= d <= MFCD_MAX_D, through
+ * the same fp32 MFMA kernel and the same bounded slab of whole score rows, so every score is formed once and is the number
+ * mfcd_topk_rows compares.  row_ids: `rows` row numbers (device), any order, repeats allowed; NULL = rows 0 .. rows-1.
+ * Two CSR lists are indexed by requested row r:
+ *   tgt_off int64 [rows+1], tgt_items int32 [entries]          the columns to rank, in any order, repeats allowed
+ *   excl_off int64 [rows+1], excl_items int32 [excl_entries]   the row's barred columns, strictly ascending; both NULL =
+ *                                                              nothing is barred
+ * Order: mfcd_topk_rows' `best` order — key = ~sortable_key(score), -0.0 equals +0.0, NaN above +inf, equal keys by
+ * ascending column: a total order on (key, column).  A column is admissible for a row when it is not barred there.
+ *   rank [entries]        the number of admissible columns c != t of the row that precede the entry's column t: the
+ *                         position t has in mfcd_topk_rows' list under the same exclusion list
+ *   ties [entries]        the number of admissible c != t whose key equals t's
+ *   score [entries]       nullable; the score that was compared
+ *   admissible [rows]     m minus the number of the row's barred columns
+ *   status [rows]         0, or 2: invalid data
+ * An entry whose own column is barred for its row gets rank -1 and ties -1 (its score is still the column's); the row's
+ * other targets are ordinary admissible columns, and a repeated target gets equal results.
+ * Status 2: offsets that are not 0 <= off[r] <= off[r+1] <= entries (excl_entries), a target or barred column outside
+ * [0, m), a barred list that is not strictly ascending, a row id outside [0, n), or more than 1 048 576 targets in the row
+ * — all checked before anything is gathered, and no address is formed from a value that failed.  The row's admissible is
+ * -1 and, where its target offsets are valid, its entries are rank -1, ties -1, score NaN; other rows are unaffected.
+ * Entries that lie in no valid row's slice are not written.  The rows' target slices are taken to be disjoint (the rows of
+ * one CSR list, or repeats of a row with a copy of its slice): an entry shared by two rows would receive both rows' counts.
+ * All accumulation is integer (a key comparison per (target, column), counts added by integer atomics into outputs the
+ * entry initialises itself): two calls are bit-equal, and a row's outputs depend neither on the other rows, nor on its
+ * position in the call, nor on where a slab ends.  No allocation and no host wait.
+ * Limits: rows >= 0 and entries >= 0 (0 of either is success; with rows > 0, admissible and status are still written),
+ * 1 <= m <= 4 194 304, n >= 1, pointers present where the counts are positive, excl_off and excl_items both or neither,
+ * outputs overlapping neither the inputs nor each other; MFCD_EINVAL outside them and MFCD_EWORKSPACE for a short
+ * workspace, both before anything touches the device.
+ * workspace: factor mode, mfcd_rank_entries_workspace_bytes(rows, m, d, entries) bytes, 256-byte aligned: the slab, at
+ * most 128 MiB (at least 128 rows), whatever n and entries are; 0 = sizes out of range (d = 0 included).  The dense mode
+ * needs none (NULL, 0).
+ */
+size_t mfcd_rank_entries_workspace_bytes(int rows, int m, int d, int64_t entries);
+int mfcd_rank_entries(const float *X, int64_t ldx, const float *A, const float *B, int d, const int32_t *row_ids, int rows,
+                      int n, int m, const int64_t *tgt_off, const int32_t *tgt_items, int64_t entries,
+                      const int64_t *excl_off, const int32_t *excl_items, int64_t excl_entries, int32_t *rank,
+                      int32_t *ties, float *score, int32_t *admissible, int32_t *status, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

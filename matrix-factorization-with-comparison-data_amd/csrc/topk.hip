@@ -6,7 +6,7 @@
 // lists for many rows at once, and the recommendation extensions of structure.py need them for U V^T.
 //
 // Form built: SLAB, then SELECT.
-//   factor mode   topk_scores_kernel writes a bounded slab of score rows (at most kSlabBytes, whole rows) into the
+//   factor mode   topk_scores_kernel (scores_common.h, shared with rank_entries.hip) writes a bounded slab of score rows (at most kSlabBytes, whole rows) into the
 //                 caller's workspace: 128 x 128 output block per workgroup, four waves of 2 x 2 tiles on the exact
 //                 fp32 MFMA (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain, the same for every element), operands
 //                 staged through LDS 32 factor columns at a time, any d.  Each score is computed ONCE, so selection
@@ -22,103 +22,14 @@
 // Ordered key: best = ~sortable(x), worst = sortable(x) with common.h's sortable_key (-0.0 == +0.0), NaN -> the
 // smallest key for best (torch.topk's convention), the largest for worst; equal keys are ordered by column.
 #include "common.h"
+#include "scores_common.h"
 
 namespace {
 
 constexpr int kTopkThreads = 1024;
 constexpr int kTopkWaves = kTopkThreads / MFCD_WAVE;
 constexpr int kTopkMaxK = 8192;                 // (key, column) pairs of one row that are sorted in LDS: 64 KiB
-constexpr int kTopkMaxM = 1 << 22;
 constexpr int kBins = 2048;                     // histogram of the widest radix digit (11 bits)
-constexpr size_t kSlabBytes = (size_t)128 << 20;   // score slab of the factor mode (at least one block of 128 rows)
-constexpr int kBlk = 128, kKC = 32, kLD = kKC + 1;  // score kernel: output block, factor columns per LDS stage, padded row
-
-// ascending ordered key = output order of the end
-__device__ __forceinline__ unsigned ordered_key(float f, bool worst)
-{
-    if (f != f) return worst ? 0xFFFFFFFFu : 0u;
-    const unsigned s = sortable_key(f);
-    return worst ? s : ~s;
-}
-
-// the id of requested row r, or -1 when it is not a row of the table
-__device__ __forceinline__ int row_id_of(const int32_t *row_ids, int row_base, int r, int n)
-{
-    const int id = row_ids ? row_ids[r] : row_base + r;
-    return id >= 0 && id < n ? id : -1;
-}
-
-// S[r][c] = A[id(r)] . B[c] for the `rows` requested rows of this slab (rows of S are `ld` floats apart).
-__global__ __launch_bounds__(256) void topk_scores_kernel(const float *__restrict__ A, const float *__restrict__ B,
-                                                          const int32_t *__restrict__ row_ids, int row_base, int rows,
-                                                          int n, int m, int d, float *__restrict__ S, int64_t ld)
-{
-    __shared__ float As[kBlk * kLD], Bs[kBlk * kLD];
-    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31, wave = tid >> 6;
-    const int r0 = blockIdx.y * kBlk, c0 = blockIdx.x * kBlk;
-    const int wr = (wave >> 1) * 64, wc = (wave & 1) * 64;
-    // loader: thread -> factor column lk of the stage, block rows lr + 8 i
-    const int lk = tid & 31, lr = tid >> 5;
-    int arow[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int r = r0 + lr + 8 * i;
-        arow[i] = r < rows ? row_id_of(row_ids, row_base, r, n) : -1;
-    }
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ti][tj][r] = 0.0f;
-
-    for (int k0 = 0; k0 < d; k0 += kKC) {
-        const int kk = k0 + lk;
-        const bool kok = kk < d;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int c = c0 + lr + 8 * i;
-            As[(lr + 8 * i) * kLD + lk] = kok && arow[i] >= 0 ? A[(int64_t)arow[i] * d + kk] : 0.0f;
-            Bs[(lr + 8 * i) * kLD + lk] = kok && c < m ? B[(int64_t)c * d + kk] : 0.0f;
-        }
-        __syncthreads();
-        const int steps = (min(kKC, d - k0) + 1) >> 1;   // MFMA k index: step s, lane half h -> k0 + 2 s + h
-        for (int s = 0; s < steps; ++s) {
-            const float a0 = As[(wr + l31) * kLD + 2 * s + half], a1 = As[(wr + 32 + l31) * kLD + 2 * s + half];
-            const float b0 = Bs[(wc + l31) * kLD + 2 * s + half], b1 = Bs[(wc + 32 + l31) * kLD + 2 * s + half];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj) {
-            const int col = c0 + wc + 32 * tj + l31;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int r = r0 + wr + 32 * ti + tile_row(reg, half);
-                if (r < rows && col < m) S[(int64_t)r * ld + col] = acc[ti][tj][reg];
-            }
-        }
-}
-
-// column c is in the ascending list items[lo, hi)
-__device__ __forceinline__ bool is_barred(const int32_t *__restrict__ items, int64_t lo, int64_t hi, int c)
-{
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        const int v = items[mid];
-        if (v == c) return true;
-        if (v < c) lo = mid + 1;
-        else hi = mid;
-    }
-    return false;
-}
 
 // inclusive sum of v over the workgroup's threads in thread order; total = the sum over all of them
 __device__ __forceinline__ int block_scan_incl(int v, int *wtot, int &total)
@@ -359,18 +270,6 @@ int select_rows(const SelectArgs &a, int rows, hipStream_t st)
          : m <= 16 * kTopkThreads ? launch_select<16>(a, rows, st)
          : m <= 32 * kTopkThreads ? launch_select<32>(a, rows, st)
          : launch_select<0>(a, rows, st);   // (64 keys per thread do not fit 128 registers without scratch)
-}
-
-inline int64_t slab_ld(int m) { return ((int64_t)m + 63) & ~(int64_t)63; }   // rows of the slab start on 256 bytes
-
-// rows per slab: whole blocks of the score kernel, at most kSlabBytes (but at least one block)
-inline int slab_rows(int rows, int m)
-{
-    const int64_t per = slab_ld(m) * 4;
-    int64_t rb = (int64_t)(kSlabBytes / (size_t)per) / kBlk * kBlk;
-    if (rb < kBlk) rb = kBlk;
-    const int64_t need = ((int64_t)rows + kBlk - 1) / kBlk * kBlk;
-    return (int)(rb < need ? rb : need);
 }
 
 inline bool topk_sizes_ok(int rows, int m, int d, int k, int ends)

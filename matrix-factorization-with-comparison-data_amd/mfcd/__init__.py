@@ -14,10 +14,11 @@
 `population` the exact block steps of the ridge-regularised population risk: Newton-CG on mfcd_pair_hvp_rows.
 `ratings`  the all-pairs risk, gradient and metrics on observed ratings: ragged rows (mfcd_pair_ragged_stats, _grad).
 `ratings_exact` the exact block steps of the ridge-regularised ratings risk: Newton-CG on mfcd_pair_ragged_hvp.
+`ranking` ranks of held-out entries among all admissible items and the full-catalogue ranking metrics (mfcd_rank_entries).
 `design`   the D-optimal comparison design of every user: pairwise Frank-Wolfe on the arg-max of mfcd_pair_best_rows.
 """
-from . import (_lib, alternating, batching, design, engine, foldin, metrics, newton, pairs, population, ratings,  # noqa: F401
-               ratings_exact, topk)
+from . import (_lib, alternating, batching, design, engine, foldin, metrics, newton, pairs, population, ranking,  # noqa: F401
+               ratings, ratings_exact, topk)
 
 __all__ = ["_lib", "alternating", "batching", "design", "engine", "foldin", "metrics", "newton", "pairs", "population",
-           "ratings", "ratings_exact", "topk"]
+           "ranking", "ratings", "ratings_exact", "topk"]

@@ -139,6 +139,9 @@ SIGNATURES = {
     "mfcd_ratings_fold_in_workspace_bytes": (_sz, [_i32, _i32, _i64]),
     "mfcd_ratings_fold_in_users": (_i32, [_vp, _i32, _i32, _vp, _vp, _i64, _vp, _i32, _dbl, _i32, _dbl, _dbl, _vp, _i32, _dbl,
                                           _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mfcd_rank_entries_workspace_bytes": (_sz, [_i32, _i32, _i32, _i64]),
+    "mfcd_rank_entries": (_i32, [_vp, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64] +
+                          [_vp] * 6 + [_sz, _vp]),
 }
 
 TUNE_KEYS = {"resident_lookahead": 3, "resident_spin_limit": 5, "uvt_target_wgs": 9, "uvt_min_stages": 10,

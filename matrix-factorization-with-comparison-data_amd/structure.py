@@ -28,6 +28,7 @@ from mfcd import metrics as _metrics
 from mfcd import newton as _newton
 from mfcd import pairs as _pairs
 from mfcd import population as _population
+from mfcd import ranking as _ranking
 from mfcd import ratings as _ratings
 from mfcd import ratings_exact as _ratings_exact
 from mfcd import ratings_foldin as _ratings_foldin
@@ -369,6 +370,26 @@ def compute_ratings_metrics(model, data, s=1.0, skip_ties=False):
     layout."""
     _need_gpu(model.U.device)
     return _ratings.ratings_metrics(model.U.data, model.V.data, data, s, skip_ties)
+
+
+def compute_ranking_metrics(model, test, train=None, ks=(10,), min_value=None, users=None):
+    """Extension (not in the reference): where the held-out ratings land in every user's ranking of the FULL catalogue —
+    recall@k, precision@k, hit@k and ndcg@k for every k of `ks`, mrr, mean_rank and auc, with the items of `train` left
+    out of the user's list as `recommend_items(exclude=...)` leaves them out (include/mfcd.h mfcd_rank_entries: the rank
+    of every test entry among the user's admissible items, counted by integer comparisons; no row is sorted and nothing
+    n x m is formed).  test, train: mfcd.ratings.RatingsData on the model's device, typically the two parts of
+    `data.split`; min_value: only test entries with value >= min_value are targets, the others stay ordinary candidates.
+    Returns a dict in the convention of `compute_pairwise_metrics`: every key is the mean over the users that have a
+    target, every key with the suffix `_per_user` a float64 numpy array (NaN for users without one; users: None = every
+    user, else user numbers, returned in that order), plus the counts `users`, `targets`, `dropped_barred` (targets that
+    are in `train` themselves) and `dropped_invalid`.  auc follows the order (score, then item number) with no half
+    credit for ties (mfcd.ranking.ranking_metrics has the formulas).  `model` may also be a dense GPU tensor X or a
+    `FactoredMatrix`: on a table made by `observe_ratings` the truth's own ranking gives the ceiling.  Not part of the
+    result dict / .pkl layout."""
+    if isinstance(model, nn.Module):
+        _need_gpu(model.U.device)
+        model = (model.U.data, model.V.data)
+    return _ranking.ranking_metrics(model, test, train, ks, min_value, users)
 
 
 def ratings_hvp(model, data, dU, dV, s=1.0, skip_ties=False, gauss_newton=False):

@@ -8,7 +8,8 @@ of a build against a build of the parent commit.
                                     deg), mfcd_pair_hvp_multi_rows, mfcd_pair_best_rows and the three ragged entries
                                     (with and without skip-ties and deg), on edge shapes, on inputs long enough for a
                                     second launch block of every host loop, and on the three shapes the tools time
-  identity_lines                    `digest` under the library in use and under a parent build, one child process each
+  identity_lines                    `digest` (or another tool's --digest) under the library in use and under a parent
+                                    build, one child process each
   bench_lines                       bench.py in this tree and in a built checkout of the parent, taking turns
 
 Usage of its own: pair_bench_common.py --digest (the library is MFCD_LIB, or the tree's).
@@ -181,18 +182,19 @@ def digest():
     print(json.dumps(out))
 
 
-def identity_lines(parent_lib):
-    """`digest` under the library in use and under `parent_lib`, each in a child process of its own."""
+def identity_lines(parent_lib, script=None, what="every pair entry"):
+    """`digest` under the library in use and under `parent_lib`, each in a child process of its own.  script: another tool
+    whose --digest prints such a JSON line of `what` (bench_ranking.py: mfcd_topk_rows)."""
     found = {}
     for tag, lib in (("this build", None), ("parent build", os.path.abspath(parent_lib))):
         env = dict(os.environ)
         env.pop("MFCD_LIB", None)
         if lib:
             env["MFCD_LIB"] = lib
-        done = subprocess.run([sys.executable, os.path.abspath(__file__), "--digest"], env=env, capture_output=True,
+        done = subprocess.run([sys.executable, os.path.abspath(script or __file__), "--digest"], env=env, capture_output=True,
                               text=True, check=True, timeout=600)
         found[tag] = json.loads(done.stdout.strip().splitlines()[-1])
-    lines = ["# identity: outputs of every pair entry, this build against a build of the parent commit (sha256 of every "
+    lines = [f"# identity: outputs of {what}, this build against a build of the parent commit (sha256 of every "
              "output tensor, first 12 digits; an entry the parent lacks: -)"]
     for key, a in found["this build"].items():
         b = found["parent build"].get(key)
