@@ -21,6 +21,16 @@ inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) & ~(a - 1)
         if (e__ != hipSuccess) return (int)e__;   \
     } while (0)
 
+// Before a launch with `bytes` of dynamic LDS: raises the kernel's limit when the launch needs more than `allowed`, the
+// call site's record (a static, one per kernel instantiation, 0 at first) of what its kernel was last allowed.
+inline hipError_t allow_dynamic_lds(const void *kernel, size_t bytes, size_t &allowed)
+{
+    if (bytes <= allowed) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) allowed = bytes;
+    return e;
+}
+
 // DPP lane move inside a row of 16 (no LDS round trip, unlike __shfl / ds_bpermute).
 template <int CTRL>
 __device__ __forceinline__ float dpp_move(float x)

@@ -23,8 +23,8 @@
 //                       gradient entry; thread (bi, bj) adds the chunk's rank-64 update to the 4 x 4 block of the Hessian
 //                       it owns.  Gradient entries, Hessian blocks and the f partials live in registers for the whole
 //                       pass: every sum has one owner and a fixed order, so no reduction over d^2 entries is needed.
-//   Cholesky            in place in LDS on the lower triangle, right-looking, two barriers per column; the two
-//                       triangular solves keep one right-hand-side entry per thread, one barrier per column.
+//   Cholesky            fold_cholesky_solve (foldin_common.h): in place in LDS, right-looking, two barriers per column;
+//                       the two triangular solves keep one right-hand-side entry per thread, one barrier per column.
 //   line search         the same staging without the Hessian part.  The Armijo test is taken on the decrease
 //                       f(u + t s) - f(u) summed term by term, softplus(x + h) - softplus(x) = log1p(p expm1(h)) for
 //                       |h| < 1, not on two rounded values of f: close to the minimiser (a warm start from an fp32 row)
@@ -44,7 +44,7 @@
 // normal case; the hardware's workgroup dispatcher balances ragged rows.
 //
 // d > 64: foldin_cg.hip solves the same two problems by conjugate gradients on Hessian-vector products instead of a
-// Cholesky factor in LDS; what the two kernels share is in foldin_common.h.
+// Cholesky factor in LDS; what the two kernels share, the host check of their entries included, is in foldin_common.h.
 #include "foldin_common.h"
 
 namespace {
@@ -235,37 +235,8 @@ __global__ __launch_bounds__(NT) void fold_in_kernel(const float *__restrict__ V
     int it = 0, status = 1;
     for (;;) {                                         // g, H and fcur belong to u
         ++it;
-        // ---- Cholesky of H (lower triangle, in place; the diagonal of L goes to diag[]) ----
-        bool pd = true;
-        for (int k = 0; k < dpad; ++k) {
-            __syncthreads();
-            const double dk = H[k * ld + k];
-            if (!(dk > 0.0)) {
-                pd = false;
-                break;
-            }
-            const double lkk = sqrt(dk);
-            if (tid == 0) diag[k] = lkk;
-            for (int i = k + 1 + tid; i < dpad; i += NT) H[i * ld + k] = H[i * ld + k] / lkk;
-            __syncthreads();
-            for (int i = k + 1 + (tid / G); i < dpad; i += G)
-                for (int j = k + 1 + (tid % G); j <= i; j += G)
-                    H[i * ld + j] = fma(-H[i * ld + k], H[j * ld + k], H[i * ld + j]);
-        }
-        if (!pd) break;                                // not reached for l2 > 0 and finite data; u stays as it is
-        // ---- L y = -g, then L^T s = y: one entry per thread, one barrier per column ----
-        double rhs = tid < dpad ? -g[tid] : 0.0;
-        for (int k = 0; k < dpad; ++k) {
-            if (tid == k) sol[k] = rhs / diag[k];
-            __syncthreads();
-            if (tid > k && tid < dpad) rhs = fma(-H[tid * ld + k], sol[k], rhs);
-        }
-        rhs = tid < dpad ? sol[tid] : 0.0;
-        for (int k = dpad - 1; k >= 0; --k) {
-            if (tid == k) s[k] = rhs / diag[k];
-            __syncthreads();
-            if (tid < k) rhs = fma(-H[k * ld + tid], s[k], rhs);
-        }
+        // s = -H^-1 g; a pivot that is not positive is not reached for l2 > 0 and finite data: u stays as it is
+        if (!fold_cholesky_solve<NT, G>(H, ld, dpad, diag, sol, g, s, tid)) break;
         if (tid == 0) {
             double smax = 0.0, gs = 0.0;
             for (int k = 0; k < d; ++k) {
@@ -317,12 +288,8 @@ int fold_launch(const float *V, int m, int d, const mfcd_sample *rec, const int6
                 const FoldItem &item, hipStream_t st)
 {
     const size_t lds = fold_lds_doubles(d) * sizeof(double);
-    static size_t allowed = 48 * 1024;                 // raise the dynamic-LDS limit only when needed (per kernel)
-    if (lds > allowed) {
-        MFCD_HIP_TRY(hipFuncSetAttribute((const void *)fold_in_kernel<NT, ITEM>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        allowed = lds;
-    }
+    static size_t allowed = 0;
+    MFCD_HIP_TRY(allow_dynamic_lds((const void *)fold_in_kernel<NT, ITEM>, lds, allowed));
     hipLaunchKernelGGL((fold_in_kernel<NT, ITEM>), dim3((unsigned)rows), dim3(NT), lds, st, V, m, d, rec, row_off, l2,
                        U_init, max_iter, xtol, U_out, objective, iters_status, item);
     return (int)hipGetLastError();
@@ -345,16 +312,10 @@ extern "C" int mfcd_fold_in_users(const float *V, int m, int d, const mfcd_sampl
                                   double *objective, int32_t *iters_status, void *workspace, size_t workspace_bytes,
                                   void *stream)
 {
-    if (!V || !row_off || !U_out || !iters_status || m < 1 || d < 1 || d > kFoldMaxD || rows < 0) return MFCD_EINVAL;
-    if (!std::isfinite(l2) || !(l2 > 0.0) || max_iter < 1 || max_iter > 1000 || !std::isfinite(xtol) || xtol < 0.0)
-        return MFCD_EINVAL;
-    const size_t out_bytes = (size_t)rows * d * sizeof(float);
-    if (U_out == V || U_out == U_init || fold_overlap(U_out, out_bytes, V, (size_t)m * d * sizeof(float)) ||
-        (U_init && fold_overlap(U_out, out_bytes, U_init, out_bytes)))
-        return MFCD_EINVAL;
-    if (rows == 0) return 0;
-    if (!workspace) return MFCD_EINVAL;
-    if (workspace_bytes < mfcd_fold_in_workspace_bytes(rows, d)) return MFCD_EWORKSPACE;
+    if (!V || m < 1) return MFCD_EINVAL;
+    const int bad = fold_entry_check(d, kFoldMaxD, row_off, rows, l2, max_iter, xtol, U_out, iters_status, V, m, U_init, rows,
+                                     workspace, workspace_bytes, mfcd_fold_in_workspace_bytes(rows, d));
+    if (bad || rows == 0) return bad;
     hipStream_t st = (hipStream_t)stream;
     const FoldItem none{};
     if (d <= 16)
@@ -375,20 +336,12 @@ extern "C" int mfcd_item_step(const float *U, int n, const float *V, int m, int 
                               int max_iter, double xtol, float *V_out, double *objective2, int32_t *iters_status,
                               void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!U || !V || !row_off || !V_out || !iters_status || n < 1 || m < 1 || d < 1 || d > kFoldMaxD || rows < 0) return MFCD_EINVAL;
-    if (!row_item && rows > m) return MFCD_EINVAL;
-    if (!std::isfinite(l2) || !(l2 > 0.0) || !(theta > 0.0 && theta <= 1.0) || max_iter < 1 || max_iter > 1000 ||
-        !std::isfinite(xtol) || xtol < 0.0)
-        return MFCD_EINVAL;
-    const size_t out_bytes = (size_t)rows * d * sizeof(float);
-    if (V_out == V || V_out == U || fold_overlap(V_out, out_bytes, V, (size_t)m * d * sizeof(float)) ||
-        fold_overlap(V_out, out_bytes, U, (size_t)n * d * sizeof(float)))
-        return MFCD_EINVAL;
-    if (rows == 0) return 0;
-    if (!workspace) return MFCD_EINVAL;
+    if (!U || !V || n < 1 || m < 1 || (!row_item && rows > m) || !(theta > 0.0 && theta <= 1.0)) return MFCD_EINVAL;
     // the record count is on the device (row_off[rows]): the host requires the fixed part, and a row whose records end
     // beyond what the workspace holds is refused by its own workgroup (status 2)
-    if (workspace_bytes < mfcd_item_step_workspace_bytes(rows, d, 0)) return MFCD_EWORKSPACE;
+    const int bad = fold_entry_check(d, kFoldMaxD, row_off, rows, l2, max_iter, xtol, V_out, iters_status, U, n, V, m,
+                                     workspace, workspace_bytes, mfcd_item_step_workspace_bytes(rows, d, 0));
+    if (bad || rows == 0) return bad;
     const FoldItem item{V, m, row_item, theta, (double *)((char *)workspace + 256),
                         (int64_t)((workspace_bytes - 256) / sizeof(double))};
     hipStream_t st = (hipStream_t)stream;

@@ -4,8 +4,8 @@
 // is never formed: it is applied as q = sum_t w_t (delta_t . p) delta_t + l2 p, 2 d fma per comparison instead of d^2,
 // and what LDS holds is the row's delta_t, not a d x d factor.  include/mfcd.h states the algorithm and the stop rule
 // (|g|_2 <= l2 gtol |u|_inf, which bounds the distance to the minimiser by strong convexity); tests/foldin_cg_model.py
-// restates it in numpy.  Validation, staging, the scalar functions, the line search's rule and the epilogue are those of
-// foldin.hip (foldin_common.h); the item policy is the same template parameter.
+// restates it in numpy.  The entries' host check, validation, staging, the scalar functions, the line search's rule and
+// the epilogue are those of foldin.hip (foldin_common.h); the item policy is the same template parameter.
 //
 // One workgroup of 256 threads per row, no communication between workgroups, no atomics.  Thread k < d owns entry k of
 // every d-vector: g, the Jacobi diagonal, and CG's r, s and M^-1 r live in its registers; u, s and the CG direction p
@@ -320,12 +320,8 @@ int fold_cg_launch(const float *V, int m, int d, const mfcd_sample *rec, const i
                    int32_t *cg_iters, const FoldItem &item, const FoldCgWork &work, hipStream_t st)
 {
     const size_t lds = cg_lds_doubles(d) * sizeof(double);
-    static size_t allowed = 48 * 1024;                 // raise the dynamic-LDS limit only when needed (per kernel)
-    if (lds > allowed) {
-        MFCD_HIP_TRY(hipFuncSetAttribute((const void *)fold_cg_kernel<ITEM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds));
-        allowed = lds;
-    }
+    static size_t allowed = 0;
+    MFCD_HIP_TRY(allow_dynamic_lds((const void *)fold_cg_kernel<ITEM>, lds, allowed));
     hipLaunchKernelGGL((fold_cg_kernel<ITEM>), dim3((unsigned)rows), dim3(kCgThreads), lds, st, V, m, d, rec, row_off, l2,
                        U_init, max_iter, gtol, U_out, objective, iters_status, cg_iters, item, work);
     return (int)hipGetLastError();
@@ -333,11 +329,6 @@ int fold_cg_launch(const float *V, int m, int d, const mfcd_sample *rec, const i
 
 // the workspace behind its first 256 bytes: `arrays` f64 arrays of one length, as long as the bytes allow
 inline int64_t cg_work_cap(size_t workspace_bytes, int arrays) { return (int64_t)((workspace_bytes - 256) / (sizeof(double) * arrays)); }
-
-inline bool cg_scalars_ok(double l2, int max_iter, double gtol)
-{
-    return std::isfinite(l2) && l2 > 0.0 && max_iter >= 1 && max_iter <= 1000 && std::isfinite(gtol) && gtol >= 0.0;
-}
 
 }  // namespace
 
@@ -358,17 +349,12 @@ extern "C" int mfcd_fold_in_users_cg(const float *V, int m, int d, const mfcd_sa
                                      double *objective, int32_t *iters_status, int32_t *cg_iters, void *workspace,
                                      size_t workspace_bytes, void *stream)
 {
-    if (!V || !row_off || !U_out || !iters_status || m < 1 || d < 1 || d > kCgMaxD || rows < 0) return MFCD_EINVAL;
-    if (!cg_scalars_ok(l2, max_iter, gtol)) return MFCD_EINVAL;
-    const size_t out_bytes = (size_t)rows * d * sizeof(float);
-    if (U_out == V || U_out == U_init || fold_overlap(U_out, out_bytes, V, (size_t)m * d * sizeof(float)) ||
-        (U_init && fold_overlap(U_out, out_bytes, U_init, out_bytes)))
-        return MFCD_EINVAL;
-    if (rows == 0) return 0;
-    if (!workspace) return MFCD_EINVAL;
+    if (!V || m < 1) return MFCD_EINVAL;
     // the record count is on the device (row_off[rows]): the host requires the fixed part, and a row whose records end
     // beyond what the workspace holds is refused by its own workgroup (status 2)
-    if (workspace_bytes < mfcd_fold_in_cg_workspace_bytes(rows, d, 0)) return MFCD_EWORKSPACE;
+    const int bad = fold_entry_check(d, kCgMaxD, row_off, rows, l2, max_iter, gtol, U_out, iters_status, V, m, U_init, rows,
+                                     workspace, workspace_bytes, mfcd_fold_in_cg_workspace_bytes(rows, d, 0));
+    if (bad || rows == 0) return bad;
     const int64_t cap = cg_work_cap(workspace_bytes, 3);
     double *base = (double *)((char *)workspace + 256);
     const FoldCgWork work{base, base + cap, base + 2 * cap, cap};
@@ -387,16 +373,10 @@ extern "C" int mfcd_item_step_cg(const float *U, int n, const float *V, int m, i
                                  int max_iter, double gtol, float *V_out, double *objective2, int32_t *iters_status,
                                  int32_t *cg_iters, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!U || !V || !row_off || !V_out || !iters_status || n < 1 || m < 1 || d < 1 || d > kCgMaxD || rows < 0) return MFCD_EINVAL;
-    if (!row_item && rows > m) return MFCD_EINVAL;
-    if (!cg_scalars_ok(l2, max_iter, gtol) || !(theta > 0.0 && theta <= 1.0)) return MFCD_EINVAL;
-    const size_t out_bytes = (size_t)rows * d * sizeof(float);
-    if (V_out == V || V_out == U || fold_overlap(V_out, out_bytes, V, (size_t)m * d * sizeof(float)) ||
-        fold_overlap(V_out, out_bytes, U, (size_t)n * d * sizeof(float)))
-        return MFCD_EINVAL;
-    if (rows == 0) return 0;
-    if (!workspace) return MFCD_EINVAL;
-    if (workspace_bytes < mfcd_item_step_cg_workspace_bytes(rows, d, 0)) return MFCD_EWORKSPACE;
+    if (!U || !V || n < 1 || m < 1 || (!row_item && rows > m) || !(theta > 0.0 && theta <= 1.0)) return MFCD_EINVAL;
+    const int bad = fold_entry_check(d, kCgMaxD, row_off, rows, l2, max_iter, gtol, V_out, iters_status, U, n, V, m,
+                                     workspace, workspace_bytes, mfcd_item_step_cg_workspace_bytes(rows, d, 0));
+    if (bad || rows == 0) return bad;
     const int64_t cap = cg_work_cap(workspace_bytes, 4);
     double *base = (double *)((char *)workspace + 256);
     const FoldItem item{V, m, row_item, theta, base, cap};

@@ -1,8 +1,10 @@
-// foldin_common.h — what the two solvers of the exact block steps share (foldin.hip: Newton with a Cholesky factor in
-// LDS, d <= 64; foldin_cg.hip: Newton with conjugate gradients on Hessian-vector products, d <= 256): the
-// item policy's launch block, row validation, the NaN row, the empty rows, the prologue that forms c_t, the staging
-// rule, the per-comparison scalar functions, the line search's acceptance rule and the epilogue.  Every function is called by all
-// threads of the row's workgroup (NT of them) unless it says otherwise.
+// foldin_common.h — what the per-row Newton kernels share.  All three (foldin.hip, foldin_cg.hip,
+// ratings_foldin.hip): the line search's acceptance rule and constant, fold_overlap.  fold_cholesky_solve, the dense SPD
+// solve in LDS: foldin.hip calls it, ratings_foldin.hip keeps the same steps written out because the call measured
+// slower there (profiles/fold_family_refactor.txt); a new solver of this family calls it.  The two triplet kernels: the
+// host check of their four entries, the item policy's launch block, row validation, the NaN row, the empty rows, the
+// prologue that forms c_t, the staging rule, the per-comparison scalar functions and the epilogue.  Every device
+// function is called by all threads of the row's workgroup (NT of them) unless it says otherwise.
 #pragma once
 #include <cmath>
 
@@ -11,7 +13,7 @@
 namespace {
 
 constexpr int kFoldHalvings = 30;
-constexpr double kFoldArmijo = 1e-4;
+constexpr double kFoldArmijo = 1e-4;                   // population.ARMIJO
 
 // What the item step adds to a launch; the user step passes an empty one and never reads it.
 struct FoldItem {
@@ -27,6 +29,28 @@ inline bool fold_overlap(const void *a, size_t na, const void *b, size_t nb)
 {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + nb && y < x + na;
+}
+
+// l2, the iteration cap and the stop tolerance (xtol or gtol) of a triplet entry
+inline bool fold_scalars_ok(double l2, int max_iter, double tol)
+{
+    return std::isfinite(l2) && l2 > 0.0 && max_iter >= 1 && max_iter <= 1000 && std::isfinite(tol) && tol >= 0.0;
+}
+
+// The host check the four triplet entries share: the common arguments, the output [rows][d] against the two float tables
+// read ([n0][d], [n1][d]; a null one is skipped), the workspace.  0: the caller launches unless rows == 0.
+inline int fold_entry_check(int d, int max_d, const int64_t *row_off, int rows, double l2, int max_iter, double tol,
+                            const float *out, const int32_t *iters_status, const float *in0, int n0, const float *in1,
+                            int n1, const void *workspace, size_t workspace_bytes, size_t needed)
+{
+    if (!row_off || !out || !iters_status || d < 1 || d > max_d || rows < 0 || !fold_scalars_ok(l2, max_iter, tol))
+        return MFCD_EINVAL;
+    const size_t row_bytes = (size_t)d * sizeof(float), out_bytes = (size_t)rows * row_bytes;
+    if ((in0 && (out == in0 || fold_overlap(out, out_bytes, in0, (size_t)n0 * row_bytes))) ||
+        (in1 && (out == in1 || fold_overlap(out, out_bytes, in1, (size_t)n1 * row_bytes))))
+        return MFCD_EINVAL;
+    if (rows == 0) return 0;
+    return !workspace ? MFCD_EINVAL : workspace_bytes < needed ? MFCD_EWORKSPACE : 0;
 }
 
 // ---- validation: indices and labels before any gather, the start vector; table rows are checked as they are staged ----
@@ -179,6 +203,42 @@ __device__ __forceinline__ double fold_decrease_term(const FoldLogit &at, double
 __device__ __forceinline__ bool fold_armijo_accepts(double decrease, double fnew, double fcur, double t, double gs)
 {
     return decrease <= kFoldArmijo * t * gs || fnew <= fcur + kFoldArmijo * t * gs;
+}
+
+// ---- the Newton direction of a Cholesky kernel: out = -H^-1 g for the symmetric H [n][ld] in LDS, n <= NT ----
+// H is factored in place on its lower triangle, right-looking, two barriers per column, the trailing block walked on a
+// G x G grid of threads; the diagonal of L goes to diag[].  Then L y = -g (y in sol[]) and L^T out = y: one entry per
+// thread, one barrier per column.  The first column's barrier makes H and g visible, the last solve step's makes out
+// visible on return.  False when a pivot is not positive: out is untouched, every thread has left at the same column.
+template <int NT, int G>
+__device__ __forceinline__ bool fold_cholesky_solve(double *H, int ld, int n, double *diag, double *sol, const double *g,
+                                                    double *out, int tid)
+{
+    for (int k = 0; k < n; ++k) {
+        __syncthreads();
+        const double dk = H[k * ld + k];
+        if (!(dk > 0.0)) return false;
+        const double lkk = sqrt(dk);
+        if (tid == 0) diag[k] = lkk;
+        for (int i = k + 1 + tid; i < n; i += NT) H[i * ld + k] = H[i * ld + k] / lkk;
+        __syncthreads();
+        for (int i = k + 1 + (tid / G); i < n; i += G)
+            for (int j = k + 1 + (tid % G); j <= i; j += G)
+                H[i * ld + j] = fma(-H[i * ld + k], H[j * ld + k], H[i * ld + j]);
+    }
+    double rhs = tid < n ? -g[tid] : 0.0;
+    for (int k = 0; k < n; ++k) {
+        if (tid == k) sol[k] = rhs / diag[k];
+        __syncthreads();
+        if (tid > k && tid < n) rhs = fma(-H[tid * ld + k], sol[k], rhs);
+    }
+    rhs = tid < n ? sol[tid] : 0.0;
+    for (int k = n - 1; k >= 0; --k) {
+        if (tid == k) out[k] = rhs / diag[k];
+        __syncthreads();
+        if (tid < k) rhs = fma(-H[k * ld + tid], out[k], rhs);
+    }
+    return true;
 }
 
 // ---- epilogue: the f64 iterate u rounded once (item step: v_old + theta (v* - v_old) in f64 first), objectives, status ----

@@ -364,12 +364,8 @@ int launch_deep(const float *pts, int P, int dim, const float *C, int k, const f
                 int32_t *changed, hipStream_t st)
 {
     constexpr size_t lds = (size_t)WAVES * deep_stage_floats(TWO) * 4;
-    static bool allowed = false;
-    if (!allowed) {
-        MFCD_HIP_TRY(hipFuncSetAttribute((const void *)kmeans_assign_deep_kernel<WAVES, TWO>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        allowed = true;
-    }
+    static size_t allowed = 0;
+    MFCD_HIP_TRY(allow_dynamic_lds((const void *)kmeans_assign_deep_kernel<WAVES, TWO>, lds, allowed));
     hipLaunchKernelGGL((kmeans_assign_deep_kernel<WAVES, TWO>), dim3((unsigned)((P + 31) / 32)), dim3(64 * WAVES), lds, st,
                        pts, P, dim, C, k, hn, labels, dist2, changed);
     return 0;

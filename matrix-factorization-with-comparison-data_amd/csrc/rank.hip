@@ -127,11 +127,7 @@ int launch_radix(const float *A, int64_t lda, const float *X, int64_t ldx, int r
     region0 = (region0 + 15) & ~(size_t)15;
     const size_t lds = region0 + (size_t)m * 2;
     static size_t allowed = 0;
-    if (lds > allowed) {
-        MFCD_HIP_TRY(hipFuncSetAttribute((const void *)spearman_rows_radix_kernel<IPT>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        allowed = lds;
-    }
+    MFCD_HIP_TRY(allow_dynamic_lds((const void *)spearman_rows_radix_kernel<IPT>, lds, allowed));
     hipLaunchKernelGGL(spearman_rows_radix_kernel<IPT>, dim3((unsigned)rows), dim3(kRankThreads), lds, st, A, lda, X, ldx, m,
                        (int)region0, rho);
     MFCD_HIP_TRY(hipGetLastError());

@@ -30,7 +30,8 @@
 //                        tile's entries go through LDS in slabs of 64 and thread (bi, bj), bi >= bj, adds the rank-64
 //                        update of the 4 x 4 block it owns, as fold_in_kernel does; the upper triangle is the mirror
 //                        image of the lower, bit for bit.
-//   Cholesky and solves  fold_in_kernel's: in place in LDS, right-looking.
+//   Cholesky and solves  in place in LDS, right-looking: foldin_common.h's fold_cholesky_solve written out, because the
+//                        call cost this kernel 0.4 to 1 % (profiles/fold_family_refactor.txt): fix both copies together.
 // No atomics, no allocation, no host wait; every sum has one owner and a fixed order that depends on the row alone.
 #include <cmath>
 
@@ -43,7 +44,6 @@ constexpr int kRfMaxD = 64;
 constexpr int kRfMaxLen = 3072;                        // see include/mfcd.h: from the measured pass times at d = 64
 constexpr int kRfThreads = 256;
 constexpr int kRfStage = 64;                           // columns per LDS stage = terms per fp32 run
-constexpr double kRfArmijo = 1e-4;                     // population.ARMIJO
 constexpr double kRfMinStep = 1.0 / 4096.0;            // population.MIN_STEP
 
 struct RfArgs {
@@ -384,7 +384,7 @@ __global__ __launch_bounds__(kRfThreads) void ratings_fold_in_kernel(const RfArg
         __syncthreads();
     };
 
-    // p = -H^{-1} gv by Cholesky (fold_in_kernel's); a pivot that is not positive: p = -gv / mean(diag H).
+    // p = -H^{-1} gv by Cholesky (fold_cholesky_solve's steps); a pivot that is not positive: p = -gv / mean(diag H).
     auto direction = [&]() {
         if (tid == 0) {
             double tr = 0.0;
@@ -476,9 +476,8 @@ __global__ __launch_bounds__(kRfThreads) void ratings_fold_in_kernel(const RfArg
         const double gp = scal[4];
         const double ft = value_grad(ut, gt, t);
         ++it;
-        // the Armijo rule on the decrease summed pair by pair or on the two values of f: either evaluation accepts, as
-        // in foldin_common.h's fold_armijo_accepts; a NaN trial is a rejected one
-        if (scal[5] <= kRfArmijo * t * gp || ft <= f + kRfArmijo * t * gp) {
+        // the Armijo rule on the decrease summed pair by pair or on the two values of f; a NaN trial is a rejected one
+        if (fold_armijo_accepts(scal[5], ft, f, t, gp)) {
             if (tid < DK) {
                 u[tid] = ut[tid];
                 gv[tid] = gt[tid];
@@ -512,12 +511,8 @@ template <int DK, bool SKIP>
 int rf_launch(RfArgs g, int rows, hipStream_t st)
 {
     constexpr size_t lds = rf_lds_bytes(DK);
-    static bool raised = false;                        // the dynamic-LDS limit, once per instantiation
-    if (!raised) {
-        MFCD_HIP_TRY(hipFuncSetAttribute((const void *)ratings_fold_in_kernel<DK, SKIP>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        raised = true;
-    }
+    static size_t allowed = 0;
+    MFCD_HIP_TRY(allow_dynamic_lds((const void *)ratings_fold_in_kernel<DK, SKIP>, lds, allowed));
     return pair_chunks(rows, (int)kPairMaxBlocks, [&](int r0, int nr) {
         g.r0 = r0;
         hipLaunchKernelGGL((ratings_fold_in_kernel<DK, SKIP>), dim3((unsigned)nr), dim3(kRfThreads), lds, st, g);

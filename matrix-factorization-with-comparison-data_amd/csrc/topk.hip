@@ -251,11 +251,7 @@ int launch_select(const SelectArgs &a, int rows, hipStream_t st)
 {
     const size_t lds = (size_t)a.P * 8;
     static size_t allowed = 0;
-    if (lds > allowed) {
-        MFCD_HIP_TRY(hipFuncSetAttribute((const void *)topk_select_kernel<IPT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds));
-        allowed = lds;
-    }
+    MFCD_HIP_TRY(allow_dynamic_lds((const void *)topk_select_kernel<IPT>, lds, allowed));
     hipLaunchKernelGGL(topk_select_kernel<IPT>, dim3((unsigned)rows, a.ends == 3 ? 2u : 1u), dim3(kTopkThreads), lds, st, a.S,
                        a.ld, a.by_id, a.row_ids, a.row_base, a.n, a.m, a.k, a.P, a.ends, a.excl_off, a.excl_items, a.out);
     MFCD_HIP_TRY(hipGetLastError());

@@ -37,11 +37,32 @@ def _use_cg(L, d, method, what):
     return method == "cg" or (method == "auto" and d > L.mfcd_fold_in_max_d())
 
 
-def _with_cg_iters(result, cg_iters):
-    """`cg_iters` rides on the result as an attribute (not a field of the tuple): int32 [rows], the CG iterations of
-    each row in all; None for the Cholesky form."""
-    result.cg_iters = cg_iters
-    return result
+def _check_records(name, maker, records, row_off):
+    """The records and offsets of a call of `name` as tensors; `maker` is the function that makes them."""
+    if not torch.is_tensor(records) or not records.is_cuda or records.dtype != torch.int32 or records.dim() != 2 \
+            or records.shape[1] != 4 or not torch.is_tensor(row_off) or not row_off.is_cuda \
+            or row_off.dtype != torch.int64 or row_off.dim() != 1 or row_off.numel() < 1:
+        raise _lib.MfcdError(f"{name} needs int32 [N, 4] records and int64 [rows + 1] offsets on the GPU "
+                             f"(mfcd.foldin.{maker} makes them)")
+
+
+def _solve(L, method, what, result, dev, rows, d, cholesky, cg, head, max_iter):
+    """One call of the entry `method` selects at width d → `result` of (the rows, the columns of the objective, iters,
+    status), its attribute `cg_iters` (not a field of the tuple) set for the CG form.  `cholesky` and `cg`: the form's
+    (entry, workspace bytes, stop tolerance).  `head`: the entry's arguments before max_iter; what follows them is the
+    same for all four entries but for cg_iters."""
+    use_cg = _use_cg(L, d, method, what)
+    entry, ws_bytes, tol = cg if use_cg else cholesky
+    out = torch.empty((rows, d), dtype=torch.float32, device=dev)
+    objective = torch.empty((rows, len(result._fields) - 3), dtype=torch.float64, device=dev)
+    info = torch.empty((rows, 2), dtype=torch.int32, device=dev)
+    cg_iters = torch.empty(rows, dtype=torch.int32, device=dev) if use_cg else None
+    ws = _lib.workspace(ws_bytes, dev)
+    _lib.check(entry(*head, int(max_iter), float(tol), out.data_ptr(), objective.data_ptr(), info.data_ptr(),
+                     *((cg_iters.data_ptr(),) if use_cg else ()), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+    res = result(out, *objective.unbind(1), info[:, 0], info[:, 1])
+    res.cg_iters = cg_iters
+    return res
 
 
 def group_by_user(u, i, j, z, n):
@@ -76,11 +97,7 @@ def fold_in_users(V, records, row_off, l2, U_init=None, max_iter=50, xtol=2.0 **
         raise ValueError(f"method must be one of {METHODS}, not {method!r}")
     if not torch.is_tensor(V) or not V.is_cuda or V.dtype != torch.float32 or V.dim() != 2:
         raise _lib.MfcdError("fold_in_users needs V as a float32 [m, d] tensor on a GPU device (there is no CPU fallback)")
-    if not torch.is_tensor(records) or not records.is_cuda or records.dtype != torch.int32 or records.dim() != 2 \
-            or records.shape[1] != 4 or not torch.is_tensor(row_off) or not row_off.is_cuda \
-            or row_off.dtype != torch.int64 or row_off.dim() != 1 or row_off.numel() < 1:
-        raise _lib.MfcdError("fold_in_users needs int32 [N, 4] records and int64 [rows + 1] offsets on the GPU "
-                             "(mfcd.foldin.group_by_user makes them)")
+    _check_records("fold_in_users", "group_by_user", records, row_off)
     L = _lib.load()
     dev = V.device
     V = V.detach().contiguous()
@@ -91,24 +108,12 @@ def fold_in_users(V, records, row_off, l2, U_init=None, max_iter=50, xtol=2.0 **
         if not torch.is_tensor(U_init) or tuple(U_init.shape) != (rows, d) or U_init.dtype != torch.float32:
             raise _lib.MfcdError(f"U_init must be a float32 [{rows}, {d}] tensor")
         U_init = U_init.detach().to(dev).contiguous()
-    U = torch.empty((rows, d), dtype=torch.float32, device=dev)
-    objective = torch.empty(rows, dtype=torch.float64, device=dev)
-    info = torch.empty((rows, 2), dtype=torch.int32, device=dev)
-    rec_ptr = records.data_ptr() if records.numel() else None
-    if _use_cg(L, d, method, "the fold-in kernel"):
-        cg_iters = torch.empty(rows, dtype=torch.int32, device=dev)
-        ws = _lib.workspace(L.mfcd_fold_in_cg_workspace_bytes(rows, d, records.shape[0]), dev)
-        _lib.check(L.mfcd_fold_in_users_cg(V.data_ptr(), m, d, rec_ptr, row_off.data_ptr(), rows, float(l2),
-                                           _lib.ptr(U_init), int(max_iter), float(gtol), U.data_ptr(),
-                                           objective.data_ptr(), info.data_ptr(), cg_iters.data_ptr(), _lib.ptr(ws),
-                                           ws.numel(), _lib.stream_ptr(dev)))
-        return _with_cg_iters(FoldInResult(U, objective, info[:, 0], info[:, 1]), cg_iters)
-    ws = _lib.workspace(L.mfcd_fold_in_workspace_bytes(rows, d), dev)
-    _lib.check(L.mfcd_fold_in_users(V.data_ptr(), m, d, rec_ptr, row_off.data_ptr(), rows, float(l2), _lib.ptr(U_init),
-                                    int(max_iter), float(xtol),
-                                    U.data_ptr(), objective.data_ptr(), info.data_ptr(), _lib.ptr(ws), ws.numel(),
-                                    _lib.stream_ptr(dev)))
-    return FoldInResult(U, objective, info[:, 0], info[:, 1])
+    head = (V.data_ptr(), m, d, records.data_ptr() if records.numel() else None, row_off.data_ptr(), rows, float(l2),
+            _lib.ptr(U_init))
+    return _solve(L, method, "the fold-in kernel", FoldInResult, dev, rows, d,
+                  (L.mfcd_fold_in_users, L.mfcd_fold_in_workspace_bytes(rows, d), xtol),
+                  (L.mfcd_fold_in_users_cg, L.mfcd_fold_in_cg_workspace_bytes(rows, d, records.shape[0]), gtol),
+                  head, max_iter)
 
 
 def row_objective(U, V, records, row_off, l2):
@@ -182,11 +187,7 @@ def _fold_in_items(U, V, records, row_off, l2, row_item, theta, max_iter, xtol, 
             or U.shape[1] != V.shape[1]:
         raise _lib.MfcdError("fold_in_items needs U [n, d] and V [m, d] as float32 tensors on a GPU device (there is no "
                              "CPU fallback)")
-    if not torch.is_tensor(records) or not records.is_cuda or records.dtype != torch.int32 or records.dim() != 2 \
-            or records.shape[1] != 4 or not torch.is_tensor(row_off) or not row_off.is_cuda \
-            or row_off.dtype != torch.int64 or row_off.dim() != 1 or row_off.numel() < 1:
-        raise _lib.MfcdError("fold_in_items needs int32 [N, 4] records and int64 [rows + 1] offsets on the GPU "
-                             "(mfcd.foldin.group_by_item makes them)")
+    _check_records("fold_in_items", "group_by_item", records, row_off)
     L = _lib.load()
     dev = V.device
     U, V = U.detach().to(dev).contiguous(), V.detach().contiguous()
@@ -197,24 +198,12 @@ def _fold_in_items(U, V, records, row_off, l2, row_item, theta, max_iter, xtol, 
         if not torch.is_tensor(row_item) or tuple(row_item.shape) != (rows,) or row_item.dtype != torch.int32:
             raise _lib.MfcdError(f"row_item must be an int32 [{rows}] tensor")
         row_item = row_item.to(dev).contiguous()
-    out = torch.empty((rows, d), dtype=torch.float32, device=dev)
-    objective = torch.empty((rows, 2), dtype=torch.float64, device=dev)
-    info = torch.empty((rows, 2), dtype=torch.int32, device=dev)
-    rec_ptr = records.data_ptr() if records.numel() else None
-    if _use_cg(L, d, method, "the item step"):
-        cg_iters = torch.empty(rows, dtype=torch.int32, device=dev)
-        ws = _lib.workspace(L.mfcd_item_step_cg_workspace_bytes(rows, d, records.shape[0]), dev)
-        _lib.check(L.mfcd_item_step_cg(U.data_ptr(), n, V.data_ptr(), m, d, rec_ptr, row_off.data_ptr(),
-                                       _lib.ptr(row_item), rows, float(l2), float(theta), int(max_iter), float(gtol),
-                                       out.data_ptr(), objective.data_ptr(), info.data_ptr(), cg_iters.data_ptr(),
-                                       _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-        return _with_cg_iters(ItemStepResult(out, objective[:, 0], objective[:, 1], info[:, 0], info[:, 1]), cg_iters)
-    ws = _lib.workspace(L.mfcd_item_step_workspace_bytes(rows, d, records.shape[0]), dev)
-    _lib.check(L.mfcd_item_step(U.data_ptr(), n, V.data_ptr(), m, d, rec_ptr, row_off.data_ptr(), _lib.ptr(row_item),
-                                rows, float(l2), float(theta), int(max_iter),
-                                float(xtol), out.data_ptr(), objective.data_ptr(), info.data_ptr(), _lib.ptr(ws),
-                                ws.numel(), _lib.stream_ptr(dev)))
-    return ItemStepResult(out, objective[:, 0], objective[:, 1], info[:, 0], info[:, 1])
+    head = (U.data_ptr(), n, V.data_ptr(), m, d, records.data_ptr() if records.numel() else None, row_off.data_ptr(),
+            _lib.ptr(row_item), rows, float(l2), float(theta))
+    nrec = records.shape[0]
+    return _solve(L, method, "the item step", ItemStepResult, dev, rows, d,
+                  (L.mfcd_item_step, L.mfcd_item_step_workspace_bytes(rows, d, nrec), xtol),
+                  (L.mfcd_item_step_cg, L.mfcd_item_step_cg_workspace_bytes(rows, d, nrec), gtol), head, max_iter)
 
 
 def total_objective(U, V, u, i, j, z, l2):
