@@ -1266,6 +1266,56 @@ int mfcd_rank_entries(const float *X, int64_t ldx, const float *A, const float *
                       int32_t *ties, float *score, int32_t *admissible, int32_t *status, void *workspace,
                       size_t workspace_bytes, void *stream);
 
+/*
+ * The exact observed-versus-unobserved logistic risk of rows of a score matrix (no reference counterpart): what a model
+ * trained on implicit feedback (clicks, purchases, "rated at all") minimises, and the logistic surrogate of the per-user
+ * AUC that mfcd/ranking.py reports (mfcd/implicit.py).  For a requested row with observed columns P, barred columns E and
+ * N = [0, m) \ (P u E), over all |P \ E| |N| pairs exactly (BPR without the sampling), a = the row's scores:
+ *   R = sum over i in P \ E, j in N of softplus(a_j - a_i)
+ * Scores, row_ids, rows, n, m as mfcd_rank_entries takes them (dense X [n][ldx], or X == NULL and A [n][d] . B [m][d]
+ * through the same fp32 MFMA kernel and bounded slab, so the numbers compared are those mfcd_topk_rows and
+ * mfcd_rank_entries compare).  Two CSR lists are indexed by requested row r, both strictly ascending within a row:
+ *   pos_off int64 [rows+1], pos_items int32 [entries]          the row's observed columns
+ *   excl_off int64 [rows+1], excl_items int32 [excl_entries]   the row's barred columns; both NULL = nothing is barred
+ * coef: nullable fp32 [rows], the factor of the row's gradient; NULL = 1.
+ *   status [rows]       0, or 2: invalid data
+ *   counts [rows][4]    int64: pos = |P \ E|, neg = |N|, inverted = the pairs (i, j) whose j precedes i in mfcd_topk_rows'
+ *                       `best` order (key = ~sortable_key(score), -0.0 equals +0.0, NaN above +inf, equal keys by ascending
+ *                       column), tied = the pairs with equal keys
+ *   sums [rows]         f64: R, in natural log.  NULL = the prepare pass alone: status, pos and neg are written (inverted
+ *                       and tied as 0), no score is read, X, A, B, g and the workspace may be NULL
+ *   g [rows][ldg]       nullable fp32: the gradient of coef_r R_r with respect to the score row, columns [0, m): a negative
+ *                       column j gets coef sum_{i in P \ E} sigma(a_j - a_i), a positive column i gets
+ *                       -coef sum_{j in N} sigma(a_j - a_i), a barred column 0.  Every one of the m elements of every
+ *                       requested row is written: the caller passes uninitialised memory.
+ * Status 2: offsets that are not 0 <= off[r] <= off[r+1] <= entries (excl_entries), an item outside [0, m), a list that is
+ * not strictly ascending, a row id outside [0, n), or more than 1 048 576 observed columns in the row — all checked before
+ * anything is gathered, and no address is formed from a value that failed.  Such a row gets counts -1, sum NaN and a NaN
+ * gradient row; other rows are unaffected.
+ * A score that is inf or NaN at a column that is not barred: sum NaN and an all-NaN gradient row, status 0 (the pair
+ * gradients' rule); the integer counts still follow the key order.  Scores at barred columns are never used.
+ * Deterministic: no floating-point atomic, every float sum has one owner and a fixed order, every fp32 run is at most 64
+ * terms before it is added to an f64 sum; sigma and softplus come from exp(-|v|) only, one exp and one reciprocal per pair.
+ * Two calls are bit-equal, and a row's outputs depend neither on the other rows, nor on its position in the call, nor on
+ * where a slab ends.  No allocation and no host wait.
+ * Limits: rows >= 0 (0 is success), entries >= 0, 1 <= m <= 4 194 304, n >= 1, 1 <= d <= MFCD_MAX_D in factor mode,
+ * ldx >= m, ldg >= m, pointers present where the counts are positive, excl_off and excl_items both or neither, outputs
+ * overlapping neither the inputs nor each other; MFCD_EINVAL outside them, MFCD_EALIGN for a misaligned pointer and
+ * MFCD_EWORKSPACE for a short workspace, all before anything touches the device.
+ * workspace: mfcd_implicit_rows_workspace_bytes(rows, m, d) bytes (d = 0: the dense mode), 256-byte aligned: the factor
+ * mode's slab (at most 128 MiB, at least 128 rows) and the per-(row, chunk) partials of one block of rows (at most
+ * 40 MiB); 0 = sizes out of range.  mfcd_implicit_chunk(): the columns per workgroup of the column pass;
+ * mfcd_implicit_tile(): the observed columns per tile.
+ */
+int mfcd_implicit_chunk(void);
+int mfcd_implicit_tile(void);
+size_t mfcd_implicit_rows_workspace_bytes(int rows, int m, int d);
+int mfcd_implicit_rows(const float *X, int64_t ldx, const float *A, const float *B, int d, const int32_t *row_ids, int rows,
+                       int n, int m, const int64_t *pos_off, const int32_t *pos_items, int64_t entries,
+                       const int64_t *excl_off, const int32_t *excl_items, int64_t excl_entries, const float *coef,
+                       int64_t *counts, double *sums, float *g, int64_t ldg, int32_t *status, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

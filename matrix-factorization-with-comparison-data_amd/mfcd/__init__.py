@@ -15,10 +15,11 @@
 `ratings`  the all-pairs risk, gradient and metrics on observed ratings: ragged rows (mfcd_pair_ragged_stats, _grad).
 `ratings_exact` the exact block steps of the ridge-regularised ratings risk: Newton-CG on mfcd_pair_ragged_hvp.
 `ranking` ranks of held-out entries among all admissible items and the full-catalogue ranking metrics (mfcd_rank_entries).
+`implicit` the exact observed-versus-unobserved logistic risk on implicit feedback, its fit and metrics (mfcd_implicit_rows).
 `design`   the D-optimal comparison design of every user: pairwise Frank-Wolfe on the arg-max of mfcd_pair_best_rows.
 """
-from . import (_lib, alternating, batching, design, engine, foldin, metrics, newton, pairs, population, ranking,  # noqa: F401
-               ratings, ratings_exact, topk)
+from . import (_lib, alternating, batching, design, engine, foldin, implicit, metrics, newton, pairs, population,  # noqa: F401
+               ranking, ratings, ratings_exact, topk)
 
-__all__ = ["_lib", "alternating", "batching", "design", "engine", "foldin", "metrics", "newton", "pairs", "population",
+__all__ = ["_lib", "alternating", "batching", "design", "engine", "foldin", "implicit", "metrics", "newton", "pairs", "population",
            "ranking", "ratings", "ratings_exact", "topk"]

@@ -24,6 +24,7 @@ from mfcd import alternating as _alternating
 from mfcd import design as _design
 from mfcd import engine as _engine
 from mfcd import foldin as _foldin
+from mfcd import implicit as _implicit
 from mfcd import metrics as _metrics
 from mfcd import newton as _newton
 from mfcd import pairs as _pairs
@@ -390,6 +391,76 @@ def compute_ranking_metrics(model, test, train=None, ks=(10,), min_value=None, u
         _need_gpu(model.U.device)
         model = (model.U.data, model.V.data)
     return _ranking.ranking_metrics(model, test, train, ks, min_value, users)
+
+
+def implicit_positives(data, min_value=None):
+    """Extension (not in the reference): the observed items of every user as the CSR pair (offsets int64 [n + 1], items
+    int32) that the implicit-feedback functions take — every entry of `data` (an mfcd.ratings.RatingsData), or
+    with `min_value` only the entries whose value is >= min_value: the user's other ratings are then ordinary unobserved
+    items, as in `compute_ranking_metrics`.  The pair is on the table's device.  Not part of the result dict / .pkl
+    layout."""
+    if min_value is None:
+        return data.row_off, data.item
+    keep = data.value >= float(min_value)
+    off = torch.zeros(data.n + 1, dtype=torch.int64, device=data.device)
+    off[1:] = torch.cumsum(torch.bincount(data.user[keep].long(), minlength=data.n), 0)
+    return off, data.item[keep].contiguous()
+
+
+def implicit_risk(model, data, exclude=None, normalize="pairs", min_value=None):
+    """Extension (not in the reference): the exact observed-versus-unobserved logistic risk of the model on implicit
+    feedback as a differentiable scalar — over every user, every observed item i and ALL items j the user has not
+    observed, softplus(a_j - a_i): BPR with the sampling removed, the logistic surrogate of the `auc` of
+    `compute_ranking_metrics` (include/mfcd.h mfcd_implicit_rows; nothing n x m is formed).  normalize="pairs" divides
+    the users' sums by the number of all pairs, normalize="user" averages every user's own mean.  exclude: items barred
+    per user (an mfcd.ratings.RatingsData or a CSR pair), neither observed nor unobserved.  min_value: only ratings >=
+    min_value are observed items.  Returns a 0-dim fp32 tensor on the model's device; `.backward()` fills `model.U.grad`
+    / `model.V.grad`.  fp32 models only.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _implicit.implicit_risk(model.U, model.V, implicit_positives(data, min_value), exclude, normalize)
+
+
+def train_model_implicit(model, data, optimizer, device, num_steps=1000, log_every=100, exclude=None, normalize="pairs",
+                         min_value=None):
+    """Extension (not in the reference): `train_model_ratings` on `implicit_risk(model, data, exclude, normalize)` —
+    full-batch optimiser steps on the exact risk of the observed items against all unobserved ones.  Returns (steps,
+    risks) as `train_model_ratings` does.  torch.optim.Adam takes the fused loop (mfcd.implicit.fit_implicit), any other
+    optimiser zero_grad / implicit_risk / backward / step.  Not part of the result dict / .pkl layout."""
+    _need_gpu(device)
+    model.train()
+    pos = implicit_positives(data, min_value)
+    if _engine.fused_step_applies(model, optimizer):
+        out = _implicit.fit_implicit(_engine.AdamBinding(model, optimizer), pos, num_steps, log_every, exclude, normalize)
+    else:
+        at, seen = [], []
+        for t in range(int(num_steps)):
+            optimizer.zero_grad()
+            loss = _implicit.implicit_risk(model.U, model.V, pos, exclude, normalize)
+            loss.backward()
+            optimizer.step()
+            if log_every > 0 and t % log_every == 0:
+                at.append(t)
+                seen.append(loss.detach())
+        if log_every > 0:
+            with torch.no_grad():
+                at.append(int(num_steps))
+                seen.append(_implicit.implicit_risk(model.U, model.V, pos, exclude, normalize))
+        out = (at, torch.stack(seen).double().cpu().tolist() if seen else [])
+    model.eval()
+    return out
+
+
+def compute_implicit_metrics(model, data, exclude=None, min_value=None):
+    """Extension (not in the reference): the exact per-user `auc`, `auc_midrank` (half credit for tied pairs) and
+    `log_likelihood` of the model on implicit feedback, over all (observed, unobserved) pairs of every user, with the
+    counts pos, neg, inverted and tied (include/mfcd.h mfcd_implicit_rows; mfcd.implicit.implicit_metrics has the
+    formulas).  Typically data is a held-out split and exclude the training split.  Every key is the mean over the
+    users that have a pair, every key with the suffix `_per_user` a numpy array (NaN for a user without one).  `model`
+    may also be a dense GPU tensor X or a `FactoredMatrix`.  Not part of the result dict / .pkl layout."""
+    if isinstance(model, nn.Module):
+        _need_gpu(model.U.device)
+        model = (model.U.data, model.V.data)
+    return _implicit.implicit_metrics(model, None, implicit_positives(data, min_value), exclude)
 
 
 def ratings_hvp(model, data, dU, dV, s=1.0, skip_ties=False, gauss_newton=False):
