@@ -1316,6 +1316,39 @@ int mfcd_implicit_rows(const float *X, int64_t ldx, const float *A, const float 
                        int64_t *counts, double *sums, float *g, int64_t ldg, int32_t *status, void *workspace,
                        size_t workspace_bytes, void *stream);
 
+/*
+ * The Hessian of mfcd_implicit_rows' risk with respect to the score row, applied to a direction (no reference
+ * counterpart; mfcd/implicit.py, mfcd/implicit_exact.py).  Rows, lists, coef, status and limits as mfcd_implicit_rows takes
+ * them.  For a requested row with scores a, direction y and the weights
+ *   w_ij = sigma(a_j - a_i) sigma(a_i - a_j)   for i in P \ E, j in N
+ * the outputs are a bipartite weighted Laplacian applied to y, and its diagonal:
+ *   q [rows][ldq]       fp32, columns [0, m): a positive column i gets coef sum_{j in N} w_ij (y_i - y_j), a negative
+ *                       column j gets coef sum_{i in P \ E} w_ij (y_j - y_i), a barred column 0
+ *   deg [rows][ldd]     nullable fp32: coef times the sum of w over the column's partners (the Jacobi preconditioner of
+ *                       a solve with the operator); a barred column 0.  q does not depend on whether deg is asked for.
+ * Every one of the m elements of every requested row is written: the caller passes uninitialised memory.
+ * Scores and direction both come dense — X [n][ldx], Y [n][ldy], addressed by row id; A, B, Ay, By NULL — or both by
+ * factors of one width d — X == Y == NULL, scores A [n][d] . B [m][d], direction Ay [n][d] . By [m][d], each through
+ * mfcd_topk_rows' score kernel into a bounded slab of its own, in blocks of rows; nothing n x m is formed.  Inputs may
+ * alias one another (a user step passes B == By, an item step A == Ay).
+ * The difference of the direction is formed per pair: a constant direction row gives q exactly +0, as does a row with
+ * pos neg = 0.  Status 2 (see mfcd_implicit_rows): NaN rows of q and deg.  A score or a direction that is inf or NaN at
+ * a column that is not barred: NaN rows of q and deg, status 0; values at barred columns are never used.
+ * Deterministic: no atomic, one writer per output, fp32 runs of at most 64 terms before an f64 sum, one exp and one
+ * reciprocal per pair and pass.  Two calls are bit-equal, and a row's outputs depend neither on the other rows, nor on
+ * its position in the call, nor on where a slab ends.  No allocation and no host wait.
+ * MFCD_EINVAL, MFCD_EALIGN and MFCD_EWORKSPACE as for mfcd_implicit_rows, before anything touches the device.
+ * workspace: mfcd_implicit_hvp_rows_workspace_bytes(rows, m, d) bytes (d = 0: the dense mode), 256-byte aligned: the two
+ * slabs of the factor mode and one int32 per (row, chunk) of a block of rows; 0 = sizes out of range.
+ */
+size_t mfcd_implicit_hvp_rows_workspace_bytes(int rows, int m, int d);
+int mfcd_implicit_hvp_rows(const float *X, int64_t ldx, const float *Y, int64_t ldy, const float *A, const float *B,
+                           const float *Ay, const float *By, int d, const int32_t *row_ids, int rows, int n, int m,
+                           const int64_t *pos_off, const int32_t *pos_items, int64_t entries, const int64_t *excl_off,
+                           const int32_t *excl_items, int64_t excl_entries, const float *coef, float *q, int64_t ldq,
+                           float *deg, int64_t ldd, int32_t *status, void *workspace, size_t workspace_bytes,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

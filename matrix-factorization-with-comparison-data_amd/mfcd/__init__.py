@@ -16,10 +16,11 @@
 `ratings_exact` the exact block steps of the ridge-regularised ratings risk: Newton-CG on mfcd_pair_ragged_hvp.
 `ranking` ranks of held-out entries among all admissible items and the full-catalogue ranking metrics (mfcd_rank_entries).
 `implicit` the exact observed-versus-unobserved logistic risk on implicit feedback, its fit and metrics (mfcd_implicit_rows).
+`implicit_exact` the exact block steps of the ridge-regularised implicit risk: Newton-CG on mfcd_implicit_hvp_rows.
 `design`   the D-optimal comparison design of every user: pairwise Frank-Wolfe on the arg-max of mfcd_pair_best_rows.
 """
-from . import (_lib, alternating, batching, design, engine, foldin, implicit, metrics, newton, pairs, population,  # noqa: F401
-               ranking, ratings, ratings_exact, topk)
+from . import (_lib, alternating, batching, design, engine, foldin, implicit, implicit_exact, metrics, newton,  # noqa: F401
+               pairs, population, ranking, ratings, ratings_exact, topk)
 
-__all__ = ["_lib", "alternating", "batching", "design", "engine", "foldin", "implicit", "metrics", "newton", "pairs", "population",
-           "ranking", "ratings", "ratings_exact", "topk"]
+__all__ = ["_lib", "alternating", "batching", "design", "engine", "foldin", "implicit", "implicit_exact", "metrics", "newton", "pairs",
+           "population", "ranking", "ratings", "ratings_exact", "topk"]

@@ -147,6 +147,9 @@ SIGNATURES = {
     "mfcd_implicit_rows_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "mfcd_implicit_rows": (_i32, [_vp, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64] +
                            [_vp] * 4 + [_i64, _vp, _vp, _sz, _vp]),
+    "mfcd_implicit_hvp_rows_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "mfcd_implicit_hvp_rows": (_i32, [_vp, _i64, _vp, _i64] + [_vp] * 4 + [_i32, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp,
+                                      _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
 }
 
 TUNE_KEYS = {"resident_lookahead": 3, "resident_spin_limit": 5, "uvt_target_wgs": 9, "uvt_min_stages": 10,

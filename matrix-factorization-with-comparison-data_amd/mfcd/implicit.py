@@ -8,10 +8,12 @@ E_u is an optional exclusion list, as in `ranking.rank_entries`.  This is BPR wi
 surrogate of the per-user AUC that `ranking.ranking_metrics` reports.
 
 `implicit_rows` is the kernel call (per-row counts, risk sums and the gradient with respect to the score row),
-`implicit_risk` the risk of a model as a differentiable scalar, `implicit_metrics` the exact per-user AUC and
-log-likelihood, `fit_implicit` the fused loop of block sweeps and one dense Adam step.  The matrix is a dense fp32 GPU
-tensor, a `generation_data.FactoredMatrix` or a pair (A, B) of GPU tensors, as for `ranking.rank_entries`.  There is no
-CPU form of any of it."""
+`implicit_hvp_rows` its second-order twin (include/mfcd.h: mfcd_implicit_hvp_rows) and `implicit_hvp` the product of the
+risk's Hessian with a direction in the tables (the exact block steps on it are mfcd/implicit_exact.py), `implicit_risk`
+the risk of a model as a differentiable scalar, `implicit_metrics` the exact per-user AUC and log-likelihood,
+`fit_implicit` the fused loop of block sweeps and one dense Adam step.  The matrix is a dense fp32 GPU tensor, a
+`generation_data.FactoredMatrix` or a pair (A, B) of GPU tensors, as for `ranking.rank_entries`.  There is no CPU form of
+any of it."""
 from collections import namedtuple
 
 import numpy as np
@@ -63,6 +65,23 @@ def _lists(positives, exclude, ids64, nrows, n, m, dev):
     return p_off, p_items, p_items.numel(), e_off, e_items, excl_entries
 
 
+def _request(positives, exclude, rows, coef, n, m, dev, who):
+    """What the row entries share → (ids int32 or None, the number of requested rows, the two lists, coef checked)."""
+    if rows is None:
+        ids64, ids, nrows = None, None, n
+    else:
+        ids64 = torch.as_tensor(rows).reshape(-1).to(device=dev, dtype=torch.int64)
+        ids, nrows = ids64.to(torch.int32).contiguous(), ids64.numel()
+    lists = _lists(positives, exclude, ids64, nrows, n, m, dev)
+    if coef is not None:
+        if not torch.is_tensor(coef) or not coef.is_cuda or coef.dtype != torch.float32:
+            raise _lib.MfcdError(f"{who} needs coef as a float32 GPU tensor (there is no CPU fallback)")
+        if coef.numel() != nrows:
+            raise ValueError(f"{coef.numel()} coefficients for {nrows} requested rows")
+        coef = coef.reshape(-1).contiguous()
+    return ids, nrows, lists, coef
+
+
 def implicit_rows(X, positives, exclude=None, rows=None, grad=False, coef=None, prepare_only=False):
     """→ `ImplicitRows`: per requested row the counts, the risk sum R and, with grad=True, the gradient of coef R with
     respect to the score row.
@@ -83,18 +102,7 @@ def implicit_rows(X, positives, exclude=None, rows=None, grad=False, coef=None, 
     counts -1, sum NaN and a NaN gradient row; a row with an inf or NaN score at a column that is not barred has status
     0, sum NaN and a NaN gradient row.  Deterministic: two calls are bit-equal."""
     Xd, A, B, n, m, d, dev = _resolve(X, None)
-    if rows is None:
-        ids64, ids, nrows = None, None, n
-    else:
-        ids64 = torch.as_tensor(rows).reshape(-1).to(device=dev, dtype=torch.int64)
-        ids, nrows = ids64.to(torch.int32).contiguous(), ids64.numel()
-    lists = _lists(positives, exclude, ids64, nrows, n, m, dev)
-    if coef is not None:
-        if not torch.is_tensor(coef) or not coef.is_cuda or coef.dtype != torch.float32:
-            raise _lib.MfcdError("implicit_rows needs coef as a float32 GPU tensor (there is no CPU fallback)")
-        if coef.numel() != nrows:
-            raise ValueError(f"{coef.numel()} coefficients for {nrows} requested rows")
-        coef = coef.reshape(-1).contiguous()
+    ids, nrows, lists, coef = _request(positives, exclude, rows, coef, n, m, dev, "implicit_rows")
     counts = torch.empty((nrows, 4), dtype=torch.int64, device=dev)
     status = torch.empty(nrows, dtype=torch.int32, device=dev)
     if prepare_only:
@@ -106,6 +114,63 @@ def implicit_rows(X, positives, exclude=None, rows=None, grad=False, coef=None, 
     g = torch.empty((nrows, m), dtype=torch.float32, device=dev) if grad else None
     _launch(Xd, A, B, n, m, d, dev, ids, nrows, *lists, coef, counts, sums, g, status)
     return ImplicitRows(counts, sums, status, g)
+
+
+def _launch_hvp(Xd, Yd, A, B, Ay, By, n, m, d, dev, ids, nrows, p_off, p_items, entries, e_off, e_items, excl_entries, coef,
+                q, deg, status):
+    """One mfcd_implicit_hvp_rows call on checked device tensors: dense (Xd, Yd) or by factors (A, B, Ay, By)."""
+    L = _lib.load()
+    dense = Xd is not None
+    nbytes = L.mfcd_implicit_hvp_rows_workspace_bytes(nrows, m, 0 if dense else d)
+    if nbytes == 0:
+        raise _lib.MfcdError(f"implicit_hvp_rows: sizes out of range (rows {nrows}, m {m}, d {d})")
+    ws = _lib.workspace(nbytes, dev)
+    _lib.check(L.mfcd_implicit_hvp_rows(Xd.data_ptr() if dense else None, Xd.stride(0) if dense else 0,
+                                        Yd.data_ptr() if dense else None, Yd.stride(0) if dense else 0,
+                                        _lib.ptr(A), _lib.ptr(B), _lib.ptr(Ay), _lib.ptr(By), d, _lib.ptr(ids), nrows, n, m,
+                                        _lib.ptr(p_off), _lib.ptr(p_items) if entries else None, entries, _lib.ptr(e_off),
+                                        _lib.ptr(e_items), excl_entries, _lib.ptr(coef), _lib.ptr(q) if nrows else None,
+                                        q.stride(0), _lib.ptr(deg), deg.stride(0) if deg is not None else m,
+                                        _lib.ptr(status) if nrows else None, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+
+
+def _shape(X):
+    """(n, m, d) of a dense matrix (d = 0) or of a factor pair, whatever its device; None where `_resolve` is to refuse."""
+    if torch.is_tensor(X):
+        return (X.shape[0], X.shape[1], 0) if X.dim() == 2 else None
+    A, B = (X.A, X.B) if _lib.is_factored(X) else X if isinstance(X, (tuple, list)) and len(X) == 2 else (None, None)
+    ok = torch.is_tensor(A) and torch.is_tensor(B) and A.dim() == 2 and B.dim() == 2
+    return (A.shape[0], B.shape[0], A.shape[1]) if ok else None
+
+
+def implicit_hvp_rows(X, Y, positives, exclude=None, rows=None, coef=None, deg=False):
+    """→ (q, deg or None, status): the Hessian of coef R of `implicit_rows` with respect to the score row, applied to
+    the direction rows Y — per requested row, with w_ij = sigmoid'(a_j - a_i) over its (observed, unobserved) pairs,
+    q_i = coef sum_j w_ij (y_i - y_j) for an observed column, q_j = coef sum_i w_ij (y_j - y_i) for an unobserved one and 0
+    for a barred one: a bipartite weighted Laplacian.  deg=True also returns its diagonal, coef sum w over the column's
+    partners (the Jacobi preconditioner).
+
+    X, Y       the scores and the direction: both dense fp32 GPU tensors [n, m], or both factors — a FactoredMatrix or a
+               pair (A, B) of GPU tensors — of one width d (a user step passes the same B twice, an item step the same A)
+    positives, exclude, rows, coef   as `implicit_rows` takes them
+
+    q and deg are fp32 [rows, m], status int32 [rows].  A constant direction row, and a row with pos neg = 0, give exactly
+    +0.  A row with an invalid list or row number has status 2 and NaN rows; a row with an inf or NaN score or direction
+    at a column that is not barred has status 0 and NaN rows.  Deterministic: two calls are bit-equal, and q does not
+    depend on `deg`."""
+    if torch.is_tensor(X) != torch.is_tensor(Y):
+        raise ValueError("the scores and the direction must both be dense or both be factor pairs")
+    sx, sy = _shape(X), _shape(Y)
+    if sx is not None and sy is not None and sx != sy:         # a shape `_shape` cannot read is `_resolve`'s to refuse
+        raise ValueError(f"scores of shape [n, m, d] = {list(sx)} and a direction of shape {list(sy)}")
+    Xd, A, B, n, m, d, dev = _resolve(X, None)
+    Yd, Ay, By, _, _, _, _ = _resolve(Y, None)
+    ids, nrows, lists, coef = _request(positives, exclude, rows, coef, n, m, dev, "implicit_hvp_rows")
+    q = torch.empty((nrows, m), dtype=torch.float32, device=dev)
+    dg = torch.empty((nrows, m), dtype=torch.float32, device=dev) if deg else None
+    status = torch.empty(nrows, dtype=torch.int32, device=dev)
+    _launch_hvp(Xd, Yd, A, B, Ay, By, n, m, d, dev, ids, nrows, *lists, coef, q, dg, status)
+    return q, dg, status
 
 
 def _tables(U, V, who):
@@ -181,6 +246,36 @@ class _Plan:
         # a user without a pair has sum 0 and coefficient 0; a NaN sum stays NaN
         return (self.sums * self.coef64).sum(), dU, dV
 
+    def hvp_sweep(self, U, V, dU, dV, gauss_newton):
+        """One pass over the users in row blocks → (HU, HV) f64: per block the Laplacian applied to the two parts of
+        the score-space direction dU[b] V^T + U[b] dV^T (two kernel calls whose results add: the operator is linear),
+        carried back by library GEMMs; the exact form adds the gradient block's bilinear terms g dV and g^T dU."""
+        n, m, d, rb = self.n, self.m, U.shape[1], self.row_block
+        p_off, p_items, entries, e_off, e_items, excl_entries = self.lists
+        V64, dV64 = V.double(), dV.double()
+        HU = torch.empty((n, d), dtype=torch.float64, device=self.dev)
+        HV = torch.zeros((m, d), dtype=torch.float64, device=self.dev)
+        q = torch.empty((2, min(rb, n), m), dtype=torch.float32, device=self.dev)
+        for u0 in range(0, n, rb):
+            u1 = min(n, u0 + rb)
+            lists = (p_off[u0:u1 + 1], p_items, entries, e_off[u0:u1 + 1] if e_off is not None else None, e_items,
+                     excl_entries)
+            for k, (Ay, By) in enumerate(((dU, V), (U, dV))):
+                _launch_hvp(None, None, U, V, Ay, By, n, m, d, self.dev, self.ids[u0:u1], u1 - u0, *lists,
+                            self.coef[u0:u1], q[k, :u1 - u0], None, self.status[u0:u1])
+            Q = q[0, :u1 - u0].double() + q[1, :u1 - u0].double()
+            U64 = U[u0:u1].double()
+            torch.mm(Q, V64, out=HU[u0:u1])
+            HV.addmm_(Q.t(), U64)
+            if not gauss_newton:
+                g = q[0, :u1 - u0]
+                _launch(None, U, V, n, m, d, self.dev, self.ids[u0:u1], u1 - u0, *lists, self.coef[u0:u1],
+                        self.counts[u0:u1], self.sums[u0:u1], g, self.status[u0:u1])
+                G = g.double()
+                HU[u0:u1].addmm_(G, dV64)
+                HV.addmm_(G.t(), dU[u0:u1].double())
+        return HU, HV
+
 
 class _ImplicitRisk(torch.autograd.Function):
     """The normalised risk as a function of the factor tables.  With a gradient required, forward computes the value and
@@ -217,6 +312,21 @@ def implicit_risk(U, V, data, exclude=None, normalize="pairs", row_block=None):
     plan = _Plan(U.shape[0], V.shape[0], U.device, data, exclude, normalize, row_block)
     need = torch.is_grad_enabled() and (U.requires_grad or V.requires_grad)
     return _ImplicitRisk.apply(U, V, plan, need)
+
+
+def implicit_hvp(U, V, dU, dV, data, exclude=None, normalize="pairs", row_block=None, gauss_newton=False):
+    """→ (HU, HV), f64 device tensors shaped like U and V: the Hessian of `implicit_risk(U, V, data, exclude, normalize)`
+    with respect to the two tables, applied to the direction (dU, dV) — one sweep over the users in blocks of `row_block`
+    rows (mfcd_implicit_hvp_rows on the score-space direction dU V^T + U dV^T, library GEMMs back to the tables), nothing
+    n x m formed.  gauss_newton=True leaves out the bilinear cross term (the gradient block times the other table's
+    direction), as `ratings.ratings_hvp` does: that form is positive semi-definite."""
+    if all(torch.is_tensor(t) for t in (U, V, dU, dV)) and (dU.shape != U.shape or dV.shape != V.shape):
+        raise ValueError(f"directions of shapes {tuple(dU.shape)}, {tuple(dV.shape)} for tables of shapes "
+                         f"{tuple(U.shape)}, {tuple(V.shape)}")
+    U, V = _tables(U, V, "the implicit Hessian-vector product")
+    dU, dV = _tables(dU, dV, "the implicit Hessian-vector product")
+    plan = _Plan(U.shape[0], V.shape[0], U.device, data, exclude, normalize, row_block)
+    return plan.hvp_sweep(U, V, dU, dV, bool(gauss_newton))
 
 
 def metrics_from_counts(counts, sums, status, tied_before=None):

@@ -25,6 +25,7 @@ from mfcd import design as _design
 from mfcd import engine as _engine
 from mfcd import foldin as _foldin
 from mfcd import implicit as _implicit
+from mfcd import implicit_exact as _implicit_exact
 from mfcd import metrics as _metrics
 from mfcd import newton as _newton
 from mfcd import pairs as _pairs
@@ -461,6 +462,73 @@ def compute_implicit_metrics(model, data, exclude=None, min_value=None):
         _need_gpu(model.U.device)
         model = (model.U.data, model.V.data)
     return _implicit.implicit_metrics(model, None, implicit_positives(data, min_value), exclude)
+
+
+def implicit_hvp(model, data, dU, dV, exclude=None, normalize="pairs", min_value=None, gauss_newton=False):
+    """Extension (not in the reference): `population_hvp` on implicit feedback — the Hessian of `implicit_risk(model, data,
+    exclude, normalize)` with respect to the factor tables, applied to the direction (dU [n, d], dV [m, d]) → (HU, HV) f64
+    on the model's device (include/mfcd.h mfcd_implicit_hvp_rows, the bipartite Laplacian of every user's observed-versus-
+    unobserved risk, and library GEMMs per block of users; nothing n x m is formed).  gauss_newton=True drops the terms
+    that hold the risk's gradient: the product is then positive semidefinite.  fp32 models only.  Not part of the result
+    dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _implicit.implicit_hvp(model.U.data, model.V.data, dU, dV, implicit_positives(data, min_value), exclude, normalize,
+                                  None, gauss_newton)
+
+
+def fit_users_implicit(V_or_model, data, weight_decay, exclude=None, coef=None, min_value=None):
+    """Extension (not in the reference): fold-in on implicit feedback — with the item table held fixed, the vectors of the
+    users of `data` from their observed items alone: for every user the minimiser of  c_u * (the user's observed-versus-
+    unobserved risk sum) + (wd / 2) |u|^2,  started at zero (mfcd.implicit_exact.implicit_user_step: Newton-CG on
+    mfcd_implicit_hvp_rows).  The users need not have been in training; data.m must be the number of rows of V.
+    V_or_model: a model or a bare fp32 V [m, d] on the GPU.  c_u = 1 / (the pairs of `data`), or `coef` (a scalar or one
+    value per user): pass the training table's normaliser so that the ridge weighs as it did in training.  Returns the
+    PopulationStepResult (rows [data.n, d], ready for `recommend_items`; status 0 certified / 1 stopped / 2 invalid,
+    newton_iters, cg_iters, objective_before, objective_after, grad_ratio); a user without a pair gets the zero row.
+    weight_decay must be > 0.  Not part of the result dict / .pkl layout."""
+    V = V_or_model.V.data if hasattr(V_or_model, "V") and hasattr(V_or_model, "U") else V_or_model
+    if not torch.is_tensor(V):
+        raise TypeError("fit_users_implicit takes a model or its V table")
+    _need_gpu(V.device)
+    return _implicit_exact.implicit_user_step(None, V, implicit_positives(data, min_value), float(weight_decay), exclude,
+                                              coef=coef)
+
+
+def refit_users_implicit(model, data, weight_decay, exclude=None, normalize="pairs", min_value=None):
+    """Extension (not in the reference): `refit_users_ratings` on implicit feedback — for the model's own V, the best
+    response of every user's row on  F = implicit_risk + (wd / 2)(|U|^2 + |V|^2),  the objective whose stationary points
+    `train_model_implicit` approaches under Adam's coupled weight decay, by mfcd.implicit_exact.implicit_user_step
+    started at `model.U`.  Returns (result, gain): the PopulationStepResult and, per user, gain = objective_before -
+    objective_after >= 0: what the trained row still had to gain in F with V fixed.  weight_decay must be > 0.  The
+    model is not changed.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    result = _implicit_exact.implicit_user_step(model.U.data, model.V.data, implicit_positives(data, min_value),
+                                                float(weight_decay), exclude, normalize)
+    return result, result.objective_before - result.objective_after
+
+
+def refit_items_implicit(model, data, weight_decay, exclude=None, normalize="pairs", min_value=None):
+    """Extension (not in the reference): the mirror of `refit_users_implicit` — for the model's own U, the minimiser over
+    all of V of F (one problem: a user's pairs couple the items), by mfcd.implicit_exact.implicit_item_step started at
+    `model.V`.  Returns (result, gain) with result.rows the best-response V [m, d] and gain the 0-dim decrease of F.
+    weight_decay must be > 0.  The model is not changed.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.V.device)
+    result = _implicit_exact.implicit_item_step(model.U.data, model.V.data, implicit_positives(data, min_value),
+                                                float(weight_decay), exclude, normalize)
+    return result, result.objective_before - result.objective_after
+
+
+def train_model_implicit_exact(model, data, weight_decay, sweeps=10, exclude=None, normalize="pairs", min_value=None):
+    """Extension (not in the reference): `train_model_implicit` by exact block steps instead of Adam — `sweeps` sweeps of
+    one exact user step and one exact item step of  F = implicit_risk + (wd / 2)(|U|^2 + |V|^2)
+    (mfcd.implicit_exact.fit_implicit_exact), each a Newton-CG solve on mfcd_implicit_hvp_rows, in place on the model's
+    tables.  Returns F after every sub-step as a list of [after the user step, after the item step] per sweep; it does
+    not increase.  fp32 models only; weight_decay must be > 0.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    result = _implicit_exact.fit_implicit_exact(model.U.data, model.V.data, implicit_positives(data, min_value),
+                                                float(weight_decay), sweeps, exclude, normalize)
+    model.eval()
+    return result.history.cpu().tolist()
 
 
 def ratings_hvp(model, data, dU, dV, s=1.0, skip_ties=False, gauss_newton=False):
