@@ -1349,6 +1349,83 @@ int mfcd_implicit_hvp_rows(const float *X, int64_t ldx, const float *Y, int64_t 
                            float *deg, int64_t ldd, int32_t *status, void *workspace, size_t workspace_bytes,
                            void *stream);
 
+/*
+ * The exact user step on implicit feedback in one launch (no reference counterpart): what mfcd/implicit_exact.py's
+ * implicit_user_step computes with a chain of small launches per Newton iteration; the serving-time fold-in of a user
+ * who was not in training.  The two CSR lists are mfcd_implicit_rows': pos_off / pos_items the row's observed columns,
+ * excl_off / excl_items its barred columns (both NULL = nothing is barred), both strictly ascending within a row.  With
+ * P = observed \ barred, N = [0, m) \ (observed u barred) and V [m][d] fixed, U_out[r] minimises
+ *     f(u) = coef_r * sum over i in P, j in N of softplus(a_j - a_i) + (l2 / 2) |u|^2,   a_c = u . v_c.
+ * coef: f64 [rows] on the device, NULL = 1.  U_init = NULL starts every row at 0 and is bit-equal to a zero U_init.
+ * Algorithm (mfcd/population.py's _newton with solver "direct", per row; tests/implicit_foldin_model.py restates it):
+ *   1. u = U_init[r] or 0, t = 1, iterations = 0.
+ *   2. g = coef (sum_j g_j v~_j - sum_i G_i v~_i) + l2 u, g_j = sum_i sigmoid(a_j - a_i), G_i = sum_j sigmoid(a_j - a_i).
+ *      |g|_2 <= gtol l2 |u|_inf: status 0.  Otherwise iterations == max_newton: status 1.
+ *   3. If u moved since the direction was formed, or there is none yet:
+ *      H = coef sum_{i,j} sigmoid'(a_i - a_j)(v~_i - v~_j)(v~_i - v~_j)^T + l2 I, p = -H^{-1} g by Cholesky in LDS; a
+ *      pivot that is not positive: p = -g / mean(diag H).
+ *   4. f_t = f(u + t p), iterations += 1.  f_t <= f + 1e-4 t (g . p) (a NaN f_t fails): u += t p, t = min(2 t, 1).
+ *      Otherwise t /= 2, the direction is kept, and t < 2^-12 ends the row with status 1.  Back to 2.
+ *      The inequality is taken on the two values of f; when that fails, on the decrease f(u + t p) - f(u) summed pair
+ *      by pair (softplus(a + h) - softplus(a) = log1p(sigmoid(a) expm1(h)) for |h| < 1), which resolves decreases below
+ *      the fp32 rounding of f itself.  Either evaluation accepts, as in mfcd_ratings_fold_in_users; the second is
+ *      evaluated only when the first fails, which decides the same thing.  It changes the outcome where coef times the
+ *      risk (fp32) outweighs the ridge part (f64) of f; where the ridge dominates, the values alone decide the same.
+ * The sum of step 3 is formed by its bipartite structure, with w_ij = sigmoid'(a_i - a_j), D_i = sum_j w_ij,
+ * D_j = sum_i w_ij, y_j = sum_i w_ij v~_i:  (T + T^T) / 2,  T = sum_i v~_i (D_i v~_i)^T + sum_j v~_j (D_j v~_j - 2 y_j)^T.
+ * Precision: u, g, H, the solves, f and every dot product over d are f64.  v~_c is V[c] minus the f64 mean of the rows
+ * of V that P names, rounded to fp32 once (everything above depends on differences of the v_c only); a_c is an f64 chain
+ * over k rounded to fp32 once, formed again from V in every pass: nothing per column is kept.  The pair arithmetic is
+ * fp32, csrc/pairs_common.h's, in runs of at most 64 terms widened to f64; y_j is formed per column in fp32 runs of 64
+ * positives on the vector pipe, widened to f64, and D_j v~_j - 2 y_j is rounded to fp32 once; T is added in f64.  U_out
+ * is the f64 iterate rounded to fp32 once.
+ * Outputs, as mfcd_ratings_fold_in_users': objective [rows][2] = {f at the start, f at the returned row}; grad_ratio
+ * [rows] = |g|_2 / (l2 |u|_inf) at the returned row; iters_status [rows][2] = {iterations, status}; info [rows][d][d] =
+ * the sum of step 3 at the returned row, without coef and ridge ([p][q] and [q][p] bit-equal; one more Hessian pass,
+ * taken only when info is not NULL; with max_newton = 0 the information at the start row).  objective, grad_ratio and
+ * info may be NULL, and a row's other outputs do not depend on it.
+ * Statuses: 0 certified; 1 stopped (iteration cap, or no Armijo decrease); 2 invalid data: offsets that are not
+ * 0 <= off[r] <= off[r+1] <= entries (excl_entries), an item outside [0, m), a list that is not strictly ascending, a
+ * non-finite V row of an admissible column, a non-finite U_init row, a coef that is not finite and positive — the lists
+ * are checked before any gather, no address is formed from a value that failed — the row, its objective, grad_ratio
+ * and info are NaN, 0 iterations; 3: more than mfcd_implicit_fold_in_max_pos() admissible positives, or |P| |N| above
+ * mfcd_implicit_fold_in_max_pairs(): outputs as for 2.  Status 3 is decided from the list lengths wherever they decide
+ * it (always when nothing is barred: at least pos_len - excl_len positives, m - pos_len - excl_len negatives), and then
+ * nothing of the row beyond them is read; otherwise from the counts, after the lists were checked.  A row with
+ * |P| |N| = 0 is answered in closed form: row +0, status 0, 0 iterations, objective {(l2 / 2) |U_init[r]|^2, 0},
+ * grad_ratio 0, info +0.
+ * One 256-thread workgroup owns a row from start to finish; threads own columns, in stages of
+ * mfcd_implicit_fold_in_chunk() = 2048 columns; no floating-point atomics, every sum has one owner and a fixed order
+ * that depends on the row alone: two calls are bit-equal and a row's outputs depend neither on the other rows, nor on
+ * its position, nor on which optional outputs are asked for.  No allocation and no host wait.
+ * Caps: mfcd_implicit_fold_in_max_pos() = 4608 (16 bytes of LDS per admissible positive);
+ * mfcd_implicit_fold_in_max_pairs() = 11 534 336 (11 x 2^20): one workgroup takes a whole row, and a row at the cap
+ * should stay under a second at max_newton = 20.  Measured on one MI355X (profiles/implicit_fold_in.txt, one row of
+ * 1024 observed items among 8192, d = 64): a value-and-gradient pass runs at 2.28 G pairs/s on its compute unit and a
+ * Hessian pass at 0.270 G pairs/s, 4.15 ns per pair for an iteration of one pass each, so a row at the cap takes
+ * 11 534 336 x 20 x 4.15 ns = 0.96 s (2^24 pairs: 1.39 s).  It is not a tuning knob.  implicit_user_step takes rows of
+ * any size.  The cap bounds the pair work only: every pass also re-forms m scores of width d from V, about five times
+ * per iteration, which no cap bounds — a short row in a very large catalogue is not held under a second by it (10
+ * observed items of 65 536 at d = 64: 129 ms for 256 rows side by side, nearly all of it scoring).
+ * workspace: mfcd_implicit_fold_in_workspace_bytes(rows, m, d) = 256 whatever the sizes (0 = sizes out of range): a
+ * row's state lives in its workgroup's LDS; calls of more than 2^20 rows go through in launches of 2^20.
+ * Limits: 1 <= d <= mfcd_implicit_fold_in_max_d() = 64, 1 <= m <= 4 194 304, rows >= 0 (0 = success, nothing launched),
+ * entries >= 0, excl_off and excl_items both or neither (excl_entries 0 without them), l2 finite and > 0, gtol finite and
+ * >= 0, 0 <= max_newton <= 1000, V, pos_off, U_out and iters_status not NULL, pos_items where entries > 0, the outputs
+ * overlapping none of the inputs nor each other; MFCD_EINVAL outside them and MFCD_EWORKSPACE for a short workspace,
+ * both before anything touches the device.
+ */
+int mfcd_implicit_fold_in_max_d(void);
+int mfcd_implicit_fold_in_max_pos(void);
+int64_t mfcd_implicit_fold_in_max_pairs(void);
+int mfcd_implicit_fold_in_chunk(void);
+size_t mfcd_implicit_fold_in_workspace_bytes(int rows, int m, int d);
+int mfcd_implicit_fold_in_users(const float *V, int m, int d, const int64_t *pos_off, const int32_t *pos_items,
+                                int64_t entries, const int64_t *excl_off, const int32_t *excl_items, int64_t excl_entries,
+                                int rows, const double *coef, double l2, const float *U_init, int max_newton, double gtol,
+                                float *U_out, double *objective, double *grad_ratio, int32_t *iters_status, double *info,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

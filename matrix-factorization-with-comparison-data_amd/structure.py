@@ -26,6 +26,7 @@ from mfcd import engine as _engine
 from mfcd import foldin as _foldin
 from mfcd import implicit as _implicit
 from mfcd import implicit_exact as _implicit_exact
+from mfcd import implicit_foldin as _implicit_foldin
 from mfcd import metrics as _metrics
 from mfcd import newton as _newton
 from mfcd import pairs as _pairs
@@ -505,6 +506,44 @@ def refit_users_implicit(model, data, weight_decay, exclude=None, normalize="pai
     result = _implicit_exact.implicit_user_step(model.U.data, model.V.data, implicit_positives(data, min_value),
                                                 float(weight_decay), exclude, normalize)
     return result, result.objective_before - result.objective_after
+
+
+def fold_in_users_implicit(V_or_model, data, weight_decay, exclude=None, coef=None, min_value=None):
+    """Extension (not in the reference): `fit_users_implicit` in one launch — the same problem, start (zero), normaliser
+    and PopulationStepResult, solved by mfcd.implicit_foldin.implicit_fold_in_users: one workgroup per user runs the whole
+    damped Newton iteration with the user's d x d Hessian in LDS (include/mfcd.h mfcd_implicit_fold_in_users), d <= 64;
+    the serving-time step, its rows ready for `recommend_items`.  `cg_iters` is all zeros, and a user beyond
+    mfcd_implicit_fold_in_max_pos() admissible observed items or mfcd_implicit_fold_in_max_pairs() pairs gets status 3
+    and a NaN row (`fit_users_implicit` takes any size).  weight_decay must be > 0.  Not part of the result dict / .pkl
+    layout."""
+    V = V_or_model.V.data if hasattr(V_or_model, "V") and hasattr(V_or_model, "U") else V_or_model
+    if not torch.is_tensor(V):
+        raise TypeError("fold_in_users_implicit takes a model or its V table")
+    _need_gpu(V.device)
+    return _implicit_foldin.implicit_fold_in_users(None, V, implicit_positives(data, min_value), float(weight_decay),
+                                                   exclude, coef=coef)
+
+
+def refit_users_implicit_kernel(model, data, weight_decay, exclude=None, normalize="pairs", min_value=None):
+    """Extension (not in the reference): `refit_users_implicit` in one launch — (result, gain) with the same meaning, the
+    users' best responses started at `model.U`, by mfcd.implicit_foldin.implicit_fold_in_users (d <= 64).  weight_decay
+    must be > 0.  The model is not changed.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    result = _implicit_foldin.implicit_fold_in_users(model.U.data, model.V.data, implicit_positives(data, min_value),
+                                                     float(weight_decay), exclude, normalize)
+    return result, result.objective_before - result.objective_after
+
+
+def implicit_user_information(model, data, exclude=None, min_value=None):
+    """Extension (not in the reference): `user_information` on implicit feedback — for every user of `data` the d x d
+    Hessian of the user's observed-versus-unobserved risk sum in the user's row at the model's tables, H_u = sum over the
+    user's (observed, unobserved) pairs of sigmoid'(a_i - a_j) (v_i - v_j)(v_i - v_j)^T → mfcd.pairs.UserInformation
+    (info f64 [n, d, d], weight f64 [n] the user's pairs, status int32 [n]) on the model's device (one call of
+    mfcd_implicit_fold_in_users without a Newton iteration; d <= 64).  fp32 models only.  Not part of the result dict /
+    .pkl layout."""
+    _need_gpu(model.U.device)
+    return _implicit_foldin.implicit_user_information(model.U.data, model.V.data, implicit_positives(data, min_value),
+                                                      exclude)
 
 
 def refit_items_implicit(model, data, weight_decay, exclude=None, normalize="pairs", min_value=None):

@@ -1,7 +1,7 @@
 """What the bench_pair*.py tools share: the timing loops, the full law they time under, and the comparison
 of a build against a build of the parent commit.
 
-  stretch, alternated, best, wall   HIP-event and wall-clock timing
+  stretch, rounds, alternated, best, wall   HIP-event and wall-clock timing
   full_law                          alpha / beta over six decades, margin 0.95, three labels
   digest                            sha256 of the outputs of every pair entry → one JSON line: the six dense entries
                                     (statistics as counts, sums and both; the Hessian-vector entries with and without
@@ -52,14 +52,19 @@ def stretch(fn, seconds):
     return total / calls
 
 
-def alternated(fns):
-    """min over two rounds of every function's stretch, the functions taking turns within a round."""
+def rounds(fns):
+    """Per function the ms per call of its two rounds' stretches, the functions taking turns within a round."""
     found = [[] for _ in fns]
     for _ in range(2):
         for k, fn in enumerate(fns):
             stretch(fn, SECONDS / 2)
             found[k].append(stretch(fn, SECONDS))
-    return [min(t) for t in found]
+    return found
+
+
+def alternated(fns):
+    """min over two rounds of every function's stretch, the functions taking turns within a round."""
+    return [min(t) for t in rounds(fns)]
 
 
 def best(fn):
@@ -203,18 +208,19 @@ def identity_lines(parent_lib, script=None, what="every pair entry"):
     return lines
 
 
-def bench_lines(parent_tree, runs):
-    """bench.py in this tree and in `parent_tree`, taking turns."""
+def bench_lines(parent_tree, runs, swap=False):
+    """bench.py in this tree and in `parent_tree`, taking turns; swap: the parent goes first in every second turn."""
+    trees = (("this commit", ROOT), ("its parent", os.path.abspath(parent_tree)))
     found = {"this commit": [], "its parent": []}
-    for _ in range(runs):
-        for tag, tree in (("this commit", ROOT), ("its parent", os.path.abspath(parent_tree))):
+    for turn in range(runs):
+        for tag, tree in (trees[::-1] if swap and turn % 2 else trees):
             env = dict(os.environ)
             env.pop("MFCD_LIB", None)
             done = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "10490", "--warmup", "1049"], cwd=tree,
                                   env=env, capture_output=True, text=True, check=True, timeout=600)
             found[tag].append(json.loads(done.stdout.strip().splitlines()[-1])["value"] / 1e6)
     lines = [f"# bench.py --gpus 1 --steps 10490 --warmup 1049 in this tree and in a built checkout of the parent commit, {runs} "
-             "runs each, the commits taking turns on one GPU; M triplet-updates/s"]
+             f"runs each, the commits taking turns on one GPU{', the order swapping from turn to turn' if swap else ''}; M triplet-updates/s"]
     for tag, vals in found.items():
         med = sorted(vals)[len(vals) // 2]
         lines.append(f"#   {tag:12s} " + " ".join(f"{v:8.2f}" for v in vals) + f"   median {med:8.2f}   spread "
