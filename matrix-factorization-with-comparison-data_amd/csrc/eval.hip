@@ -81,8 +81,11 @@ int eval_batches_impl(const TP *U, const TP *V, const mfcd_sample *samples, int6
     if (N == 0) return 0;
     if (!samples || !loss_per_batch) return MFCD_EINVAL;
     const int64_t nb = (N + B - 1) / B;
-    hipLaunchKernelGGL((eval_batches_kernel<TP>), dim3((unsigned)nb), dim3(kEvalWaves * 64), sizeof(float) * 2 * (size_t)B,
-                       (hipStream_t)stream, U, V, samples, N, B, d, loss_per_batch, correct_per_batch, p_out,
+    const size_t lds = sizeof(float) * 2 * (size_t)B;   // 128 KiB at B = 16384: above the 64 KiB a launch gets unasked
+    static size_t allowed = 0;
+    MFCD_HIP_TRY(allow_dynamic_lds((const void *)eval_batches_kernel<TP>, lds, allowed));
+    hipLaunchKernelGGL((eval_batches_kernel<TP>), dim3((unsigned)nb), dim3(kEvalWaves * 64), lds, (hipStream_t)stream,
+                       U, V, samples, N, B, d, loss_per_batch, correct_per_batch, p_out,
                        (const mfcd_detail::EvalSeg *)nullptr, 0);
     MFCD_HIP_TRY(hipGetLastError());
     return 0;
@@ -92,9 +95,11 @@ int eval_batches_impl(const TP *U, const TP *V, const mfcd_sample *samples, int6
 namespace mfcd_detail {
 int launch_eval_multi(const EvalSeg *segs_dev, int nseg, int64_t blocks, int max_B, hipStream_t st)
 {
-    hipLaunchKernelGGL((eval_batches_kernel<float>), dim3((unsigned)blocks), dim3(kEvalWaves * 64),
-                       sizeof(float) * 2 * (size_t)max_B, st, (const float *)nullptr, (const float *)nullptr,
-                       (const mfcd_sample *)nullptr, (int64_t)0, 0, 0, (float *)nullptr, (int32_t *)nullptr,
+    const size_t lds = sizeof(float) * 2 * (size_t)max_B;
+    static size_t allowed = 0;
+    MFCD_HIP_TRY(allow_dynamic_lds((const void *)eval_batches_kernel<float>, lds, allowed));
+    hipLaunchKernelGGL((eval_batches_kernel<float>), dim3((unsigned)blocks), dim3(kEvalWaves * 64), lds, st,
+                       (const float *)nullptr, (const float *)nullptr, (const mfcd_sample *)nullptr, (int64_t)0, 0, 0, (float *)nullptr, (int32_t *)nullptr,
                        (float *)nullptr, segs_dev, nseg);
     MFCD_HIP_TRY(hipGetLastError());
     return 0;

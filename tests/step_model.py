@@ -90,6 +90,41 @@ selects; local.hip takes only the Adam update from it (its phase A calls sigmoid
 SAFETY multiplies every bound and is 1: tests/test_step_cpu.py prints the largest error / bound of emulate() and of the C
 oracle per family and output (profiles/step_accuracy_cpu.txt); a ratio above 1 on the GPU is a finding, not a reason to
 raise it.
+
+THE PARTS (evaluation and the split step kernels: csrc/eval.hip, the split entries of csrc/streaming.hip; always
+"ieee").  eval_model, coef_model, grad_model, adam_model, apply_model return (model, bounds) of one entry from the same
+stage functions model() and bounds() are made of; emu_* are the oracle's fp32 arithmetic with the errors of PART_FAULTS.
+(E) evaluation (eval.hip eval_batches_kernel; mfcd_eval_batches, _bf16, _multi).  `p = sigmoid_f32(wave_score(..))`
+    (eval.hip:37; common.h wave_score: `acc += ldf(ur, k) * (ldf(vi, k) - ldf(vj, k))`, then wave_sum64) is (X) and (S)
+    unchanged: p_out is held to dp.  bf16 tables are widened exactly by ldf (common.h: `(float)p[i]`), so the model takes
+    the widened values and (B) does not apply.  `terms[t] = bce_term_f32(p, s.z)` (eval.hip:39) is the dterm of (L).
+    `acc += terms[t]` over a lane's samples, wave_sum64, `acc / (float)b` (eval.hip:48-55) are at most b - 1 additions
+    and one division of the batch's own b = min(B, N - off) (eval.hip:34): the mean bound of (L) with that b.
+    `match[t] = ((p > 0.5f ? 1.0f : 0.0f) == s.z)` (eval.hip:40): a sample with |p - 0.5| > dp is decided, the kernel's
+    prediction is the model's, and it matches iff the prediction EQUALS the label (a soft label never does, p = 0.5
+    predicts 0).  The count is exact integer arithmetic (wave_sum64_i), so correct_per_batch lies in [lo, lo + a] with
+    lo the decided matches and a the undecided samples of the batch.
+    Exact zero: if every product U[u][k] (V[i][k] - V[j][k]) is exactly zero (i == j: vi[k] - vj[k] = 0 for finite
+    values; a zero U row), every lane's acc is 0, wave_sum64 adds zeros, expf(-0) = 1, 1 + 1 = 2 and 1 / 2 = 0.5 with no
+    rounding: dp = 0, p_out must be 0.5 and the sample is decided (prediction 0).
+(K) coefficients (streaming.hip coeff_kernel).  The same `sigmoid_f32(wave_score(..))` (streaming.hip:269): p_out is
+    held to dp, term_out to dterm; `bce_sigmoid_backward_f32(p, s.z, inv_batch)` with inv_batch = `1.0f /
+    (float)batch_divisor` (streaming.hip:398) is (C) with 1 / b replaced by 1 / batch_divisor, the same count of
+    roundings: g_out is held to dc(batch_divisor).
+(DG) dense gradient (train_step_kernel MODE 1).  Phase 1 recomputes p per hit (streaming.hip:199-201), forms g by
+    bce_sigmoid_backward_f32 with inv_batch = 1 / batch_divisor, and accumulates `dst[k] += g * (ldf(vi, k) - ldf(vj,
+    k))`, `dst[k] += g * ldf(ur, k)`, `dst[k] += -(g * ldf(ur, k))` (streaming.hip:210-218) in batch order, one wave per
+    row; phase 2 stores the LDS value unchanged (`store_vec(G + e, gs)`, streaming.hip:241).  That is (G): gradU, gradV
+    are held to ds with dc from (C); a row no sample touches has ds = 0 and must be exactly 0 (streaming.hip:238).
+    mfcd_dense_grad_from_coefficients reads `g = g_in[(base + tl) * g_stride]` (streaming.hip:196): the caller's fp32
+    value is exact, the model takes it as given, dc = 0 and ds = gamma(h + 3) S2.
+(AD) Adam from a dense gradient (MODE 2, mfcd_adam_dense).  `load_vec(G + e, gs)` (streaming.hip:233) reads the dense
+    gradient exactly: ds = 0, so dg = 2 u |wd P| + u |g| (+ 2^-140 where not zero) from `fmaf(wd, P, d)`, then (M), (V),
+    (D), (U), (U2) of adam_update unchanged.  A NaN gradient element makes m', v', P' NaN; an infinite one makes m', v'
+    infinite and P' NaN (num / den = inf / inf); _ratio demands exactly that, and the neighbours' bounds do not widen.
+(AS) the step from given coefficients (MODE 0 with g_in, mfcd_apply_step).  (G) with dc = 0 as in (DG), then the chain
+    with that ds; the result is copied back by hipMemcpyAsync (streaming.hip:423-424), which changes no bit.  B = 0:
+    no hit, ds = 0, the pure weight-decay / moment step of (AD) with a zero gradient.
 ---------------------------------------------------------------------------------------------------------------------
 """
 import os
@@ -149,28 +184,56 @@ def _adam64(P, m, v, g, h, step):
     return P + delta, m1, v1, den, delta
 
 
-def model(state, batch, h, step):
-    """-> dict: U, V, mU, vU, mV, vV, loss as the step defines them (f64), and "aux": what bounds() reuses."""
-    U, V = state["U"].astype(np.float64), state["V"].astype(np.float64)
+def _batch64(batch):
     u, i, j = (np.asarray(t, dtype=np.int64) for t in batch[:3])
-    z = np.asarray(batch[3], dtype=np.float64)
-    b = len(u)
+    return u, i, j, np.asarray(batch[3], dtype=np.float64)
+
+
+def stage_forward(U, V, u, i, j, z):
+    """Score, sigmoid and BCE term of every sample (f64 tables) -> dict(Uu, W, x, p, q, l0, l1, term, zero); zero marks
+    the samples whose products U[u][k] (V[i][k] - V[j][k]) are all exactly zero."""
     with np.errstate(all="ignore"):
         Uu, W = U[u], V[i] - V[j]
         x = (Uu * W).sum(axis=1)
         p, q = 1.0 / (1.0 + np.exp(-x)), 1.0 / (1.0 + np.exp(x))
         l0, l1 = np.maximum(-np.logaddexp(0.0, -x), -100.0), np.maximum(-np.logaddexp(0.0, x), -100.0)
         term = (z - 1.0) * l1 - z * l0
+        zero = (Uu * W == 0.0).all(axis=1)
+    return {"Uu": Uu, "W": W, "x": x, "p": p, "q": q, "l0": l0, "l1": l1, "term": term, "zero": zero}
+
+
+def stage_coefficient(fw, z, div):
+    """The backward coefficient of every sample for a mean over `div` samples -> dict(f, pz, c)."""
+    p, q = fw["p"], fw["q"]
+    with np.errstate(all="ignore"):
         pq = p * q
         f = np.where(pq > 0.0, pq / np.maximum(pq, 1e-12), 0.0)
         pz = np.where(z > 0.5, (1.0 - z) - q, p - z)          # p - z without cancellation next to p = 1
-        c = pz / b * f
-        gU, gV = h["wd"] * U, h["wd"] * V
+        c = pz / div * f
+    return {"f": f, "pz": pz, "c": c}
+
+
+def stage_rows(gU, gV, u, i, j, c, Uu, W):
+    """The row gradients of the batch added onto gU, gV (which hold wd P, or zeros) in place."""
+    with np.errstate(all="ignore"):
         np.add.at(gU, u, c[:, None] * W)
         np.add.at(gV, i, c[:, None] * Uu)
         np.add.at(gV, j, -c[:, None] * Uu)
-        out = {"loss": float(term.mean())}
-        aux = {"x": x, "p": p, "q": q, "f": f, "pz": pz, "c": c, "l0": l0, "l1": l1, "term": term, "b": b}
+    return gU, gV
+
+
+def model(state, batch, h, step):
+    """-> dict: U, V, mU, vU, mV, vV, loss as the step defines them (f64), and "aux": what bounds() reuses."""
+    U, V = state["U"].astype(np.float64), state["V"].astype(np.float64)
+    u, i, j, z = _batch64(batch)
+    b = len(u)
+    with np.errstate(all="ignore"):
+        fw = stage_forward(U, V, u, i, j, z)
+        co = stage_coefficient(fw, z, b)
+        gU, gV = stage_rows(h["wd"] * U, h["wd"] * V, u, i, j, co["c"], fw["Uu"], fw["W"])
+        out = {"loss": float(fw["term"].mean())}
+        aux = {k: fw[k] for k in ("x", "p", "q", "l0", "l1", "term")}
+        aux.update(co, b=b)
         for T, g in (("U", gU), ("V", gV)):
             P1, m1, v1, den, delta = _adam64(U if T == "U" else V, state["m" + T].astype(np.float64),
                                              state["v" + T].astype(np.float64), g, h, step)
@@ -193,83 +256,119 @@ def _dlog(dp, p, l):
     return np.where(r < 0.5, -np.log1p(-np.minimum(r, 0.5)), 100.0) + 3.0 * U32 * np.abs(l)
 
 
-def bounds(state, batch, h, step, form, flavour="ieee", mdl=None):
-    """-> dict: absolute error bounds of U, V, mU, vU, mV, vV (arrays) and loss (float) for a step in `form` under
-    `flavour`; see the module docstring, whose letters the comments name."""
-    mdl = mdl if mdl is not None else model(state, batch, h, step)
-    fast_hit, fast_adam = fast_parts(form, flavour)
-    a = mdl["aux"]
-    U, V = state["U"].astype(np.float64), state["V"].astype(np.float64)
-    u, i, j = (np.asarray(t, dtype=np.int64) for t in batch[:3])
-    z = np.asarray(batch[3], dtype=np.float64)
-    b, d, uu = a["b"], U.shape[1], U32
-    x, p, q, f, pz, c = a["x"], a["p"], a["q"], a["f"], a["pz"], a["c"]
-    out = {}
+def bound_forward(Uu, W, x, p, q, d, fast_hit=False):
+    """(X), (S) -> (dx, dp) per sample."""
+    uu = U32
     with np.errstate(all="ignore"):
-        Uu, W = U[u], V[i] - V[j]
         dx = gamma(d + 2) * (np.abs(Uu) * np.abs(W)).sum(axis=1)                                                  # (X)
         E = (2.0 * np.abs(x) + 2.0 * dx + 2.0) * uu if fast_hit else 2.0 * uu                                     # (S)
         dp = p * q * dx * np.exp(dx) + p * (q * E + (4.0 if fast_hit else 3.0) * uu) + 2.0 ** -124
+    return dx, dp
+
+
+def bound_coefficient(p, q, f, pz, dp, div, fast_hit=False):
+    """(C) -> dc per sample, for a mean over `div` samples."""
+    uu = U32
+    with np.errstate(all="ignore"):
         dlo, dhi = np.minimum(dp, p), np.minimum(dp, q)          # the interval [p - dlo, p + dhi] inside [0, 1]     (C)
         phiA, phiB = (p - dlo) * (q + dlo), (p + dhi) * (q - dhi)
         phi_lo = np.minimum(phiA, phiB)
         phi_hi = np.where((p - dlo <= 0.5) & (p + dhi >= 0.5), 0.25, np.maximum(phiA, phiB))
         f_lo, f_hi = np.minimum(1.0, phi_lo / 1e-12), np.minimum(1.0, phi_hi / 1e-12)
         cc = 11.0 if fast_hit else 10.0
-        dc = (np.abs(pz) * np.maximum(f - f_lo, f_hi - f) + dp * f_hi + cc * uu * (np.abs(pz) + dp) * f_hi) / b + ETA
-        ss, bc2s = _scalars(h, step)
-        k, kp = (6.0, 5.0) if fast_adam else (4.0, 4.0)
+        return (np.abs(pz) * np.maximum(f - f_lo, f_hi - f) + dp * f_hi + cc * uu * (np.abs(pz) + dp) * f_hi) / div + ETA
+
+
+def bound_rows(T, shape, u, i, j, dc, c, Uu, W):
+    """(G) -> ds [rows, d] of table T ("U" or "V"): the row gradients summed over a row's hits."""
+    with np.errstate(all="ignore"):
+        S1, S2, hits = np.zeros(shape), np.zeros(shape), np.zeros(shape[0])                                       # (G)
+        if T == "U":
+            np.add.at(S1, u, dc[:, None] * np.abs(W))
+            np.add.at(S2, u, np.abs(c)[:, None] * np.abs(W))
+            np.add.at(hits, u, 1.0)
+        else:
+            for idx in (i, j):
+                np.add.at(S1, idx, dc[:, None] * np.abs(Uu))
+                np.add.at(S2, idx, np.abs(c)[:, None] * np.abs(Uu))
+                np.add.at(hits, idx, 1.0)
+        gh = gamma(hits + 3.0)[:, None]
+        return (1.0 + gh) * S1 + gh * S2
+
+
+def bound_adam(P, m, v, g, m1, v1, den, delta, P1, ds, h, step, fast_adam=False):
+    """(M), (V), (D), (U), (U2) -> (dP, dm, dv) of one table from the bound ds of its sparse (or dense) gradient."""
+    uu = U32
+    ss, bc2s = _scalars(h, step)
+    k, kp = (6.0, 5.0) if fast_adam else (4.0, 4.0)
+    with np.errstate(all="ignore"):
+        dg = ds + 2.0 * uu * np.abs(h["wd"] * P) + uu * (np.abs(g) + ds)
+        dg = dg + _nz(dg)
+        A = (1.0 - h["beta1"]) * (dg + 2.0 * uu * (np.abs(g - m) + dg)) * (1.0 + 2.0 * uu)                     # (M)
+        dm = A + uu * (np.abs(m1) + A)
+        dm = dm + _nz(dm)
+        T1 = 2.01 * uu * h["beta2"] * v                                                                       # (V)
+        T2 = (1.0 - h["beta2"]) * (2.0 * np.abs(g) * dg + dg * dg) + 3.01 * uu * (1.0 - h["beta2"]) * (np.abs(g) + dg) ** 2
+        dv = T1 + T2 + uu * (v1 + T1 + T2)
+        dv = dv + _nz(dv)
+        ab = (2.0 ** -63 / bc2s) * (v1 - dv < 2.0 ** -125) if fast_adam else 0.0                              # (D)
+        den_lo = (np.sqrt(np.maximum(v1 - dv, 0.0)) / bc2s * (1.0 - k * uu) - ab + h["eps"] * (1.0 - uu)) * (1.0 - uu)
+        den_hi = (np.sqrt(v1 + dv) / bc2s * (1.0 + k * uu) + ab + h["eps"] * (1.0 + uu)) * (1.0 + uu)
+        den_lo = np.maximum(den_lo, 0.0)
+        mhi = np.abs(m1) + dm                                                                                 # (U)
+        dD = ss * (dm / den_lo + np.abs(m1) * np.maximum(1.0 / den_lo - 1.0 / den, 1.0 / den - 1.0 / den_hi)) \
+            + kp * uu * ss * mhi / den_lo
+        # (U2): through g, whose error m' and v' share; the rounding-only parts of dm and dv; the smaller of the two
+        w1, w2, b1, b2 = 1.0 - h["beta1"], 1.0 - h["beta2"], h["beta1"], h["beta2"]
+        v_lo = b2 * v + w2 * np.maximum(np.abs(g) - dg, 0.0) ** 2
+        num = w1 * b2 * v + b1 * w2 * np.abs(m) * (np.abs(g) + dg)
+        G = (w1 * h["eps"] + np.where(num > 0.0, num / (bc2s * np.sqrt(v_lo)), 0.0)) / (den_lo * den_lo)
+        dm_r = np.maximum(dm - w1 * dg, 0.0)
+        dv_r = np.maximum(dv - w2 * (2.0 * np.abs(g) * dg + dg * dg), 0.0)
+        D_r = np.where(dv_r > 0.0, np.minimum(np.sqrt(dv_r), dv_r / np.sqrt(v_lo)), 0.0)
+        dden = D_r / bc2s + k * uu * np.sqrt(v1 + dv) / bc2s + ab + 2.0 * uu * den_hi
+        dD2 = ss * (G * dg + dm_r / den_lo + (np.abs(m1) + w1 * dg) * dden / (den_lo * den_lo)) + kp * uu * ss * mhi / den_lo
+        dD = np.where(np.isnan(dD2), dD, np.fmin(dD, dD2))
+        dD = np.where(ss * mhi > 0.0, dD + ETA, 0.0)
+        dP = np.where(np.abs(delta) + dD > 0.0, dD + uu * (np.abs(P1) + dD), 0.0)
+        return tuple(np.where(np.isfinite(ref), SAFETY * val, np.nan) for val, ref in ((dP, P1), (dm, m1), (dv, v1)))
+
+
+def bound_term(dp, p, q, l0, l1, z):
+    """(L) -> dterm per sample."""
+    with np.errstate(all="ignore"):
+        dl0, dl1 = _dlog(dp, p, l0), _dlog(dp, q, l1)
+        return (1.0 - z) * dl1 + z * dl0 + 3.0 * U32 * ((1.0 - z) * (np.abs(l1) + dl1) + z * (np.abs(l0) + dl0))
+
+
+def bound_mean(term, dterm):
+    """(L) -> the bound of the fp32 mean of one batch's terms (its own length b)."""
+    with np.errstate(all="ignore"):
+        return SAFETY * float(dterm.mean() + gamma(len(term) + 2) * (np.abs(term) + dterm).mean())
+
+
+def bounds(state, batch, h, step, form, flavour="ieee", mdl=None):
+    """-> dict: absolute error bounds of U, V, mU, vU, mV, vV (arrays) and loss (float) for a step in `form` under
+    `flavour`; see the module docstring, whose letters the stage functions name."""
+    mdl = mdl if mdl is not None else model(state, batch, h, step)
+    fast_hit, fast_adam = fast_parts(form, flavour)
+    a = mdl["aux"]
+    U, V = state["U"].astype(np.float64), state["V"].astype(np.float64)
+    u, i, j, z = _batch64(batch)
+    b, d = a["b"], U.shape[1]
+    x, p, q, f, pz, c = a["x"], a["p"], a["q"], a["f"], a["pz"], a["c"]
+    out = {}
+    with np.errstate(all="ignore"):
+        Uu, W = U[u], V[i] - V[j]
+        dx, dp = bound_forward(Uu, W, x, p, q, d, fast_hit)
+        dc = bound_coefficient(p, q, f, pz, dp, b, fast_hit)
         for T in ("U", "V"):
             P = U if T == "U" else V
             m, v = state["m" + T].astype(np.float64), state["v" + T].astype(np.float64)
-            g, m1, v1, den, delta, P1 = a["g" + T], mdl["m" + T], mdl["v" + T], a["den" + T], a["delta" + T], mdl[T]
-            S1, S2, hits = np.zeros_like(P), np.zeros_like(P), np.zeros(P.shape[0])                               # (G)
-            if T == "U":
-                np.add.at(S1, u, dc[:, None] * np.abs(W))
-                np.add.at(S2, u, np.abs(c)[:, None] * np.abs(W))
-                np.add.at(hits, u, 1.0)
-            else:
-                for idx in (i, j):
-                    np.add.at(S1, idx, dc[:, None] * np.abs(Uu))
-                    np.add.at(S2, idx, np.abs(c)[:, None] * np.abs(Uu))
-                    np.add.at(hits, idx, 1.0)
-            gh = gamma(hits + 3.0)[:, None]
-            ds = (1.0 + gh) * S1 + gh * S2
-            dg = ds + 2.0 * uu * np.abs(h["wd"] * P) + uu * (np.abs(g) + ds)
-            dg = dg + _nz(dg)
-            A = (1.0 - h["beta1"]) * (dg + 2.0 * uu * (np.abs(g - m) + dg)) * (1.0 + 2.0 * uu)                     # (M)
-            dm = A + uu * (np.abs(m1) + A)
-            dm = dm + _nz(dm)
-            T1 = 2.01 * uu * h["beta2"] * v                                                                       # (V)
-            T2 = (1.0 - h["beta2"]) * (2.0 * np.abs(g) * dg + dg * dg) + 3.01 * uu * (1.0 - h["beta2"]) * (np.abs(g) + dg) ** 2
-            dv = T1 + T2 + uu * (v1 + T1 + T2)
-            dv = dv + _nz(dv)
-            ab = (2.0 ** -63 / bc2s) * (v1 - dv < 2.0 ** -125) if fast_adam else 0.0                              # (D)
-            den_lo = (np.sqrt(np.maximum(v1 - dv, 0.0)) / bc2s * (1.0 - k * uu) - ab + h["eps"] * (1.0 - uu)) * (1.0 - uu)
-            den_hi = (np.sqrt(v1 + dv) / bc2s * (1.0 + k * uu) + ab + h["eps"] * (1.0 + uu)) * (1.0 + uu)
-            den_lo = np.maximum(den_lo, 0.0)
-            mhi = np.abs(m1) + dm                                                                                 # (U)
-            dD = ss * (dm / den_lo + np.abs(m1) * np.maximum(1.0 / den_lo - 1.0 / den, 1.0 / den - 1.0 / den_hi)) \
-                + kp * uu * ss * mhi / den_lo
-            # (U2): through g, whose error m' and v' share; the rounding-only parts of dm and dv; the smaller of the two
-            w1, w2, b1, b2 = 1.0 - h["beta1"], 1.0 - h["beta2"], h["beta1"], h["beta2"]
-            v_lo = b2 * v + w2 * np.maximum(np.abs(g) - dg, 0.0) ** 2
-            num = w1 * b2 * v + b1 * w2 * np.abs(m) * (np.abs(g) + dg)
-            G = (w1 * h["eps"] + np.where(num > 0.0, num / (bc2s * np.sqrt(v_lo)), 0.0)) / (den_lo * den_lo)
-            dm_r = np.maximum(dm - w1 * dg, 0.0)
-            dv_r = np.maximum(dv - w2 * (2.0 * np.abs(g) * dg + dg * dg), 0.0)
-            D_r = np.where(dv_r > 0.0, np.minimum(np.sqrt(dv_r), dv_r / np.sqrt(v_lo)), 0.0)
-            dden = D_r / bc2s + k * uu * np.sqrt(v1 + dv) / bc2s + ab + 2.0 * uu * den_hi
-            dD2 = ss * (G * dg + dm_r / den_lo + (np.abs(m1) + w1 * dg) * dden / (den_lo * den_lo)) + kp * uu * ss * mhi / den_lo
-            dD = np.where(np.isnan(dD2), dD, np.fmin(dD, dD2))
-            dD = np.where(ss * mhi > 0.0, dD + ETA, 0.0)
-            dP = np.where(np.abs(delta) + dD > 0.0, dD + uu * (np.abs(P1) + dD), 0.0)
-            for name, val, ref in ((T, dP, P1), ("m" + T, dm, m1), ("v" + T, dv, v1)):
-                out[name] = np.where(np.isfinite(ref), SAFETY * val, np.nan)
-        l0, l1, term = a["l0"], a["l1"], a["term"]                                                                # (L)
-        dl0, dl1 = _dlog(dp, p, l0), _dlog(dp, q, l1)
-        dterm = (1.0 - z) * dl1 + z * dl0 + 3.0 * uu * ((1.0 - z) * (np.abs(l1) + dl1) + z * (np.abs(l0) + dl0))
-        out["loss"] = SAFETY * float(dterm.mean() + gamma(b + 2) * (np.abs(term) + dterm).mean())
+            ds = bound_rows(T, P.shape, u, i, j, dc, c, Uu, W)
+            out[T], out["m" + T], out["v" + T] = bound_adam(P, m, v, a["g" + T], mdl["m" + T], mdl["v" + T], a["den" + T],
+                                                            a["delta" + T], mdl[T], ds, h, step, fast_adam)
+        out["loss"] = bound_mean(a["term"], bound_term(dp, p, q, a["l0"], a["l1"], z))
     return out
 
 
@@ -632,3 +731,410 @@ def case_inputs(case, bf16=False):
         U, V = bf16_round(U), bf16_round(V)
     st = preset_state(U, V, case["start"]) if case["start"] else fresh_state(U, V)
     return data, st, case["start"] + 1
+
+
+# =====================================================================================================================
+# THE PARTS: evaluation, coefficients, dense gradient, Adam from a dense gradient, the step from given coefficients
+# (csrc/eval.hip, the split entries of csrc/streaming.hip).  All "ieee": neither file has a fast path.  The derivation is
+# in the module docstring ((E), (K), (DG), (AD), (AS)); the stage functions above do the arithmetic.
+# =====================================================================================================================
+
+PART_FAULTS = ("match_ge_half", "match_rounded_label", "short_batch_by_B", "divisor_ignored", "flip_j_sign",
+               "drop_second_hit", "partial_block_unwritten", "seam", "bias_from_step0", "param_not_updated")
+PART_FAMILIES = FAMILIES + ("half",)
+
+
+def plan(n, m, d, aligned=True):
+    """streaming.hip make_plan -> (vec, chunks, E): vector access needs d % 4 == 0 and 16-byte aligned arrays."""
+    vec = 4 if (d % 4 == 0 and aligned) else 1
+    chunks, total = 1, (n + m) * d
+    while chunks < 4 and total // (256 * vec * chunks) > 2048:
+        chunks *= 2
+    return vec, chunks, 256 * vec * chunks
+
+
+def half_family(n, m, d, B, N, seed=0):
+    """The "half" family: samples whose score is exactly zero (i == j; the zero row U[0]) with labels 0, 1 and 0.5,
+    samples with x = +-2^-19, +-2^-20 exactly (p - 0.5 = x / 4 is 4 and 2 times the bound: decided), and, from N = 500 on,
+    two samples of batch 0 with x = +-2^-24 (inside the bound: undecided).  U rows 0 .. 6 and V rows 0, 1 are special; the
+    random samples use the other users."""
+    assert n >= 8 and m >= 4
+    rng = np.random.default_rng([len(FAMILIES), n, m, d, B, N, seed])
+    U = rng.standard_normal((n, d)) / np.sqrt(d)
+    V = rng.standard_normal((m, d)) / np.sqrt(d)
+    U[:7] = 0.0
+    U[1:7, 0] = [2.0 ** -19, -2.0 ** -19, 2.0 ** -20, -2.0 ** -20, 2.0 ** -24, -2.0 ** -24]
+    V[:2] = 0.0
+    V[0, 0] = 1.0
+    u, i = rng.integers(7, n, N), rng.integers(0, m, N)
+    j = (i + 1 + rng.integers(0, max(m - 1, 1), N)) % m
+    z = rng.integers(0, 2, N).astype(np.float64)
+    t = np.arange(N)
+    lab3 = np.array([0.0, 1.0, 0.5])[(t // 8) % 3]
+    same, zrow, near = t % 8 == 1, t % 8 == 3, t % 8 == 5
+    j = np.where(same, i, j)
+    u = np.where(zrow, 0, u)
+    u, i, j = np.where(near, 1 + (t // 8) % 4, u), np.where(near, 0, i), np.where(near, 1, j)
+    z = np.where(same | zrow, lab3, np.where(near, ((t // 32) % 2).astype(np.float64), z))
+    if N >= 500:
+        for pos, row, lab in ((7, 5, 1.0), (15, 6, 1.0)):
+            u[pos], i[pos], j[pos], z[pos] = row, 0, 1, lab
+    return dict(U=U.astype(np.float32), V=V.astype(np.float32), u=u.astype(np.int64), i=i.astype(np.int64),
+                j=j.astype(np.int64), z=z.astype(np.float32))
+
+
+def part_family(name, n, m, d, B, N, seed=0):
+    return half_family(n, m, d, B, N, seed) if name == "half" else family(name, n, m, d, B, N, seed)
+
+
+def _ratios(got, mdl, bnd, names):
+    return {k: _ratio(got[k], mdl[k], bnd[k]) for k in names if got.get(k) is not None}
+
+
+# ---- evaluation ------------------------------------------------------------------------------------------------------
+def _forward_parts(U, V, batch):
+    """-> (fw, dp, dterm, z) with the exact-zero rule of (E) applied."""
+    U, V = np.asarray(U, np.float64), np.asarray(V, np.float64)
+    u, i, j, z = _batch64(batch)
+    fw = stage_forward(U, V, u, i, j, z)
+    _, dp = bound_forward(fw["Uu"], fw["W"], fw["x"], fw["p"], fw["q"], U.shape[1])
+    dp = np.where(fw["zero"], 0.0, dp)
+    return fw, dp, bound_term(dp, fw["p"], fw["q"], fw["l0"], fw["l1"], z), z
+
+
+def eval_model(U, V, data, B):
+    """(E) -> (mdl, bnd): mdl = dict(p [N], term [N], loss [nb], correct [nb] the MIDDLE of the admissible interval,
+    lo, hi [nb], decided [N], zero [N]); bnd = dict(p, term, loss, correct = half the interval's width)."""
+    batch = (data["u"], data["i"], data["j"], data["z"])
+    N = len(batch[0])
+    fw, dp, dterm, z = _forward_parts(U, V, batch)
+    decided = fw["zero"] | (np.abs(fw["p"] - 0.5) > dp)
+    match = ((fw["p"] > 0.5).astype(np.float64) == z) & decided
+    nb = (N + B - 1) // B
+    loss, dloss, lo, hi = np.zeros(nb), np.zeros(nb), np.zeros(nb), np.zeros(nb)
+    for k in range(nb):
+        s = slice(k * B, min((k + 1) * B, N))
+        loss[k], dloss[k] = fw["term"][s].mean(), bound_mean(fw["term"][s], dterm[s])
+        lo[k] = match[s].sum()
+        hi[k] = lo[k] + (~decided[s]).sum()
+    mdl = dict(p=fw["p"], term=fw["term"], loss=loss, correct=0.5 * (lo + hi), lo=lo, hi=hi, decided=decided, zero=fw["zero"])
+    return mdl, dict(p=SAFETY * dp, term=SAFETY * dterm, loss=dloss, correct=0.5 * (hi - lo))
+
+
+def eval_check(got, mdl, bnd):
+    """got = dict(loss, and p, correct or None) -> ratios of the outputs that are present."""
+    return _ratios(got, mdl, bnd, ("p", "loss", "correct"))
+
+
+# ---- coefficients ----------------------------------------------------------------------------------------------------
+def coef_model(U, V, batch, divisor):
+    """(K) -> (mdl, bnd) with keys g, term, p."""
+    fw, dp, dterm, z = _forward_parts(U, V, batch)
+    co = stage_coefficient(fw, z, divisor)
+    dc = bound_coefficient(fw["p"], fw["q"], co["f"], co["pz"], dp, divisor)
+    return dict(g=co["c"], term=fw["term"], p=fw["p"]), dict(g=SAFETY * dc, term=SAFETY * dterm, p=SAFETY * dp)
+
+
+# ---- dense gradient --------------------------------------------------------------------------------------------------
+def grad_model(U, V, batch, divisor=None, g=None):
+    """(DG) -> (mdl, bnd) with keys gradU, gradV (and term for the entry that computes the coefficients itself).  Give
+    `divisor` for mfcd_dense_grad, or the fp32 coefficients `g` for mfcd_dense_grad_from_coefficients."""
+    assert (divisor is None) != (g is None)
+    U, V = np.asarray(U, np.float64), np.asarray(V, np.float64)
+    u, i, j, z = _batch64(batch)
+    mdl, bnd = {}, {}
+    if g is None:
+        fw, dp, dterm, z = _forward_parts(U, V, batch)
+        co = stage_coefficient(fw, z, divisor)
+        c, dc = co["c"], bound_coefficient(fw["p"], fw["q"], co["f"], co["pz"], dp, divisor)
+        mdl["term"], bnd["term"] = fw["term"], SAFETY * dterm
+    else:
+        fw = stage_forward(U, V, u, i, j, z)
+        c = np.asarray(g, np.float64)
+        dc = np.zeros(len(u))
+    mdl["gradU"], mdl["gradV"] = stage_rows(np.zeros_like(U), np.zeros_like(V), u, i, j, c, fw["Uu"], fw["W"])
+    for T, P in (("U", U), ("V", V)):
+        bnd["grad" + T] = SAFETY * bound_rows(T, P.shape, u, i, j, dc, c, fw["Uu"], fw["W"])
+    return mdl, bnd
+
+
+# ---- Adam from a dense gradient, and the step from given coefficients ------------------------------------------------
+def _chain(state, gU, gV, dsU, dsV, h, step):
+    mdl, bnd = {}, {}
+    with np.errstate(all="ignore"):
+        for T, g, ds in (("U", gU, dsU), ("V", gV, dsV)):
+            P, m, v = (state[k + T].astype(np.float64) for k in ("", "m", "v"))
+            P1, m1, v1, den, delta = _adam64(P, m, v, g, h, step)
+            mdl[T], mdl["m" + T], mdl["v" + T] = P1, m1, v1
+            bnd[T], bnd["m" + T], bnd["v" + T] = bound_adam(P, m, v, g, m1, v1, den, delta, P1, ds, h, step)
+    return mdl, bnd
+
+
+def adam_model(state, gradU, gradV, h, step):
+    """(AD) -> (mdl, bnd) of the six tables after mfcd_adam_dense from the fp32 dense gradients."""
+    with np.errstate(all="ignore"):
+        gU = h["wd"] * state["U"].astype(np.float64) + np.asarray(gradU, np.float64)
+        gV = h["wd"] * state["V"].astype(np.float64) + np.asarray(gradV, np.float64)
+    return _chain(state, gU, gV, 0.0, 0.0, h, step)
+
+
+def apply_model(state, batch, g, h, step):
+    """(AS) -> (mdl, bnd) of the six tables after mfcd_apply_step with the fp32 coefficients g (B = 0: empty batch)."""
+    U, V = state["U"].astype(np.float64), state["V"].astype(np.float64)
+    u, i, j, z = _batch64(batch)
+    fw = stage_forward(U, V, u, i, j, z)
+    c = np.asarray(g, np.float64)
+    gU, gV = stage_rows(h["wd"] * U, h["wd"] * V, u, i, j, c, fw["Uu"], fw["W"])
+    ds = [bound_rows(T, P.shape, u, i, j, np.zeros(len(u)), c, fw["Uu"], fw["W"]) for T, P in (("U", U), ("V", V))]
+    return _chain(state, gU, gV, ds[0], ds[1], h, step)
+
+
+def check_tables(got, mdl, bnd):
+    return _ratios(got, mdl, bnd, TABLES)
+
+
+# ---- fp32 emulation of the parts (the oracle's arithmetic), with the deliberate errors of PART_FAULTS ----------------
+def emu_forward(U, V, batch):
+    """mfcd_orc_forward -> (p, term) fp32."""
+    U, V = np.ascontiguousarray(U, dtype=F4), np.ascontiguousarray(V, dtype=F4)
+    u, i, j = (np.asarray(t, dtype=np.int64) for t in batch[:3])
+    z = np.asarray(batch[3], dtype=F4)
+    one = F4(1.0)
+    with np.errstate(all="ignore"):
+        x = _score32(U[u], V[i], V[j])
+        p = (one / (one + np.exp(-x, dtype=F4)).astype(F4)).astype(F4)
+        l1, l0 = np.maximum(np.log1p(-p, dtype=F4), F4(-100.0)), np.maximum(np.log(p, dtype=F4), F4(-100.0))
+        term = (((z - one).astype(F4) * l1).astype(F4) - (z * l0).astype(F4)).astype(F4)
+    return p, term
+
+
+def _mean32(term, div):
+    return F4(np.cumsum(term, dtype=F4)[-1] / F4(div))        # cumsum: the serial fp32 sum of mean_terms
+
+
+def emu_eval(U, V, data, B, fault=None):
+    """mfcd_orc_eval_batches -> dict(p [N], loss [nb], correct [nb])."""
+    assert fault is None or fault in PART_FAULTS
+    p, term = emu_forward(U, V, (data["u"], data["i"], data["j"], data["z"]))
+    z = np.asarray(data["z"], dtype=F4)
+    if fault == "match_rounded_label":
+        z = np.rint(z).astype(F4)
+    hard = ((p >= F4(0.5)) if fault == "match_ge_half" else (p > F4(0.5))).astype(F4)
+    N = len(p)
+    nb = (N + B - 1) // B
+    loss, corr = np.zeros(nb, F4), np.zeros(nb, np.int32)
+    for k in range(nb):
+        s = slice(k * B, min((k + 1) * B, N))
+        loss[k] = _mean32(term[s], B if fault == "short_batch_by_B" else s.stop - s.start)
+        corr[k] = int((hard[s] == z[s]).sum())
+    return dict(p=p, loss=loss, correct=corr)
+
+
+def emu_coef(U, V, batch, divisor, fault=None):
+    """The per-sample part of mfcd_orc_grad -> dict(g, term, p) fp32."""
+    assert fault is None or fault in PART_FAULTS
+    p, term = emu_forward(U, V, batch)
+    z = np.asarray(batch[3], dtype=F4)
+    one = F4(1.0)
+    invb = one / F4(len(p) if fault == "divisor_ignored" else divisor)
+    with np.errstate(all="ignore"):
+        pq = ((one - p).astype(F4) * p).astype(F4)
+        a = ((invb * (p - z).astype(F4)).astype(F4) / np.maximum(pq, F4(1e-12))).astype(F4)
+        g = ((a * (one - p).astype(F4)).astype(F4) * p).astype(F4)
+    return dict(g=g, term=term, p=p)
+
+
+def _occurrence(idx):
+    """-> for every entry of idx, how many earlier entries hold the same value."""
+    order = np.argsort(idx, kind="stable")
+    s = idx[order]
+    first = np.r_[True, s[1:] != s[:-1]]
+    start = np.maximum.accumulate(np.where(first, np.arange(len(s)), 0))
+    occ = np.empty(len(s), dtype=np.int64)
+    occ[order] = np.arange(len(s)) - start
+    return occ
+
+
+def _scatter32(dst, idx, contrib, drop):
+    """index_put_(accumulate=True), serial in batch order, fp32: round r adds every row's hit number r."""
+    if not len(idx):
+        return
+    occ = _occurrence(idx)
+    for r in range(int(occ.max()) + 1):
+        if drop and r == 1:
+            continue
+        sel = occ == r
+        dst[idx[sel]] = (dst[idx[sel]] + contrib[sel]).astype(F4)
+
+
+def emu_grad(U, V, batch, g, fault=None, E=None):
+    """The scatter of mfcd_orc_grad from fp32 coefficients g -> dict(gradU, gradV) fp32.  E: elements per workgroup (for
+    the fault that leaves the partial last block of a table unwritten)."""
+    assert fault is None or fault in PART_FAULTS
+    U, V = np.ascontiguousarray(U, dtype=F4), np.ascontiguousarray(V, dtype=F4)
+    u, i, j = (np.asarray(t, dtype=np.int64) for t in batch[:3])
+    g = np.asarray(g, dtype=F4)[:, None]
+    n = U.shape[0]
+    drop = fault == "drop_second_hit"
+    with np.errstate(all="ignore"):
+        W = (V[i] - V[j]).astype(F4)
+        gu = (g * U[u]).astype(F4)
+        # the seam fault: rows [n + 1) of one stacked table, hits of V row 0 land in U's last row
+        dU, dVi, dVj = np.zeros((n + 1,) + U.shape[1:], F4), np.zeros_like(V), np.zeros_like(V)
+        _scatter32(dU, u, (g * W).astype(F4), drop)
+        if fault == "seam":
+            for idx, c in ((i, gu), (j, -gu)):
+                hit = idx == 0
+                _scatter32(dU, np.full(int(hit.sum()), n - 1), c[hit], False)
+                _scatter32(dVi, idx[~hit], c[~hit], False)
+        else:
+            _scatter32(dVi, i, gu, drop)
+            _scatter32(dVj, j, gu if fault == "flip_j_sign" else -gu, drop)
+        out = dict(gradU=dU[:n], gradV=(dVi + dVj).astype(F4))
+    if fault == "partial_block_unwritten":
+        for k in out:
+            flat = out[k].reshape(-1)
+            flat[(flat.size // E) * E:] = F4(1.0)
+    return out
+
+
+def emu_adam(state, gradU, gradV, h, step, fault=None, E=None):
+    """mfcd_orc_adam on both tables -> dict of the six tables."""
+    assert fault is None or fault in PART_FAULTS
+    out = {}
+    gradU, gradV = np.asarray(gradU, F4), np.asarray(gradV, F4)
+    if fault == "seam":
+        gradV = gradV.copy()
+        gradV[0] = gradU[-1]
+    for T, g in (("U", gradU), ("V", gradV)):
+        P, m, v = (np.asarray(state[k + T], F4) for k in ("", "m", "v"))
+        P1, m1, v1 = _adam32(P, m, v, g, h, step, fault if fault == "bias_from_step0" else None)
+        if fault == "param_not_updated":
+            P1 = P.copy()
+        if fault == "partial_block_unwritten":
+            for new, old in ((P1, P), (m1, m), (v1, v)):
+                new.reshape(-1)[(new.size // E) * E:] = old.reshape(-1)[(new.size // E) * E:]
+        out[T], out["m" + T], out["v" + T] = P1, m1, v1
+    return out
+
+
+def emu_apply(state, batch, g, h, step, fault=None, E=None):
+    gr = emu_grad(state["U"], state["V"], batch, g, fault if fault in ("flip_j_sign", "drop_second_hit", "seam") else None)
+    return emu_adam(state, gr["gradU"], gr["gradV"], h, step, None if fault == "seam" else fault, E)
+
+
+# ---- the inputs both test files run ----------------------------------------------------------------------------------
+EVAL_ROWS = {1: (300, 290), 2: (41, 40), 3: (97, 53), 63: (64, 50), 64: (70, 45), 65: (45, 60), 100: (120, 80),
+             256: (60, 41), 1024: (40, 43), 8: (300, 200)}
+EVAL_D = (1, 2, 3, 63, 64, 65, 100, 256, 1024)
+EVAL_NB = ((1, 1), (5, 64), (15, 16), (17, 16), (64 * 9 + 5, 64), (1000, 1000))
+EVAL_NB_BIG = ((2 * 8192 + 3, 8192), (16384 + 7, 16384))          # at d = 8 only
+EVAL_FAMILIES = ("uniform", "soft", "saturated", "half")
+
+
+def eval_cases():
+    """-> [(d, N, B, family)] of the evaluation tests."""
+    return [(d, N, B, fam) for d in EVAL_D for N, B in EVAL_NB for fam in EVAL_FAMILIES] + \
+        [(8, N, B, fam) for N, B in EVAL_NB_BIG for fam in EVAL_FAMILIES]
+
+
+# At d = 1024 the worst-case (X) gives dp ~ 1.4e-5 against scores of size sqrt(2 / d) = 0.044: about one random sample in
+# 1000 is undecided there, and the first draw of these two inputs put 3 into one batch of 1000: another draw, same cap
+EVAL_SEED = {(1024, 1000, 1000, "soft"): 1, (1024, 1000, 1000, "half"): 1}
+
+
+def eval_input(d, N, B, fam, bf16=False):
+    n, m = EVAL_ROWS[d]
+    data = part_family(fam, n, m, d, B, N, EVAL_SEED.get((d, N, B, fam), 0))
+    if bf16:
+        data["U"], data["V"] = bf16_round(data["U"]), bf16_round(data["V"])
+    return data
+
+
+COEF_B = (1, 3, 4, 5, 64, 1001)
+COEF_SUBSETS = tuple((bool(k & 1), bool(k & 2), bool(k & 4)) for k in (7, 1, 2, 4, 3, 5, 6, 0))    # (g, term, p) present
+
+
+def coef_cases():
+    """-> [(d, B, divisor, family, (g, term, p present))]: tables of 50 x 40 rows."""
+    out = []
+    for a, B in enumerate(COEF_B):
+        for b, fam in enumerate(EVAL_FAMILIES):
+            for c, mult in enumerate((1, 8)):
+                k = 8 * a + 2 * b + c
+                out.append(((5, 64, 100)[k % 3], B, mult * B, fam, COEF_SUBSETS[(a + 2 * b + c) % 8]))
+    return out
+
+
+GRAD_FAMILIES = ("uniform", "one_user", "repeat", "ij_cross", "half")
+GRAD_SHAPES = {3: (300, 200, 64), 5: (300, 200, 64), 4: (300, 290, 64), 255: (37, 23, 32), 1023: (9, 8, 16),
+               64: (37, 23, 32), 256: (37, 23, 32), 1024: (9, 8, 16)}        # d -> (n, m, B)
+
+
+def grad_cases():
+    """-> [(label, n, m, d, B, family, seed)]: one batch each.  The streaming shapes of CASES (their own family; batch =
+    the whole first batch) and d in {3, 5, 255, 1023} (scalar access, rows that span workgroups) and {4, 64, 256, 1024}
+    with every family of GRAD_FAMILIES; last the autograd shape (200, 150, 16) with B = 20000."""
+    out = [("stream-" + c["label"], c["n"], c["m"], c["d"], c["B"], c["family"], c["seed"]) for c in STREAMING]
+    out += [(f"d{d}-{fam}", n, m, d, B, fam, 0) for d, (n, m, B) in GRAD_SHAPES.items() for fam in GRAD_FAMILIES]
+    return out + [("autograd", 200, 150, 16, 20000, "uniform", 0)]
+
+
+def grad_input(case):
+    label, n, m, d, B, fam, seed = case
+    if fam == "fuzz":
+        data = family("fuzz", n, m, d, B, 1462)
+        return {k: (v[:B] if k in "uijz" else v) for k, v in data.items()}
+    return part_family(fam, n, m, d, B, B, seed)
+
+
+def signed_coefficients(B, seed=0):
+    """Coefficients for mfcd_dense_grad_from_coefficients / mfcd_apply_step: N(0, 1) / B with exact zeros and values of
+    size 1e4 among them."""
+    rng = np.random.default_rng([11, B, seed])
+    g = rng.standard_normal(B) / B
+    g[rng.random(B) < 0.15] = 0.0
+    big = rng.random(B) < 0.1
+    g[big] = 1e4 * np.sign(rng.standard_normal(int(big.sum())))
+    return g.astype(np.float32)
+
+
+# mfcd_adam_dense: (label, n, m, d, start, hyper, aligned).  The small shapes take every state and both hyper-parameter
+# sets; the four multi-chunk shapes (4.2 M elements at most) take one each.
+ADAM_SHAPES = (("one_block", 3, 2, 4), ("partial_a", 37, 41, 12), ("partial_b", 300, 7, 100))
+ADAM_BIG = (("v4c2", 4100, 4100, 256, 0, {}), ("v4c4", 8200, 8200, 256, 500, {}),
+            ("v1c2", 1100, 1100, 251, 10 ** 6, {}), ("v1c4", 2100, 2100, 251, 0, {"lr": 0.0}))
+
+
+def adam_cases():
+    out = [(f"{lab}-s{start}-{'lr0' if hy else 'def'}", n, m, d, start, hyper(**hy), True)
+           for lab, n, m, d in ADAM_SHAPES for start in (0, 500, 10 ** 6) for hy in ({}, {"lr": 0.0})]
+    out += [(lab, n, m, d, start, hyper(**hy), True) for lab, n, m, d, start, hy in ADAM_BIG]
+    return out + [("misaligned", 37, 41, 64, 500, hyper(), False)]
+
+
+def adam_input(case):
+    """-> (state, gradU, gradV, step, special): the gradient mixes normal values, exact zeros, subnormals, values next to
+    -wd P and a handful of +-inf and NaN (special: their flat positions per table)."""
+    label, n, m, d, start, h, aligned = case
+    rng = np.random.default_rng([13, n, m, d, start])
+    U = (rng.standard_normal((n, d)) / np.sqrt(d)).astype(np.float32)
+    V = (rng.standard_normal((m, d)) / np.sqrt(d)).astype(np.float32)
+    st = preset_state(U, V, start) if start else fresh_state(U, V)
+    grads, special = [], {}
+    for T in ("U", "V"):
+        P = st[T]
+        g = 1e-3 * rng.standard_normal(P.shape)
+        kind = rng.random(P.shape)
+        g[kind < 0.10] = 0.0
+        sub = (kind >= 0.10) & (kind < 0.15)
+        g[sub] = rng.integers(-2 ** 20, 2 ** 20, int(sub.sum())) * 2.0 ** -149
+        near = (kind >= 0.15) & (kind < 0.25)
+        g[near] = (-h["wd"] * P.astype(np.float64) * (1.0 + 1e-5 * rng.standard_normal(P.shape)))[near]
+        g = g.astype(np.float32)
+        flat = g.reshape(-1)
+        pos = rng.choice(flat.size, size=min(6, flat.size // 3), replace=False)
+        flat[pos] = np.array([np.inf, -np.inf, np.nan, np.inf, np.nan, -np.inf], dtype=np.float32)[:len(pos)]
+        grads.append(g)
+        special[T] = np.sort(pos)
+    return st, grads[0], grads[1], start + 1, special
