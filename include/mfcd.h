@@ -1426,6 +1426,55 @@ int mfcd_implicit_fold_in_users(const float *V, int m, int d, const int64_t *pos
                                 float *U_out, double *objective, double *grad_ratio, int32_t *iters_status, double *info,
                                 void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * The Plackett–Luce loss of ranked lists and its gradient in the scores, over ragged rows (no reference counterpart: the
+ * reference's BTL triplet is a list of two).  CSR layout as mfcd_pair_ragged_stats: row r owns entries
+ * [row_off[r], row_off[r + 1]) of a [entries], the model's scores of the L items shown to it, in rank order, best first.
+ * depth [rows] int32 (NULL: every row fully ranked) is the number of ranked positions, 0 <= depth <= L: the entries past
+ * it are an unordered tail, shown and not ranked.  stages = min(depth, L - 1): the choice out of one item carries
+ * nothing.  Per row, with k, l counted from 0,
+ *     lse_k = log sum_{l >= k} exp(a_l)
+ *     loss  = sum_{k < stages} (lse_k - a_k)                       the negative log-likelihood of the stages' choices
+ *     g_l   = sum_{k <= l, k < stages} exp(a_l - lse_k) - [l < stages]         its gradient in a_l
+ *     hits  = the stages k with a_k >= a_l for every l >= k         (the choices the model would have made; ties count)
+ *   what     bit 1: loss [rows] f64 and counts [rows][2] int64 = (stages, hits); bit 2: g [entries] fp32.
+ *   status   [rows] int32: 0, or 2 for a row that fails validation.
+ * Arithmetic.  Both sums are scans over the log-sum-exp monoid: lse is a reverse scan of a, and with
+ * N_l = log sum_{k <= l, k < stages} exp(-lse_k), a forward scan, g_l = exp(a_l + N_l) - [l < stages].  An element is a
+ * (max, sum scaled by exp(-max)) pair in f64, joined as an online softmax joins them, so every exponent is <= 0: nothing
+ * overflows, and no suffix sum underflows to 0 however far apart the scores lie (exp(a - row max) followed by a plain
+ * suffix sum does, for exactly the confident, well-fitted rows).  A pair stays a pair to the end: exp(-lse_k) enters the
+ * forward scan as (-max_k, 1 / sum_k), the loss term is (max_k - a_k) + log sum_k, g_l = exp(a_l + M_l) S_l - [l < stages].
+ * exp, log and the sums are f64; g is rounded to fp32 once.  tests/list_pl_model.py is the same function in numpy
+ * (np.logaddexp.accumulate in both directions; it folds each pair into one f64, so it loses the log of a count next to
+ * a score of the size of 1e17 or more, where the kernel does not).
+ * Tiles.  A row is cut into tiles of TILE = mfcd_list_pl_tile() = 256 entries; the caller passes tile_off [rows + 1], the
+ * prefix sum of ceil(L_r / TILE), and its total n_tiles (the host cannot see row_off, and the entry has no host wait).  A
+ * first kernel validates every row before any entry of it is read: 0 <= row_off[r] <= row_off[r + 1] <= entries,
+ * L <= 1 048 576, 0 <= depth[r] <= L, tile_off[r + 1] - tile_off[r] = ceil(L / TILE) inside [0, n_tiles], and every tile
+ * of the row found by the binary search over tile_off.  Then one 256-thread workgroup per tile, one entry per thread.  A
+ * row of one tile does both scans in its workgroup.  A longer row (a full catalogue is one row) is reduced, then
+ * scanned: the tiles' reverse aggregates, a one-wave pass per row that turns them into carries, a tile pass that forms
+ * lse_k, the tile's loss and hit partials and its forward aggregate, a second one-wave pass that forms the forward
+ * carries and adds the row's partials in tile order, and the tile pass that writes g.  Every dependency is a kernel
+ * boundary: no workgroup waits on another.  No floating-point atomics, every sum has one owner and a fixed order that
+ * depends on the row alone: two calls are bit-equal, what = 1 / what = 2 are bit-equal to the matching half of what = 3,
+ * and a row's outputs do not depend on the other rows of the call or on its position in it.
+ * Rows.  A row that fails validation gets status 2, a NaN loss, counts -1 and none of its entries of g written; no address
+ * is formed from its offsets.  A row with a non-finite score gets a NaN loss, counts -1, an all-NaN slice of g and status
+ * 0; the other rows are untouched.  L <= 1 or depth 0 gives a +0 loss, counts (0, 0) and +0 in g.
+ * Limits: rows >= 0 (0 = success, nothing launched), entries >= 0, 0 <= n_tiles <= 2^40, what in {1, 2, 3} with its
+ * outputs present (g where entries > 0, and not a), a where entries > 0, row_off, tile_off and status; MFCD_EINVAL
+ * outside them and MFCD_EWORKSPACE for a short workspace, before anything touches the device.  workspace:
+ * mfcd_list_pl_workspace_bytes(rows, n_tiles), 88 bytes per tile and 4 per row, each region rounded up to 256 (0 = sizes
+ * out of range), 256-byte aligned; launches are cut to 2^20 workgroups.  No allocation and no host wait.
+ */
+int mfcd_list_pl_tile(void);
+size_t mfcd_list_pl_workspace_bytes(int rows, int64_t n_tiles);
+int mfcd_list_pl(const float *a, int64_t entries, const int64_t *row_off, const int32_t *depth, int rows,
+                 const int64_t *tile_off, int64_t n_tiles, int what, double *loss, int64_t *counts, float *g,
+                 int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@ from mfcd import foldin as _foldin
 from mfcd import implicit as _implicit
 from mfcd import implicit_exact as _implicit_exact
 from mfcd import implicit_foldin as _implicit_foldin
+from mfcd import lists as _lists
 from mfcd import metrics as _metrics
 from mfcd import newton as _newton
 from mfcd import pairs as _pairs
@@ -373,6 +374,82 @@ def compute_ratings_metrics(model, data, s=1.0, skip_ties=False):
     layout."""
     _need_gpu(model.U.device)
     return _ratings.ratings_metrics(model.U.data, model.V.data, data, s, skip_ties)
+
+
+def observe_rankings(X, length, depth=None, s=1.0, seed=0):
+    """Extension (not in the reference): ranked lists from a dense X — every user is shown `length` items, a uniform draw
+    without replacement, and orders them by s x + Gumbel noise, an exact Plackett–Luce draw with scores s x (s = inf: the
+    noiseless order); depth=K keeps the order of the best K only, the rest is an unordered tail.  The draw comes from a
+    private torch.Generator(seed) on X's device (the global torch and numpy RNG states are not touched).  Returns an
+    mfcd.lists.RankedLists on X's device: what `rankings_risk`, `train_model_rankings` and `compute_rankings_metrics`
+    take.  Not part of the result dict / .pkl layout."""
+    return _lists.sample_rankings(X, length, depth, s, seed)
+
+
+def load_rankings(path, sep=None, depth=None):
+    """Extension (not in the reference): reads a text file of `user item position [ignored columns]` lines (sep=None: any
+    white space) with numpy; the user and item ids are mapped to 0..n-1 and 0..m-1 in the order of their sorted unique
+    values, as `load_ratings` maps them; a user's items are ordered by position, smallest first = best.  Returns
+    (lists, user_ids, item_ids): an mfcd.lists.RankedLists on the CPU (`.to(device)` moves it) and the id of every row
+    and column.  Not part of the result dict / .pkl layout."""
+    table = np.loadtxt(path, delimiter=sep, usecols=(0, 1, 2), ndmin=2, dtype=np.float64)
+    user_ids, users = np.unique(table[:, 0], return_inverse=True)
+    item_ids, items = np.unique(table[:, 1], return_inverse=True)
+    if (user_ids == np.round(user_ids)).all() and (item_ids == np.round(item_ids)).all():
+        user_ids, item_ids = user_ids.astype(np.int64), item_ids.astype(np.int64)
+    if (table[:, 2] != np.round(table[:, 2])).any():
+        raise ValueError("positions must be integers")
+    lists = _lists.RankedLists(users.reshape(-1), items.reshape(-1), table[:, 2].astype(np.int64), user_ids.size,
+                               item_ids.size, depth)
+    return lists, user_ids, item_ids
+
+
+def rankings_risk(model, lists):
+    """Extension (not in the reference): the Plackett–Luce risk of the model on ranked lists as a differentiable scalar —
+    over every user the negative log-likelihood of the list as a sequence of softmax choices out of the items that
+    remain, divided by the number of such choices of all users.  Returns a 0-dim fp32 tensor on the model's device;
+    `.backward()` fills `model.U.grad` / `model.V.grad` (include/mfcd.h mfcd_list_pl, mfcd_ragged_gather_sum).  fp32
+    models only; lists: an mfcd.lists.RankedLists on the model's device.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _lists.pl_risk(model.U, model.V, lists)
+
+
+def train_model_rankings(model, lists, optimizer, device, num_steps=1000, log_every=100):
+    """Extension (not in the reference): `train_model_ratings` on `rankings_risk(model, lists)` — full-batch optimiser
+    steps on the Plackett–Luce risk of the ranked lists.  Returns (steps, risks) as `train_model_population` does.
+    torch.optim.Adam takes the fused loop (mfcd.lists.fit_lists), any other optimiser zero_grad / rankings_risk /
+    backward / step.  Not part of the result dict / .pkl layout."""
+    _need_gpu(device)
+    model.train()
+    if _engine.fused_step_applies(model, optimizer):
+        out = _lists.fit_lists(_engine.AdamBinding(model, optimizer), lists, num_steps, log_every)
+    else:
+        at, seen = [], []
+        for t in range(int(num_steps)):
+            optimizer.zero_grad()
+            loss = rankings_risk(model, lists)
+            loss.backward()
+            optimizer.step()
+            if log_every > 0 and t % log_every == 0:
+                at.append(t)
+                seen.append(loss.detach())
+        if log_every > 0:
+            with torch.no_grad():
+                at.append(int(num_steps))
+                seen.append(rankings_risk(model, lists))
+        out = (at, torch.stack(seen).double().cpu().tolist() if seen else [])
+    model.eval()
+    return out
+
+
+def compute_rankings_metrics(model, lists):
+    """Extension (not in the reference): the model's metrics on ranked lists, typically a held-out split (`lists.split`):
+    `choice_log_likelihood`, `choice_accuracy`, `uniform_log_likelihood` (the all-equal model's, in closed form) and
+    `kendall_tau` among the ranked entries, each as the mean over the users and as a `_per_user` array (include/mfcd.h
+    mfcd_list_pl, mfcd_pair_ragged_stats); a user whose list records no choice is NaN and stays out of the means.
+    Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _lists.pl_metrics(model.U.data, model.V.data, lists)
 
 
 def compute_ranking_metrics(model, test, train=None, ks=(10,), min_value=None, users=None):
