@@ -1475,6 +1475,42 @@ int mfcd_list_pl(const float *a, int64_t entries, const int64_t *row_off, const 
                  const int64_t *tile_off, int64_t n_tiles, int what, double *loss, int64_t *counts, float *g,
                  int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * The Hessian of mfcd_list_pl's loss in the scores, applied to a score-space vector y [entries], and its diagonal: the
+ * second-order twin of mfcd_list_pl on the same layout (a, row_off, depth, tile_off, n_tiles as there; no reference
+ * counterpart).  Per row, with p_{k,l} = exp(a_l - lse_k) for l >= k, the softmax of stage k over what remains,
+ *     ybar_k = sum_{j >= k} p_{k,j} y_j                                     a softmax-weighted mean: |ybar_k| <= max |y|
+ *     q_l    = sum_{k <= l, k < stages} p_{k,l} (y_l - ybar_k)              H y, H = sum_k (diag(p_k) - p_k p_k^T)
+ *     deg_l  = sum_{k <= l, k < stages} p_{k,l} (1 - p_{k,l})               H_ll >= 0
+ *   q        [entries] fp32.  deg [entries] fp32 or NULL: the diagonal is formed only where it is asked for.
+ *   status   [rows] int32: 0, or 2 for a row that fails validation.
+ * Arithmetic.  The gradient's two scans over the same monoid with a linear payload riding along.  The reverse scan joins
+ * (a_j, 1, y_j) into (m_k, s_k, t_k), t_k = sum_{j >= k} exp(a_j - m_k) y_j: s and t are scaled by the same factor in
+ * every join (one exp per join, as in mfcd_list_pl), and ybar_k = t_k / s_k.  The forward scan joins the stages'
+ * (-m_k, 1 / s_k, ybar_k / s_k) into (M_l, S_l, W_l): q_l = exp(a_l + M_l) (y_l S_l - W_l), the exponent <= 0.  The
+ * diagonal takes a second forward scan, of (-2 m_k, 1 / s_k^2) into (M2_l, S2_l):
+ * deg_l = exp(a_l + M_l) S_l - exp(2 a_l + M2_l) S2_l, held at 0 from below.  All of it f64, q and deg rounded to fp32
+ * once; nothing under- or overflows for finite fp32 a and y.  m and s never see the payload, so deg does not depend on y
+ * and q is bit-equal with and without deg.  tests/list_pl_hvp_model.py is the same function in numpy by another route.
+ * Tiles, validation and the decomposition are mfcd_list_pl's: the status pass before any entry is read; a row of one tile
+ * does everything in its workgroup in the last launch; a longer row goes through aggregate, carry, middle, carry and the
+ * final pass, every dependency a kernel boundary, no workgroup waiting on another.  No floating-point atomics, every sum
+ * has one owner and an order that depends on the row alone: two calls are bit-equal and a row's outputs do not depend on
+ * the other rows of the call or on its position in it.
+ * Rows.  A row that fails validation gets status 2 and none of its entries of q or deg written.  A row with a non-finite
+ * score or a non-finite entry of y gets an all-NaN slice of q (and deg) and status 0; the other rows are untouched.
+ * L <= 1 or depth 0 gives +0.
+ * Limits: rows >= 0 (0 = success, nothing launched), entries >= 0, 0 <= n_tiles <= 2^40; a, y and q where entries > 0;
+ * q is neither a nor y, deg none of q, a, y; row_off, tile_off and status; MFCD_EINVAL outside them and MFCD_EWORKSPACE
+ * for a short workspace, before anything touches the device.  workspace: mfcd_list_pl_hvp_workspace_bytes(rows, n_tiles),
+ * 136 bytes per tile and 4 per row, each region rounded up to 256 (0 = sizes out of range), 256-byte aligned; launches
+ * are cut to 2^20 workgroups.  No allocation and no host wait.
+ */
+size_t mfcd_list_pl_hvp_workspace_bytes(int rows, int64_t n_tiles);
+int mfcd_list_pl_hvp(const float *a, const float *y, int64_t entries, const int64_t *row_off, const int32_t *depth,
+                     int rows, const int64_t *tile_off, int64_t n_tiles, float *q, float *deg, int32_t *status,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,49 +27,9 @@
 // owner and a fixed order that depends on the row alone, so two calls are bit-equal, a row's bytes do not depend on its
 // place in the call, and what = 1 / what = 2 are the matching halves of what = 3.  The tile kernels read status[r] and
 // return for a row that failed: no address is formed from its offsets.
-#include <cmath>
-
-#include "common.h"
-#include "pairs_common.h"
+#include "list_common.h"
 
 namespace {
-
-constexpr int kPlTile = 256;                           // entries per tile = threads per workgroup (mfcd_list_pl_tile)
-constexpr int kPlWaves = kPlTile / MFCD_WAVE;
-
-// An element of the monoid: log of a sum of exponentials, as m + log(s).  The identity has s = 0 and an m below every
-// finite score and every -lse: joined with anything its side is scaled by exp(-huge) = 0, with itself by exp(0) = 1.
-struct Lse {
-    double m, s;
-};
-__device__ __forceinline__ Lse lse_none() { return Lse{-1.0e300, 0.0}; }
-
-// One exp per join; symmetric in its arguments bit for bit.
-__device__ __forceinline__ Lse lse_join(const Lse x, const Lse y)
-{
-    const bool xb = x.m >= y.m;
-    const double hi = xb ? x.m : y.m, lo = xb ? y.m : x.m;
-    const double e = exp(lo - hi);
-    return Lse{hi, xb ? x.s + y.s * e : y.s + x.s * e};
-}
-
-__device__ __forceinline__ Lse lse_shfl(const Lse v, int src)
-{
-    return Lse{__shfl(v.m, src, MFCD_WAVE), __shfl(v.s, src, MFCD_WAVE)};
-}
-
-// Inclusive scan over the wave's lanes: towards higher lanes (a prefix), or with REVERSE towards lower ones (a suffix).
-template <bool REVERSE>
-__device__ __forceinline__ Lse lse_wave_scan(Lse v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < MFCD_WAVE; off <<= 1) {
-        const int src = REVERSE ? lane + off : lane - off;
-        const Lse t = lse_shfl(v, src & (MFCD_WAVE - 1));
-        if (REVERSE ? src < MFCD_WAVE : src >= 0) v = lse_join(t, v);
-    }
-    return v;
-}
 
 struct PlTileRec {                                     // the workspace's record of one tile of a row of >= 2 tiles
     Lse rev, rev_carry;                                // the tile's reverse aggregate; that of the row's later tiles
@@ -95,8 +55,6 @@ struct PlArgs {
     int32_t *row_bad;
 };
 
-__device__ __forceinline__ double pl_qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
 // One wave per row: the validation of the header, before anything reads the row, and the outputs of a row that failed
 // or has no tile.
 __global__ __launch_bounds__(256) void pl_status_kernel(const PlArgs g)
@@ -105,74 +63,13 @@ __global__ __launch_bounds__(256) void pl_status_kernel(const PlArgs g)
     const int64_t rr = (int64_t)blockIdx.x * kPlWaves + (threadIdx.x >> 6);
     if (rr >= g.rows) return;
     const int r = (int)rr;
-    const int64_t b = g.row_off[r], e = g.row_off[r + 1], s0 = g.tile_off[r], s1 = g.tile_off[r + 1];
-    bool ok = b >= 0 && e >= b && e <= g.entries && e - b <= kPairMaxCols && s0 >= 0 && s1 >= s0 && s1 <= g.n_tiles;
-    if (ok) ok = s1 - s0 == (e - b + kPlTile - 1) / kPlTile;
-    if (ok && g.depth) ok = g.depth[r] >= 0 && g.depth[r] <= e - b;
-    if (ok)                                            // at most 4096 tiles
-        for (int64_t t = s0 + lane; t < s1; t += MFCD_WAVE) ok &= trip_find_row(g.tile_off, g.rows, t) == r;
-    ok = __ballot(!ok) == 0;
+    const bool ok = pl_row_valid(g.row_off, g.tile_off, g.depth, g.rows, g.entries, g.n_tiles, r, lane);
     if (lane != 0) return;
     g.status[r] = ok ? 0 : 2;
-    if ((g.what & 1) && (!ok || e == b)) {
+    if ((g.what & 1) && (!ok || g.row_off[r + 1] == g.row_off[r])) {
         g.loss[r] = ok ? 0.0 : pl_qnan();
         g.counts[2 * (int64_t)r] = g.counts[2 * (int64_t)r + 1] = ok ? 0 : -1;
     }
-}
-
-// The tile's row and place in it, or false: nothing of a row that failed validation is touched.
-struct PlTile {
-    int r, I, T, len, stages;
-    int64_t b;
-};
-
-__device__ __forceinline__ bool pl_tile(const PlArgs &g, int64_t t, PlTile *out)
-{
-    const int r = trip_find_row(g.tile_off, g.rows, t);
-    if (g.status[r] != 0) return false;
-    const int64_t s0 = g.tile_off[r], s1 = g.tile_off[r + 1];
-    if (t < s0 || t >= s1) return false;
-    out->r = r;
-    out->I = (int)(t - s0);
-    out->T = (int)(s1 - s0);
-    out->b = g.row_off[r];
-    out->len = (int)(g.row_off[r + 1] - out->b);
-    const int depth = g.depth ? g.depth[r] : out->len;
-    out->stages = depth < out->len - 1 ? depth : out->len - 1;
-    return true;
-}
-
-// The join of the workgroup's 256 elements, in thread 0 (the other threads' return value is not used): the waves by an
-// xor butterfly, then the four wave values in order.
-__device__ __forceinline__ Lse pl_block_join(Lse v, int tid, Lse (&sh)[kPlWaves])
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = lse_join(v, lse_shfl(v, (tid & 63) ^ off));
-    __syncthreads();                                   // the previous use's readers are done
-    if ((tid & 63) == 0) sh[tid >> 6] = v;
-    __syncthreads();
-    Lse out = sh[0];
-    for (int w = 1; w < kPlWaves; ++w) out = lse_join(out, sh[w]);
-    return out;
-}
-
-// Inclusive scan over the workgroup's 256 elements in thread order (REVERSE: a suffix), joined with `carry`, what lies
-// beyond the tile on the side the scan comes from.
-template <bool REVERSE>
-__device__ __forceinline__ Lse pl_block_scan(Lse v, const Lse carry, int tid, Lse (&sh)[kPlWaves])
-{
-    const int lane = tid & 63, wave = tid >> 6;
-    v = lse_wave_scan<REVERSE>(v, lane);
-    __syncthreads();                                   // the previous use's readers are done
-    if (lane == (REVERSE ? 0 : MFCD_WAVE - 1)) sh[wave] = v;
-    __syncthreads();
-    Lse rest = carry;                                  // the waves beyond this one, the farthest first
-    if (REVERSE) {
-        for (int w = kPlWaves - 1; w > wave; --w) rest = lse_join(rest, sh[w]);
-    } else {
-        for (int w = 0; w < wave; ++w) rest = lse_join(rest, sh[w]);
-    }
-    return lse_join(v, rest);
 }
 
 // Sums over the workgroup → thread 0: the waves by the xor butterfly, the wave sums in ascending order.

@@ -160,6 +160,8 @@ SIGNATURES = {
     "mfcd_list_pl_tile": (_i32, []),
     "mfcd_list_pl_workspace_bytes": (_sz, [_i32, _i64]),
     "mfcd_list_pl": (_i32, [_vp, _i64, _vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mfcd_list_pl_hvp_workspace_bytes": (_sz, [_i32, _i64]),
+    "mfcd_list_pl_hvp": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 TUNE_KEYS = {"resident_lookahead": 3, "resident_spin_limit": 5, "uvt_target_wgs": 9, "uvt_min_stages": 10,

@@ -6,7 +6,9 @@ of the slate S" is depth 1, the BTL triplet a list of two.
 transposition and the tile and segment offsets the entries need; every host read happens there, once per dataset.
 `list_scores` and `pl_rows` are the kernel calls, `pl_risk` the mean negative log-likelihood per choice as a
 differentiable scalar, `pl_metrics` the held-out metrics, `fit_lists` the fused loop of scores, list kernel, two
-gather-sums and one dense Adam step, `sample_rankings` an exact Plackett–Luce draw from a dense truth.  The scores, the
+gather-sums and one dense Adam step, `sample_rankings` an exact Plackett–Luce draw from a dense truth.  `pl_hvp_rows` is
+the loss's Hessian in the scores applied to a vector, with its diagonal (mfcd_list_pl_hvp), `pl_hvp` the Hessian of
+`pl_risk` in both tables applied to a direction; mfcd/lists_exact.py builds the exact block steps on them.  The scores, the
 gather-sums and the Kendall counts are ratings.py's entries (mfcd_ragged_dot, mfcd_ragged_gather_sum,
 mfcd_pair_ragged_stats) on this layout.  There is no CPU form of the kernel calls."""
 import numpy as np
@@ -166,6 +168,28 @@ def pl_rows(a, lists, what="both"):
     return loss, counts, g, status
 
 
+def pl_hvp_rows(a, y, lists, deg=False):
+    """Scores a and a score-space vector y, fp32 [entries] on the GPU, in the lists' order → (q fp32 [entries], status
+    int32 [n]), or with deg=True (q, deg, status): the Hessian of the users' list losses of `pl_rows` with respect to the
+    scores, applied to y, and its diagonal (mfcd_list_pl_hvp) — per user the sum over the stages of diag(p_k) - p_k p_k^T,
+    p_k the softmax of the scores that remain at stage k.  A user with a non-finite score or entry of y gets NaN.
+    Deterministic; q does not depend on `deg`, deg does not depend on y."""
+    a = _need(a, torch.float32, "pl_hvp_rows", "the scores")
+    y = _need(y, torch.float32, "pl_hvp_rows", "the vector")
+    _need_lists(lists, "pl_hvp_rows")
+    if a.numel() != lists.entries or y.numel() != lists.entries:
+        raise ValueError(f"{a.numel()} scores and a vector of {y.numel()} for {lists.entries} list entries")
+    L, dev, n = _lib.load(), a.device, lists.n
+    q = torch.empty_like(a)
+    d = torch.empty_like(a) if deg else None
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    ws = _lib.workspace(L.mfcd_list_pl_hvp_workspace_bytes(n, lists.n_tiles), dev)
+    _lib.check(L.mfcd_list_pl_hvp(_lib.ptr(a), _lib.ptr(y), lists.entries, _lib.ptr(lists.row_off), _lib.ptr(lists.depth), n,
+                                  _lib.ptr(lists.tile_off), lists.n_tiles, _lib.ptr(q), _lib.ptr(d), _lib.ptr(status),
+                                  _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+    return (q, d, status) if deg else (q, status)
+
+
 def _stages(lists):
     if lists.stages <= 0:
         raise ValueError("the lists record no choice: no user has two entries and a ranked position")
@@ -206,6 +230,31 @@ def pl_risk(U, V, lists):
         _need(t, torch.float32, "the list risk", name)
     _need_lists(lists, "the list risk")
     return _PlRisk.apply(U, V, lists, _stages(lists))
+
+
+def pl_hvp(U, V, dU, dV, lists, gauss_newton=False):
+    """The Hessian of `pl_risk` with respect to both tables, applied to a direction (dU, dV) of their shapes → (HU, HV)
+    fp32, as `ratings.ratings_hvp` on ranked lists: with dA = dU[user] . V[item] + U[user] . dV[item] over the entries,
+    q = `pl_hvp_rows`(a, dA), g = `pl_rows`(a, "grad") and c = 1 / lists.stages,
+        HU = c [gather_sum(q, V) + gather_sum(g, dV)] by user,   HV = c [gather_sum(q, U) + gather_sum(g, dU)] by item.
+    gauss_newton=True drops the two g terms: the positive semi-definite part.  fp32 GPU tensors; nothing is modified."""
+    tables = [_need(t, torch.float32, "the list Hessian-vector product", name)
+              for name, t in (("U", U), ("V", V), ("dU", dU), ("dV", dV))]
+    _need_lists(lists, "the list Hessian-vector product")
+    U, V, dU, dV = (t.detach() for t in tables)
+    if dU.shape != U.shape or dV.shape != V.shape:
+        raise ValueError(f"a direction of shapes {tuple(dU.shape)}, {tuple(dV.shape)} for tables {tuple(U.shape)}, "
+                         f"{tuple(V.shape)}")
+    c = 1.0 / _stages(lists)
+    a = list_scores(U, V, lists)[0]
+    dA = list_scores(dU, V, lists)[0].add_(list_scores(U, dV, lists)[0])
+    q = pl_hvp_rows(a, dA, lists)[0]
+    HU, HV = _table_grads(q, lists, U, V)
+    if not gauss_newton:
+        g = pl_rows(a, lists, "grad")[2]
+        gU, gV = _table_grads(g, lists, dU, dV)
+        HU, HV = HU.add_(gU), HV.add_(gV)
+    return HU.mul_(c), HV.mul_(c)
 
 
 _KEYS = ("choice_log_likelihood", "choice_accuracy", "uniform_log_likelihood", "kendall_tau")

@@ -28,6 +28,7 @@ from mfcd import implicit as _implicit
 from mfcd import implicit_exact as _implicit_exact
 from mfcd import implicit_foldin as _implicit_foldin
 from mfcd import lists as _lists
+from mfcd import lists_exact as _lists_exact
 from mfcd import metrics as _metrics
 from mfcd import newton as _newton
 from mfcd import pairs as _pairs
@@ -450,6 +451,67 @@ def compute_rankings_metrics(model, lists):
     Not part of the result dict / .pkl layout."""
     _need_gpu(model.U.device)
     return _lists.pl_metrics(model.U.data, model.V.data, lists)
+
+
+def rankings_hvp(model, lists, dU, dV, gauss_newton=False):
+    """Extension (not in the reference): `ratings_hvp` on ranked lists — the Hessian of `rankings_risk(model, lists)`
+    with respect to the factor tables, applied to the direction (dU [n, d], dV [m, d]) → (HU, HV) fp32 on the model's
+    device (include/mfcd.h mfcd_list_pl_hvp, per user the sum over the list's stages of diag(p) - p p^T of the softmax
+    over what remains, carried to the tables by mfcd_ragged_dot and mfcd_ragged_gather_sum).  gauss_newton=True drops
+    the terms that hold the risk's gradient: the product is then positive semidefinite.  fp32 models only.  Not part of
+    the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    return _lists.pl_hvp(model.U.data, model.V.data, dU, dV, lists, gauss_newton)
+
+
+def fit_users_rankings(V_or_model, lists, weight_decay, coef=None):
+    """Extension (not in the reference): fold-in on ranked lists — with the item table held fixed, the vectors of the
+    users of `lists` from one ranked list each: for every user the minimiser of  c * (the Plackett–Luce loss of the
+    user's list) + (wd / 2) |u|^2,  started at zero (mfcd.lists_exact.lists_user_step: Newton-CG on mfcd_list_pl_hvp).
+    The users need not have been in training; lists.m must be the number of rows of V.  V_or_model: a model or a bare
+    fp32 V [m, d] on the GPU.  c = 1 / lists.stages, or `coef`: pass the training lists' 1 / stages so that the ridge
+    weighs as it did in training.  Returns the PopulationStepResult (rows [lists.n, d], status 0 certified / 1 stopped /
+    2 invalid, newton_iters, cg_iters, objective_before, objective_after, grad_ratio); a user whose list records no
+    choice gets the zero row.  weight_decay must be > 0.  Not part of the result dict / .pkl layout."""
+    V = V_or_model.V.data if hasattr(V_or_model, "V") and hasattr(V_or_model, "U") else V_or_model
+    if not torch.is_tensor(V):
+        raise TypeError("fit_users_rankings takes a model or its V table")
+    _need_gpu(V.device)
+    return _lists_exact.lists_user_step(None, V, lists, float(weight_decay), coef)
+
+
+def refit_users_rankings(model, lists, weight_decay):
+    """Extension (not in the reference): `refit_users_ratings` on ranked lists — for the model's own V, the best response
+    of every user's row on  F = rankings_risk + (wd / 2)(|U|^2 + |V|^2),  the objective whose stationary points
+    `train_model_rankings` approaches under Adam's coupled weight decay, by mfcd.lists_exact.lists_user_step started at
+    `model.U`.  Returns (result, gain): the PopulationStepResult and, per user, gain = objective_before -
+    objective_after >= 0: what the trained row still had to gain in F with V fixed.  weight_decay must be > 0.  The
+    model is not changed.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    result = _lists_exact.lists_user_step(model.U.data, model.V.data, lists, float(weight_decay))
+    return result, result.objective_before - result.objective_after
+
+
+def refit_items_rankings(model, lists, weight_decay):
+    """Extension (not in the reference): the mirror of `refit_users_rankings` — for the model's own U, the minimiser over
+    all of V of F (one problem: a user's list couples its items), by mfcd.lists_exact.lists_item_step started at
+    `model.V`.  Returns (result, gain) with result.rows the best-response V [m, d] and gain the 0-dim decrease of F.
+    weight_decay must be > 0.  The model is not changed.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.V.device)
+    result = _lists_exact.lists_item_step(model.U.data, model.V.data, lists, float(weight_decay))
+    return result, result.objective_before - result.objective_after
+
+
+def train_model_rankings_exact(model, lists, weight_decay, sweeps=10):
+    """Extension (not in the reference): `train_model_rankings` by exact block steps instead of Adam — `sweeps` sweeps of
+    one exact user step and one exact item step of  F = rankings_risk + (wd / 2)(|U|^2 + |V|^2)
+    (mfcd.lists_exact.fit_lists_exact), each a Newton-CG solve on the list Hessian, in place on the model's tables.
+    Returns F after every sub-step as a list of [after the user step, after the item step] per sweep; it does not
+    increase.  fp32 models only; weight_decay must be > 0.  Not part of the result dict / .pkl layout."""
+    _need_gpu(model.U.device)
+    result = _lists_exact.fit_lists_exact(model.U.data, model.V.data, lists, float(weight_decay), sweeps)
+    model.eval()
+    return result.history.cpu().tolist()
 
 
 def compute_ranking_metrics(model, test, train=None, ks=(10,), min_value=None, users=None):
